@@ -13,9 +13,13 @@ steps alternate between three engine instances (own activation buffers and hipGr
 the latency-bound tail of one step (top-k, NMS, small BiFPN levels, SE gates) overlaps the wide kernels of the next - the
 way a serving loop would pipeline requests.  Every timed step runs to completion inside the timed region
 (`--in-flight 1 --sub-batches 0` restores one batch at a time as two concurrent half-batches: 11.5 k instead of 12.7 k img/s).
-Rank 0 prints ONE JSON line (contract in the round prompt) that also carries
-  roofline      dominant kernel family: algorithmic HBM bytes / HIP-event time on the launch stream
+Rank 0 prints ONE JSON line: metric, value (images/sec), unit, higher_is_better, dtype, ms_per_step (one timed step).
+A plain run does only that: set up, warm up, time --steps steps, print.  --full adds, outside the timed region,
+  roofline      dominant kernel family: algorithmic HBM bytes / HIP-event time on the launch stream (--profile-out: per launch)
   cpu_baseline  the CPU oracle (oracle/, a port of the reference's PyTorch path) timed on this host
+  side rates    one batch in flight, float32, mixed and accurate modes; parity blocks of the reduced-precision modes
+--dump-outputs DIR writes what the last timed step returned (detections, counts, OOD scores) as DIR/<name>.npy; inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -359,12 +363,14 @@ def auroc_surrogate(model, image, dev, dtype, n_img=32, bs=8, planted=3, seed=7)
 
 def timed_steps(model, x, dev, nfl, sub, steps, warmup, use_graph, barrier):
     """W warm-up + K timed DetBenchPredict.forward steps with `nfl` batches in flight (own engine instance, input and stream
-    per slot, shared weights).  Returns (elapsed seconds, launch mode, first bench)."""
+    per slot, shared weights).  Returns (elapsed seconds, launch mode, first bench, (bench, detections) of the slot that ran
+    the last timed step)."""
     import copy
     from ood_object_detection_amd.effdet.bench import DetBenchPredict
     benches = [DetBenchPredict(model if i == 0 else copy.copy(model), streams=sub).to(dev) for i in range(nfl)]
     xs = [x] + [x.clone() for _ in range(nfl - 1)]
     streams = [torch.cuda.Stream(dev) for _ in range(nfl)]
+    dets = [None] * nfl                     # each slot's returned detections (a graph's are its captured output buffer)
     with torch.no_grad():
         for _ in range(max(1, min(warmup, 3))):
             for b_, x_ in zip(benches, xs):
@@ -381,7 +387,7 @@ def timed_steps(model, x, dev, nfl, sub, steps, warmup, use_graph, barrier):
                     torch.cuda.current_stream(dev).wait_stream(s_)
                     g_ = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g_, stream=s_):
-                        b_(x_)
+                        dets[len(graphs)] = b_(x_)
                     graphs.append(g_)
                 for g_, s_ in zip(graphs, streams):
                     with torch.cuda.stream(s_):
@@ -399,7 +405,7 @@ def timed_steps(model, x, dev, nfl, sub, steps, warmup, use_graph, barrier):
                 if graphs is not None:
                     graphs[k].replay()
                 else:
-                    benches[k](xs[k])
+                    dets[k] = benches[k](xs[k])
         for i in range(warmup):
             step(i)
         barrier()
@@ -408,111 +414,43 @@ def timed_steps(model, x, dev, nfl, sub, steps, warmup, use_graph, barrier):
             step(i)
         barrier()
         elapsed = time.perf_counter() - t0
-    return elapsed, launch, benches[0]
+    k = (steps - 1) % nfl
+    return elapsed, launch, benches[0], (benches[k], dets[k])
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=100)      # 0.45 s of timed work: 20 steps (90 ms) scatter by +-2 % run to run
-    ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--model', default='tf_efficientdet_d0')
-    ap.add_argument('--image', type=int, default=640)
-    ap.add_argument('--batch', type=int, default=64, help='images per GPU')
-    ap.add_argument('--classes', type=int, default=90)
-    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32', 'accurate'],
-                    help="accurate: float32 weights, compute_mode='accurate' (two-term bf16 values, three matrix-core products per multiply)")
-    ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying one hipGraph')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the in-flight-1 / float32 / parity_bf16 side measurements')
-    ap.add_argument('--soft-nms', action='store_true')
-    ap.add_argument('--auroc-surrogate', action='store_true', help='BASELINE config 4: add the synthetic in-dist / OOD AUROC block')
-    ap.add_argument('--profile-out', default='')
-    ap.add_argument('--in-flight', type=int, default=3,
-                    help='batches in flight: consecutive steps alternate between this many engine instances / streams, so the '
-                         'latency-bound tail of one step (top-k, NMS, small BiFPN levels) overlaps the next step\'s wide kernels')
-    ap.add_argument('--sub-batches', type=int, default=1, help='concurrent sub-batches inside one forward (0: DetBenchPredict default = 2 for B >= 16)')
-    args = ap.parse_args()
+DUMP_LIMIT_BYTES = 64 * 10 ** 6          # the whole dump, .npy headers included
 
-    # --gpus N is the contract: with WORLD_SIZE set (torch.distributed.run started us) it must equal N; with WORLD_SIZE unset
-    # and N > 1 this process is only the PARENT - before any torch.cuda call it starts N fresh rank processes of this same
-    # command (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set), waits and exits with the worst child code.
-    from ood_object_detection_amd.sharding import launch_ranks, resolve_world
-    try:
-        rank, local_rank, world, must_launch = resolve_world(args.gpus)
-    except ValueError as e:
-        raise SystemExit('bench.py: %s' % e)
-    if must_launch:
-        worker = os.environ.get('EFFDET_BENCH_WORKER', os.path.abspath(__file__))     # tests substitute a GPU-free worker
-        sys.exit(launch_ranks(world, [sys.executable, worker] + sys.argv[1:]))
-    if not torch.cuda.is_available():
-        raise SystemExit('bench.py needs an MI355X: the product path has no CPU fallback')
-    # EFFDET_DIST_BACKEND=gloo rehearses the multi-rank control flow on a box with fewer GPUs than ranks
-    # (ranks then share devices round-robin); the real runs use RCCL, one rank per GPU.
-    backend = os.environ.get('EFFDET_DIST_BACKEND', 'nccl')
-    dev = torch.device('cuda', local_rank if backend == 'nccl' else local_rank % torch.cuda.device_count())
-    torch.cuda.set_device(dev)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-        if backend == 'nccl':
-            dist.init_process_group('nccl', rank=rank, world_size=world, device_id=dev)
-        else:
-            dist.init_process_group(backend, rank=rank, world_size=world)
 
-    from ood_object_detection_amd.effdet.bench import DetBenchPredict
-    dtype = torch.bfloat16 if args.dtype == 'bf16' else torch.float32
-    model = build_model(args.model, args.image, args.classes)
-    cfg = model.config
-    cfg.soft_nms = bool(args.soft_nms)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline       # the CPU baseline is an N=1 item
-    sd_cpu = {k: v.clone().float() for k, v in model.state_dict().items()} if want_cpu else None
-    model = model.to(dev).to(dtype)
-    if args.dtype == 'accurate':
-        model.compute_mode = 'accurate'
-    sub = args.sub_batches or None
-    B = args.batch
-    x = (torch.randn(B, 3, args.image, args.image, device=dev, generator=torch.Generator(device=dev).manual_seed(100 + rank))).to(dtype)
+def dump_outputs(out_dir, bench, det, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """What a caller of DetBenchPredict.forward receives from the step: the detections [B, max_det, 6] (x1, y1, x2, y2, score,
+    class) it returns, and `last_count` / `last_ood` beside them - as out_dir/<name>.npy, float32 (anchor indices float64, exact).
+    Should the whole exceed limit_bytes, each array that does not fit its share is replaced by a fixed sample of its flattened
+    elements (np.random.RandomState(seed), sorted flat indices), so that two runs sample the same elements."""
+    import numpy as np
+    arrays = {'detections': det.float(), 'detection_count': bench.last_count.float()}
+    for key, t in bench.last_ood.items():
+        arrays['ood_' + key] = t.double() if t.dtype == torch.int64 else t.float()
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    left, n_left = limit_bytes - 128 * len(arrays), len(arrays)      # np.save writes a 128-byte header per file
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        share = left // n_left
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.RandomState(seed).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+        n_left -= 1
+    return sorted(arrays)
 
-    def barrier():
-        torch.cuda.synchronize(dev)
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize(dev)
 
+def roofline_figures(args, model, x, dev, bench, ms_per_step):
+    """--full: per-launch HIP-event times of one full-batch forward (+ stem, top-k, decode / NMS), summed by kernel family;
+    returns the roofline block of the bench line and writes the per-launch table to --profile-out."""
     import copy
-    nfl = max(1, args.in_flight)
-    # every in-flight slot has its own engine (activation buffers, launch plan) on shallow copies of the model (shared weights),
-    # its own input batch and its own stream; each step still is one full DetBenchPredict.forward over B images
-    elapsed, launch, bench = timed_steps(model, x, dev, nfl, sub, args.steps, args.warmup, not args.no_graph, barrier)
-
-    rate_local = B * args.steps / elapsed                   # this rank's own images / s over its own clock
-    per_rank, ranks_seen = [round(rate_local, 1)], 1
-    if dist is not None:
-        cdev = dev if backend == 'nccl' else 'cpu'
-        t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-        ones = torch.ones(1, device=cdev, dtype=torch.float64)
-        dist.all_reduce(ones)                               # ranks that actually took part in a collective (RCCL when backend = nccl)
-        ranks_seen = int(round(float(ones.item())))
-        rates = torch.zeros(world, device=cdev, dtype=torch.float64)
-        rates[rank] = rate_local
-        dist.all_reduce(rates)
-        per_rank = [round(float(v), 1) for v in rates.tolist()]
-        if ranks_seen != world or dist.get_world_size() != world:
-            raise SystemExit('bench.py: %d ranks answered the all-reduce, --gpus %d' % (ranks_seen, world))
-    if rank != 0:
-        if dist is not None:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
-
-    ms_per_step = 1e3 * elapsed / args.steps
-    value = world * B * args.steps / elapsed
-    counts = bench.last_count.float()
-    # ---- roofline of the dominant kernel family (HIP events on the launch stream) -------------------
+    from ood_object_detection_amd.effdet.bench import DetBenchPredict
+    cfg, B = model.config, x.shape[0]
     # The timed step may run as concurrent half-batches (DetBenchPredict streams); the per-launch table is taken
     # on a full-batch launch plan of the same weights, one launch at a time, so that bytes and times per launch
     # refer to the same thing as the rocprofv3 / PMC summaries under profiles/.
@@ -599,6 +537,121 @@ def main():
                 fh.write('%-10s launches %4d  ms %8.3f  alg_GB %8.3f  GB/s %8.1f  TFLOP/s %7.2f\n' % (
                     k, f['launches'], f['ms'], f['bytes'] / 1e9, f['bytes'] / f['ms'] / 1e6, f['flops'] / f['ms'] / 1e9))
             fh.write('# network (sum of launches) ms %.3f ; timed step ms %.3f (adds top-k/decode/NMS/OOD gather)\n' % (net_ms, ms_per_step))
+    return roofline
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--gpus', type=int, default=1)
+    ap.add_argument('--steps', type=int, default=100)      # 0.45 s of timed work: 20 steps (90 ms) scatter by +-2 % run to run
+    ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--model', default='tf_efficientdet_d0')
+    ap.add_argument('--image', type=int, default=640)
+    ap.add_argument('--batch', type=int, default=64, help='images per GPU')
+    ap.add_argument('--classes', type=int, default=90)
+    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32', 'accurate'],
+                    help="accurate: float32 weights, compute_mode='accurate' (two-term bf16 values, three matrix-core products per multiply)")
+    ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying one hipGraph')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, also measure the roofline (per-launch HIP events), the CPU baseline and the '
+                         'side measurements (other precisions, one batch in flight, parity blocks)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the in-flight-1 / float32 / parity_bf16 side measurements')
+    ap.add_argument('--soft-nms', action='store_true')
+    ap.add_argument('--auroc-surrogate', action='store_true', help='BASELINE config 4: add the synthetic in-dist / OOD AUROC block')
+    ap.add_argument('--profile-out', default='', help='with --full: write the per-launch table behind the roofline block here')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all')
+    ap.add_argument('--in-flight', type=int, default=3,
+                    help='batches in flight: consecutive steps alternate between this many engine instances / streams, so the '
+                         'latency-bound tail of one step (top-k, NMS, small BiFPN levels) overlaps the next step\'s wide kernels')
+    ap.add_argument('--sub-batches', type=int, default=1, help='concurrent sub-batches inside one forward (0: DetBenchPredict default = 2 for B >= 16)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.profile_out and not args.full:
+        ap.error('--profile-out writes the per-launch table of the roofline block, which only --full measures')
+
+    # --gpus N is the contract: with WORLD_SIZE set (torch.distributed.run started us) it must equal N; with WORLD_SIZE unset
+    # and N > 1 this process is only the PARENT - before any torch.cuda call it starts N fresh rank processes of this same
+    # command (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set), waits and exits with the worst child code.
+    from ood_object_detection_amd.sharding import launch_ranks, resolve_world
+    try:
+        rank, local_rank, world, must_launch = resolve_world(args.gpus)
+    except ValueError as e:
+        raise SystemExit('bench.py: %s' % e)
+    if must_launch:
+        worker = os.environ.get('EFFDET_BENCH_WORKER', os.path.abspath(__file__))     # tests substitute a GPU-free worker
+        sys.exit(launch_ranks(world, [sys.executable, worker] + sys.argv[1:]))
+    if not torch.cuda.is_available():
+        raise SystemExit('bench.py needs an MI355X: the product path has no CPU fallback')
+    # EFFDET_DIST_BACKEND=gloo rehearses the multi-rank control flow on a box with fewer GPUs than ranks
+    # (ranks then share devices round-robin); the real runs use RCCL, one rank per GPU.
+    backend = os.environ.get('EFFDET_DIST_BACKEND', 'nccl')
+    dev = torch.device('cuda', local_rank if backend == 'nccl' else local_rank % torch.cuda.device_count())
+    torch.cuda.set_device(dev)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+        if backend == 'nccl':
+            dist.init_process_group('nccl', rank=rank, world_size=world, device_id=dev)
+        else:
+            dist.init_process_group(backend, rank=rank, world_size=world)
+
+    dtype = torch.bfloat16 if args.dtype == 'bf16' else torch.float32
+    model = build_model(args.model, args.image, args.classes)
+    cfg = model.config
+    cfg.soft_nms = bool(args.soft_nms)
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline       # the CPU baseline is an N=1 item
+    sd_cpu = {k: v.clone().float() for k, v in model.state_dict().items()} if want_cpu else None
+    model = model.to(dev).to(dtype)
+    if args.dtype == 'accurate':
+        model.compute_mode = 'accurate'
+    sub = args.sub_batches or None
+    B = args.batch
+    x = (torch.randn(B, 3, args.image, args.image, device=dev, generator=torch.Generator(device=dev).manual_seed(100 + rank))).to(dtype)
+
+    def barrier():
+        torch.cuda.synchronize(dev)
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize(dev)
+
+    import copy
+    nfl = max(1, args.in_flight)
+    # every in-flight slot has its own engine (activation buffers, launch plan) on shallow copies of the model (shared weights),
+    # its own input batch and its own stream; each step still is one full DetBenchPredict.forward over B images
+    elapsed, launch, bench, last = timed_steps(model, x, dev, nfl, sub, args.steps, args.warmup, not args.no_graph, barrier)
+
+    rate_local = B * args.steps / elapsed                   # this rank's own images / s over its own clock
+    per_rank, ranks_seen = [round(rate_local, 1)], 1
+    if dist is not None:
+        cdev = dev if backend == 'nccl' else 'cpu'
+        t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+        ones = torch.ones(1, device=cdev, dtype=torch.float64)
+        dist.all_reduce(ones)                               # ranks that actually took part in a collective (RCCL when backend = nccl)
+        ranks_seen = int(round(float(ones.item())))
+        rates = torch.zeros(world, device=cdev, dtype=torch.float64)
+        rates[rank] = rate_local
+        dist.all_reduce(rates)
+        per_rank = [round(float(v), 1) for v in rates.tolist()]
+        if ranks_seen != world or dist.get_world_size() != world:
+            raise SystemExit('bench.py: %d ranks answered the all-reduce, --gpus %d' % (ranks_seen, world))
+    if rank != 0:
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    ms_per_step = 1e3 * elapsed / args.steps
+    value = world * B * args.steps / elapsed
+    counts = bench.last_count.float()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last)
+    roofline = roofline_figures(args, model, x, dev, bench, ms_per_step) if args.full else None
     # ---- beside the headline (N = 1 only, outside the timed region): the same workload with ONE batch in flight, the float32
     #      (reference-precision) path, and the accuracy of the benched bf16 mode at detection level
     extra = {}
@@ -610,7 +663,7 @@ def main():
         except Exception as e:                                   # noqa: BLE001
             extra[name + '_error'] = '%s: %s' % (type(e).__name__, str(e)[:300])
             torch.cuda.empty_cache()
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         ks = max(5, min(args.steps, 10))
         if nfl != 1:
             side('in_flight_1_images_per_sec',
@@ -619,7 +672,7 @@ def main():
             def f32_rate():
                 m32 = build_model(args.model, args.image, args.classes).to(dev)
                 m32.config.soft_nms = bool(args.soft_nms)
-                e32, _, _ = timed_steps(m32, x.float(), dev, nfl, sub, ks, 2, not args.no_graph, barrier)
+                e32 = timed_steps(m32, x.float(), dev, nfl, sub, ks, 2, not args.no_graph, barrier)[0]
                 return round(B * ks / e32, 1)
             side('f32_images_per_sec', f32_rate)
             torch.cuda.empty_cache()
@@ -628,7 +681,7 @@ def main():
                 from ood_object_detection_amd.serving import MixedPrecisionEfficientDet
                 mm = MixedPrecisionEfficientDet(build_model(args.model, args.image, args.classes).to(dev))
                 mm.config.soft_nms = bool(args.soft_nms)
-                em, _, _ = timed_steps(mm, x, dev, nfl, sub, ks, 2, not args.no_graph, barrier)
+                em = timed_steps(mm, x, dev, nfl, sub, ks, 2, not args.no_graph, barrier)[0]
                 return round(B * ks / em, 1)
             # the point between the two: bfloat16 backbone, float32 BiFPN + heads (serving.MixedPrecisionEfficientDet)
             side('mixed_images_per_sec', mixed_rate)
@@ -637,7 +690,7 @@ def main():
                 ma = build_model(args.model, args.image, args.classes).to(dev)
                 ma.compute_mode = 'accurate'
                 ma.config.soft_nms = bool(args.soft_nms)
-                ea, _, _ = timed_steps(ma, x.float(), dev, nfl, sub, ks, 2, not args.no_graph, barrier)
+                ea = timed_steps(ma, x.float(), dev, nfl, sub, ks, 2, not args.no_graph, barrier)[0]
                 return round(B * ks / ea, 1)
             # the mode that meets north_star's 1e-3: float32 master weights, two-term bf16 values, 3 MFMAs per multiply
             side('accurate_images_per_sec', accurate_rate)

@@ -449,3 +449,45 @@ def test_episode_losses_match_reference(golden):
             v = SupportLoss(cfg, lt)(leaf, ct, npos, alpha)
             assert close(v, g['sup_%s_%s' % (lt, tag)])
             assert close(torch.autograd.grad(v, leaf)[0], g['sup_%s_%s_g0' % (lt, tag)])
+
+
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """bench.dump_outputs: every array DetBenchPredict hands its caller as a float32 / float64 .npy; whole while the total fits the
+    limit, and past it a sample of the largest arrays that is the same on every run (so two builds compare element for element)"""
+    import types
+    import bench
+    B, N = 4, 5000
+    g = torch.Generator().manual_seed(0)
+    fake = types.SimpleNamespace(last_count=torch.tensor([3, 0, 100, 7], dtype=torch.int32), last_ood={
+        'energy': torch.randn(B, 100, generator=g), 'max_logit': torch.randn(B, 100, generator=g),
+        'anchor_energy': torch.randn(B, N, generator=g), 'anchor_max_logit': torch.randn(B, N, generator=g),
+        'anchor_index': torch.randint(0, N, (B, 100), generator=g)})
+    det = torch.randn(B, 100, 6, generator=g).to(torch.bfloat16)
+    want = {'detections': det.float(), 'detection_count': fake.last_count.float(),
+            **{'ood_' + k: (v.double() if v.dtype == torch.int64 else v) for k, v in fake.last_ood.items()}}
+    whole = tmp_path / 'whole'
+    assert bench.dump_outputs(str(whole), fake, det) == sorted(want)
+    for k, v in want.items():
+        a = np.load(str(whole / (k + '.npy')))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, v.numpy())
+    limit = 100_000
+    runs = []
+    for tag in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / tag), fake, det, limit_bytes=limit)
+        runs.append({k: np.load(str(tmp_path / tag / (k + '.npy'))) for k in want})
+        assert sum(os.path.getsize(str(tmp_path / tag / f)) for f in os.listdir(str(tmp_path / tag))) <= limit
+    for k, v in want.items():
+        assert np.array_equal(runs[0][k], runs[1][k])
+        if v.numel() * v.element_size() < limit // 8:
+            assert np.array_equal(runs[0][k], v.numpy())
+        else:
+            assert 0 < runs[0][k].size < v.numel() and np.isin(runs[0][k], v.numpy().ravel()).all()
+
+
+@pytest.mark.parametrize('args,msg', [(['--steps', '0'], '--steps'), (['--profile-out', 'launches.txt'], '--full')])
+def test_bench_rejects_arguments_it_cannot_honour(args, msg):
+    """--steps sets the number of timed steps (at least one); the per-launch table comes from the --full roofline block only"""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and msg in r.stderr

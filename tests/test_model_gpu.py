@@ -247,6 +247,34 @@ def test_detbench_bench_size_properties():
     assert torch.isfinite(ood['energy'][:, :1]).all()
 
 
+def test_bench_plain_run_dumps_the_timed_path(tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the line carries the headline fields and none of the --full blocks, and the
+    dumped arrays are what DetBenchPredict returns for the bench's own seeded weights and input batch"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench as B
+    from ood_object_detection_amd.effdet.bench import DetBenchPredict
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '4', '--warmup', '1', '--image', '256', '--batch', '4',
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['steps'] == 4 and line['unit'] == 'images/sec' and line['dtype'] == 'bf16' and line['higher_is_better'] is True
+    assert line['ms_per_step'] > 0 and abs(line['value'] - 4 * 1e3 / line['ms_per_step']) <= 1e-2 * line['value']
+    assert line['roofline'] is None and line['cpu_baseline'] is None and 'f32_images_per_sec' not in line
+    model = B.build_model('tf_efficientdet_d0', 256, 90).to(DEV).to(torch.bfloat16)
+    bench = DetBenchPredict(model, streams=1).to(DEV)
+    x = torch.randn(4, 3, 256, 256, device=DEV, generator=torch.Generator(device=DEV).manual_seed(100)).to(torch.bfloat16)   # rank 0's
+    det = bench(x)
+    want = {'detections': det, 'detection_count': bench.last_count, **{'ood_' + k: v for k, v in bench.last_ood.items()}}
+    assert sorted(f[:-4] for f in os.listdir(str(tmp_path))) == sorted(want)
+    for k, v in want.items():
+        got = np.load(str(tmp_path / (k + '.npy')))
+        assert got.dtype in (np.float32, np.float64) and np.array_equal(got, v.double().cpu().numpy()), k
+
+
 def _meta_head(dtype, seed=5):
     from ood_object_detection_amd.effdet.meta_head import MetaHead
     model, cfg, nodes, sd = seeded_model('tf_efficientdet_d0', 128, 20, seed=2)

@@ -4,7 +4,7 @@ usage: python tools/pmc_traffic.py <fetch_summary.txt> <write_summary.txt> <forw
 
 FETCH_SIZE / WRITE_SIZE are KiB; on gfx950 FETCH_SIZE counts half of a wide coalesced read stream
 (MI355X_MICROARCH.md, HBM/rocprofv3 section), so reads are doubled.  `forwards` = number of forward passes
-the profiled command dispatched (bench.py --steps 5 --warmup 2 --no-graph: 7 + 1 build pass + 8 in the
+the profiled command dispatched (bench.py --full --steps 5 --warmup 2 --no-graph: 7 + 1 build pass + 8 in the
 per-launch profiling pass = 16 dispatches per launch site)."""
 import json, sys
 
