@@ -903,6 +903,22 @@ int dispatch_sep(hipStream_t st, SepArgs& a, int B) {
     }
 }
 
+// Two-term widths the 8x16 tile cannot hold (d4: 224, d5: 288): its [128 px][F] A tile at 4 bytes per channel plus a 64-row W chunk
+// passes 160 KiB above 192 channels.  These take float32's 8x8-pixel / 256-thread tile (same bytes per channel, half the A tile):
+// F = 224 needs 125 312 B for a node and 154 752 B for the 96-row class chunk, F = 288 160 384 B for a node and 64-row class
+// sub-chunks (the 96-row chunk would need 198 016 B; the running max / sum-exp carries across the sub-chunks, as in float32 d5).
+// At TW = 8 the depthwise runs on the VALU (float taps on the joined value); the pointwise conv is the same three-product MFMA.
+template <int FT>
+int dispatch_sep_pair_8x8(hipStream_t st, SepArgs& a, int B) {
+    if (a.ood_classes > 0) {
+        if constexpr (FT == 0) {
+            if (sep_lds_bytes<bf16p_t, 8, 8, 96>(a.F) > 160 * 1024) return launch_sep<bf16p_t, 8, 8, 64, true, 256, 0>(st, a, B);
+        }
+        return launch_sep<bf16p_t, 8, 8, 96, true, 256, FT>(st, a, B);
+    }
+    return launch_sep<bf16p_t, 8, 8, 64, false, 256, FT>(st, a, B);
+}
+
 }  // namespace
 
 // Flat C-ABI descriptor (mirrors SepArgs; arrays are per level / per input)
@@ -999,7 +1015,10 @@ static int sepconv_common(
             for (int i = 0; i < n_in; ++i)
                 if (reinterpret_cast<uintptr_t>(a.lv[l].in[i].ptr) % 16 || a.lv[l].in[i].image_stride % 4) return EFFDET_EINVAL;
         }
-        return dispatch_sep<bf16p_t, 8, 16, 512>(st, a, B);
+        // the geometry follows from F alone (never from B or the grid): an image's bits do not depend on the batch it came in.
+        // The 8x16 tile keeps every width whose 64-row form fits (up to 192; wider FT = 0 class heads drop to 64-row chunks there).
+        if (sep_lds_bytes<bf16p_t, 8, 16, 64>(F) <= 160 * 1024) return dispatch_sep<bf16p_t, 8, 16, 512>(st, a, B);
+        return F == 224 ? dispatch_sep_pair_8x8<224>(st, a, B) : dispatch_sep_pair_8x8<0>(st, a, B);
     }
     // bf16: 512 threads per 8x16 tile - the LDS footprint allows two workgroups per CU, so four waves per SIMD
     // share the VALU-heavy halo and epilogue phases
