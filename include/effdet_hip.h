@@ -68,17 +68,14 @@ int effdet_stem_conv(void* stream, int in_dtype, int out_dtype, const void* X, c
 /* Fused conv_stem + bn1 + SiLU -> blocks.0.0 depthwise 3x3/s1 + BN + SiLU (+ SE pool partials); the stem
  * output stays in LDS.  Wk: [C][32] im2col weights (dtype), k = (ky*3+kx)*3+ci zero-padded from 27 to 32;
  * taps [9][C] fp32; Y NHWC [B,ceil(H/2),ceil(W/2),C]; pool_partial [B][effdet_stem_dw_parts(dtype,H,W,C)][C]
- * or NULL: the launch writes exactly that many rows per image (bf16 with C = 32 and an even width takes the
- * rolling-window form, whose row count differs from the tile form's) - size AND sum the buffer by
- * effdet_stem_dw_parts, never by effdet_stem_dw_tiles_per_image (the float32 tile form's count, kept for
- * callers that run float32 only).  The same rule holds for effdet_mbconv_expand_dw[_gated]: its pool_partial
- * has effdet_mbconv[_gated]_tiles_per_image(dtype, ...) rows per image, which already answers for the form
- * the given dtype will run.  C <= 64. */
+ * or NULL: the launch writes exactly that many rows per image (the count depends on the form the dtype and
+ * sizes select) - size AND sum the buffer by effdet_stem_dw_parts.  The same rule holds for
+ * effdet_mbconv_expand_dw[_gated]: its pool_partial has effdet_mbconv[_gated]_tiles_per_image(dtype, ...) rows
+ * per image.  C <= 64. */
 int effdet_stem_dw_fused(void* stream, int in_dtype, int dtype, const void* X, const void* Wk,
                          const float* s1, const float* t1, const float* taps, const float* s2, const float* t2,
                          void* Y, float* pool_partial, int B, int H, int W, int C);
 int effdet_stem_dw_parts(int dtype, int H, int W, int C);      /* pool partial rows per image of the kernel that will run (bf16: rolling-window form) */
-int effdet_stem_dw_tiles_per_image(int H, int W);
 
 /* Input normalisation of the reference's PrefetchLoader (effdet/data/loader.py:114-128):
  * y = (float(x) - mean[c]) / std[c], x uint8 NCHW [B,C,hw], mean/std = 255 * the dataset constants

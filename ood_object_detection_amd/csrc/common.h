@@ -44,14 +44,9 @@ DEV float fast_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + fast_exp(
 // float32 TRAINING kernels (train_*.hip, the training form of dwconv.hip): SiLU / sigmoid on the hardware exp2 / rcp instructions
 // (~1 ulp each; relative error of the result < 1e-6, against the 1e-5 ... 2e-3 bounds of the gradient parity tests).  The
 // correctly rounded expf + IEEE division of silu_f cost ~10x the instructions, and the step applies ~2 G of them.  The float32
-// INFERENCE parity path keeps silu_f.  -DEFFDET_TRAIN_PRECISE_SILU restores the precise forms here too.
-#ifdef EFFDET_TRAIN_PRECISE_SILU
-DEV float sigmoid_train(float x) { return sigmoid_f(x); }
-DEV float silu_train(float x) { return silu_f(x); }
-#else
+// INFERENCE parity path keeps silu_f.
 DEV float sigmoid_train(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
 DEV float silu_train(float x) { return x * sigmoid_train(x); }
-#endif
 
 struct bf16p_t;                                     // the two-term bf16 dtype (below): hardware transcendentals like bf16
 template <typename T> struct FastMath { static constexpr bool value = sizeof(T) == 2; };
@@ -79,6 +74,20 @@ DEV f32x4 silu4_scaled(const f32x4 t, const float addc) {
     const f32x2 y1 = t1 * f32x2{__builtin_amdgcn_rcpf(d10), __builtin_amdgcn_rcpf(d11)};
     return f32x4{y0[0], y0[1], y1[0], y1[1]};
 }
+
+// SiLU of four accumulator values on packed fp32 instructions (the BN shift already sits in the accumulator)
+DEV f32x4 silu4_fast(const f32x4 x) {
+    const f32x2 x0 = {x[0], x[1]}, x1 = {x[2], x[3]};
+    const f32x2 t0 = x0 * -1.4426950408889634f, t1 = x1 * -1.4426950408889634f;
+    const f32x2 d0 = f32x2{__builtin_amdgcn_exp2f(t0[0]), __builtin_amdgcn_exp2f(t0[1])} + 1.0f;
+    const f32x2 d1 = f32x2{__builtin_amdgcn_exp2f(t1[0]), __builtin_amdgcn_exp2f(t1[1])} + 1.0f;
+    const f32x2 y0 = x0 * f32x2{__builtin_amdgcn_rcpf(d0[0]), __builtin_amdgcn_rcpf(d0[1])};
+    const f32x2 y1 = x1 * f32x2{__builtin_amdgcn_rcpf(d1[0]), __builtin_amdgcn_rcpf(d1[1])};
+    return f32x4{y0[0], y0[1], y1[0], y1[1]};
+}
+
+// a compile-time int as a value (unrolled ring phases passed to generic lambdas)
+template <int V> struct IntC { static constexpr int value = V; };
 
 template <typename T> DEV f32x4 bn_silu4(const f32x4 acc, const f32x4 sc, const f32x4 sh) {
     if constexpr (FastMath<T>::value) {

@@ -13,14 +13,6 @@
 //     depthwise taps out of LDS, BN2 + SiLU, 16-byte NHWC stores, pool partials.
 // HBM traffic per tile = input halo + output tile (+ weights from L2).
 #include "common.h"
-// Phase-ablation switch of tools/ablate_gpu.sh: exists only in the separate -DEFFDET_ABLATE build
-// (libeffdet_hip_ablate.so, `make ablate`); the product library has no run-time work-skipping switch.
-#ifdef EFFDET_ABLATE
-#include <cstdlib>
-#define MB_DBG(p) ((p).dbg)
-#else
-#define MB_DBG(p) 0
-#endif
 
 namespace {
 
@@ -38,8 +30,6 @@ struct MbArgs {
     int e_bytes;                                // size of the expanded tile (also hosts the pool scratch)
     FastDiv fd_ppr, fd_iw, fd_tx;               // / (16-byte pieces per input row), / IW, / tiles_x
     int tw_shift;                               // TW = 1 << tw_shift
-    int dbg;                                    // phase-ablation mask; only read in the -DEFFDET_ABLATE build
-    int sym;                                    // padding convention (host side: forwarded to the rolling-window launchers)
 };
 
 constexpr int MC = 64;                          // expanded channels per pass
@@ -247,7 +237,7 @@ __global__ __launch_bounds__(SM_T, 4) void mbconv_front_kernel(MbArgs p) {
         const char* xp[HK];
 #pragma unroll
         for (int kc = 0; kc < HK; ++kc) xp[kc] = xa[kc];
-        for (int ms = wave; ms < ((MB_DBG(p) & 1) ? 0 : n_msub); ms += SM_T / 64) {
+        for (int ms = wave; ms < n_msub; ms += SM_T / 64) {
             f32x4 acc[SM_NJ];
 #pragma unroll
             for (int j = 0; j < SM_NJ; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -287,7 +277,7 @@ __global__ __launch_bounds__(SM_T, 4) void mbconv_front_kernel(MbArgs p) {
         if constexpr (MF) {
             // ---- depthwise on the matrix cores: wave (dj, dhalf) owns channel tile dj and every NH-th pixel tile
             float plr[4] = {0.f, 0.f, 0.f, 0.f};
-            if (wave < NH * SM_NJ && !(MB_DBG(p) & 2)) {
+            if (wave < NH * SM_NJ) {
                 // the lane's single non-zero dword of each diagonal operand; expanded to the 16-byte fragment at use
                 unsigned abits[NPAIR];
 #pragma unroll
@@ -376,7 +366,7 @@ __global__ __launch_bounds__(SM_T, 4) void mbconv_front_kernel(MbArgs p) {
             // ---- float32: depthwise on the vector ALU out of LDS, a thread owns 8 channels of one output pixel at a time
             F8 pool = f8_zero();
             const int cg = tid % SM_CG, pg0 = tid / SM_CG;
-            if (pg0 < SM_PG && !(MB_DBG(p) & 2)) {
+            if (pg0 < SM_PG) {
                 for (int px = pg0; px < p.TH * p.TW; px += SM_PG) {
                     const int ty = px >> p.tw_shift, tx = px & (p.TW - 1);
                     const int oy = oy0 + ty, ox = ox0 + tx;
@@ -426,7 +416,6 @@ struct MbDeepArgs {
     float* pool_partial;
     int B, H, W, Cin, mid, Ho, Wo, pad_t, pad_l;
     int band_rows, nbands, nchunks, arow, e_rows_max;
-    int dbg;
     int we;                                      // bf16: columns of the zero-haloed expanded band
     FastDiv fd_w, fd_wo;
 };
@@ -522,7 +511,7 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? 4 : 2) void mbconv_deep_kernel(Mb
     // ---- expand the band: two 16-pixel sub-tiles per step share every W fragment read
     const char* Xb = reinterpret_cast<const char*>(p.X) + ((long long)b * p.H * W + (long long)iy_lo * W) * cbytes;
     const int n_pair = (npx + 31) / 32;
-    for (int mp = wave; mp < ((MB_DBG(p) & 1) ? 0 : n_pair); mp += NTH / 64) {
+    for (int mp = wave; mp < n_pair; mp += NTH / 64) {
         f32x4 acc[2][4];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -592,7 +581,7 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? 4 : 2) void mbconv_deep_kernel(Mb
         float* pl_x = reinterpret_cast<float*>(lds) + (NPAR * MC);  // [NH-1][64] pool sums handed to the first wave of a tile
         float plr[4] = {0.f, 0.f, 0.f, 0.f};
         const bool ch_ok = 16 * j + 4 * fpiece < cn;
-        if (16 * j < cn && !(MB_DBG(p) & 2)) {
+        if (16 * j < cn) {
             constexpr int NTAP = KS * KS, NPAIR = (NTAP + 1) / 2;
             const int hi = fpiece >> 1;
             const bool active = (fpiece & 1) == (frow >> 3);
@@ -668,7 +657,7 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? 4 : 2) void mbconv_deep_kernel(Mb
     const int cgn = cn / 8;
     F8 pool = f8_zero();
     const int cg = tid & 7;
-    if (cg < cgn && !(MB_DBG(p) & 2)) {
+    if (cg < cgn) {
         const F8 s2 = load8<float>(cpar + cg * 8), t2 = load8<float>(cpar + MC + cg * 8);
         const int gpr = (p.Wo + PPT - 1) / PPT;
         for (int pg = tid >> 3; pg < (oy_e - oy_b) * gpr; pg += NTH / 8) {
@@ -797,7 +786,7 @@ Geometry pick_tile(int Ho, int Wo, int Cin, int k, int stride) {
 template <typename T>
 int launch_deep(hipStream_t st, const MbArgs& a, const DeepGeometry& g) {
     MbDeepArgs d{a.X, a.Y, a.W1, a.s1, a.t1, a.taps, a.s2, a.t2, a.pool_partial, a.B, a.H, a.W, a.Cin, a.mid, a.Ho, a.Wo,
-                 a.pad_t, a.pad_l, g.band_rows, g.nbands, g.nchunks, g.arow, g.e_rows_max, a.dbg, g.we,
+                 a.pad_t, a.pad_l, g.band_rows, g.nbands, g.nchunks, g.arow, g.e_rows_max, g.we,
                  make_fastdiv(a.W), make_fastdiv(a.Wo)};
     void (*kern)(MbDeepArgs) = nullptr;
     constexpr int NTH = sizeof(T) == 2 ? 512 : 256;
@@ -812,32 +801,12 @@ int launch_deep(hipStream_t st, const MbArgs& a, const DeepGeometry& g) {
 }
 
 template <typename T>
-int launch_mb(hipStream_t st, MbArgs& a) {
-    if constexpr (sizeof(T) == 2) {
-#ifdef MB_PREFER_WIDE    /* experiment (variant builds only) */
-        if (!a.in_gate && effdet_mbconv_wide_parts(a.H, a.W, a.Cin, a.mid, a.k, a.stride) > 0)
-            return effdet_mbconv_wide_launch(st, a.X, a.Y, a.W1, a.s1, a.t1, a.taps, a.s2, a.t2, a.pool_partial,
-                                             a.B, a.H, a.W, a.Cin, a.mid, a.k, a.stride, 0, a.sym);
-#endif
-        // bf16: the rolling-window form (mbconv_roll.hip) wherever its geometry applies
-        if (effdet_mbconv_roll_parts(a.H, a.W, a.Cin, a.mid, a.k, a.stride) > 0)
-            return effdet_mbconv_roll_launch(st, a.X, a.in_gate, a.Y, a.W1, a.s1, a.t1, a.taps, a.s2, a.t2, a.pool_partial,
-                                             a.B, a.H, a.W, a.Cin, a.mid, a.k, a.stride, 0, a.sym);
-        // wider inputs: the rolling-window form with the X rows shared through LDS (mbconv_wide.hip)
-        if (!a.in_gate && effdet_mbconv_wide_parts(a.H, a.W, a.Cin, a.mid, a.k, a.stride) > 0)
-            return effdet_mbconv_wide_launch(st, a.X, a.Y, a.W1, a.s1, a.t1, a.taps, a.s2, a.t2, a.pool_partial,
-                                             a.B, a.H, a.W, a.Cin, a.mid, a.k, a.stride, 0, a.sym);
-    }
-    const DeepGeometry dg = pick_deep<T>(a.H, a.W, a.Cin, a.mid, a.k, a.stride);
-    if (dg.use && !a.in_gate) return launch_deep<T>(st, a, dg);                    // gated inputs always take the spatial form
-    const Geometry g = pick_tile<T>(a.Ho, a.Wo, a.Cin, a.k, a.stride);
-    if (g.lds > 160 * 1024) return EFFDET_EINVAL;
+int launch_front(hipStream_t st, MbArgs& a, const Geometry& g) {
     a.TH = g.TH; a.TW = g.TW; a.IH = g.IH; a.IW = g.IW; a.HP = g.HP; a.HPpad = g.HPpad; a.arow = g.arow; a.e_bytes = g.e_bytes;
     a.tiles_x = (a.Wo + g.TW - 1) / g.TW; a.tiles_y = (a.Ho + g.TH - 1) / g.TH;
     a.fd_ppr = make_fastdiv(a.Cin * (int)sizeof(T) / 16); a.fd_iw = make_fastdiv(g.IW); a.fd_tx = make_fastdiv(a.tiles_x);
     a.tw_shift = 0; while ((1 << a.tw_shift) < g.TW) ++a.tw_shift;             // candidates have TW in {4, 8, 16}
     dim3 grid(a.tiles_x * a.tiles_y, a.B), block(SM_T);
-    if (a.mid % SM_MC) return EFFDET_EINVAL;               // mid = 6 * Cin: always a multiple of 48
     void (*kern)(MbArgs) = nullptr;
 #define MB_PICK(K_, S_) mbconv_front_kernel<T, K_, S_>
     if (a.k == 3) kern = a.stride == 1 ? MB_PICK(3, 1) : MB_PICK(3, 2);
@@ -851,49 +820,49 @@ int launch_mb(hipStream_t st, MbArgs& a) {
     return effdet_check_launch();
 }
 
+enum MbForm { MB_NONE, MB_ROLL, MB_WIDE, MB_DEEP, MB_FRONT };
+
+// parts: SE pool-partial rows per image the launch writes (what the caller sizes `partial` by and hands the SE gate as nblk)
+struct MbPlan { MbForm form; int parts; DeepGeometry deep; Geometry tile; };
+
+// The one place that decides which fused form runs a block.  Forms, in order of preference:
+//   rolling window (mbconv_roll.hip; bf16 and two-term bf16)  ->  rolling window with X shared through LDS (mbconv_wide.hip;
+//   ungated inputs)  ->  band x channel slice ("deep"; float32 / bf16, ungated)  ->  spatial tiles ("front"; float32 / bf16).
+// Two-term bf16 (dtype 2) has the two rolling-window forms only.  MB_NONE: no fused form - the caller runs expand GEMM + depthwise.
+MbPlan mbconv_plan(int dtype, int H, int W, int Cin, int mid, int k, int stride, bool gated) {
+    MbPlan p{};
+    if (H <= 0 || W <= 0 || Cin <= 0 || mid <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2) || dtype < 0 || dtype > 2) return p;
+    if (dtype >= 1) {
+        const int pair = dtype == 2;
+        if ((p.parts = effdet_mbconv_roll_parts(H, W, Cin, mid, k, stride, pair)) > 0) { p.form = MB_ROLL; return p; }
+        if (!gated && (p.parts = effdet_mbconv_wide_parts(H, W, Cin, mid, k, stride, pair)) > 0) { p.form = MB_WIDE; return p; }
+        p.parts = 0;
+        if (pair) return p;
+    }
+    if (!gated) {                                        // gated inputs always take the spatial form
+        p.deep = dtype == 0 ? pick_deep<float>(H, W, Cin, mid, k, stride) : pick_deep<bf16_t>(H, W, Cin, mid, k, stride);
+        if (p.deep.use) { p.form = MB_DEEP; p.parts = p.deep.nbands; return p; }
+    }
+    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
+    p.tile = dtype == 0 ? pick_tile<float>(Ho, Wo, Cin, k, stride) : pick_tile<bf16_t>(Ho, Wo, Cin, k, stride);
+    if (p.tile.lds > 160 * 1024 || mid % SM_MC) return p;     // (mid = 6 * Cin: always a multiple of 48)
+    p.form = MB_FRONT;
+    p.parts = ((Wo + p.tile.TW - 1) / p.tile.TW) * ((Ho + p.tile.TH - 1) / p.tile.TH);
+    return p;
+}
+
 }  // namespace
 
 extern "C" int effdet_mbconv_tiles_per_image(int dtype, int H, int W, int Cin, int mid, int k, int stride) {
     (void)take_pad_flag(dtype);                          // (no geometry depends on the padding convention)
-    if (H <= 0 || W <= 0 || Cin <= 0 || mid <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2) || dtype < 0 || dtype > 2) return EFFDET_EINVAL;
-    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
-    if (dtype == 2) {                                   // two-term bf16: the two rolling-window forms only
-        int parts = effdet_mbconv_roll_parts(H, W, Cin, mid, k, stride, 1);
-        if (parts > 0) return parts;
-        parts = effdet_mbconv_wide_parts(H, W, Cin, mid, k, stride, 1);
-        return parts > 0 ? parts : EFFDET_EINVAL;
-    }
-    if (dtype == 1) {
-#ifdef MB_PREFER_WIDE
-        { const int pw_ = effdet_mbconv_wide_parts(H, W, Cin, mid, k, stride); if (pw_ > 0) return pw_; }
-#endif
-        int parts = effdet_mbconv_roll_parts(H, W, Cin, mid, k, stride);
-        if (parts > 0) return parts;
-        parts = effdet_mbconv_wide_parts(H, W, Cin, mid, k, stride);
-        if (parts > 0) return parts;
-    }
-    const DeepGeometry dg = dtype == 0 ? pick_deep<float>(H, W, Cin, mid, k, stride) : pick_deep<bf16_t>(H, W, Cin, mid, k, stride);
-    if (dg.use) return dg.nbands;
-    const Geometry g = dtype == 0 ? pick_tile<float>(Ho, Wo, Cin, k, stride) : pick_tile<bf16_t>(Ho, Wo, Cin, k, stride);
-    if (g.lds > 160 * 1024) return EFFDET_EINVAL;      // no fused geometry fits: the caller runs expand GEMM + depthwise
-    return ((Wo + g.TW - 1) / g.TW) * ((Ho + g.TH - 1) / g.TH);
+    const MbPlan p = mbconv_plan(dtype, H, W, Cin, mid, k, stride, false);
+    return p.form != MB_NONE ? p.parts : EFFDET_EINVAL;
 }
 
 extern "C" int effdet_mbconv_gated_tiles_per_image(int dtype, int H, int W, int Cin, int mid, int k, int stride) {
     (void)take_pad_flag(dtype);
-    if (H <= 0 || W <= 0 || Cin <= 0 || mid <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2) || dtype < 0 || dtype > 2) return EFFDET_EINVAL;
-    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
-    if (dtype == 2) {
-        const int parts = effdet_mbconv_roll_parts(H, W, Cin, mid, k, stride, 1);
-        return parts > 0 ? parts : EFFDET_EINVAL;
-    }
-    if (dtype == 1) {
-        const int parts = effdet_mbconv_roll_parts(H, W, Cin, mid, k, stride);
-        if (parts > 0) return parts;
-    }
-    const Geometry g = dtype == 0 ? pick_tile<float>(Ho, Wo, Cin, k, stride) : pick_tile<bf16_t>(Ho, Wo, Cin, k, stride);
-    if (g.lds > 160 * 1024 || mid % SM_MC) return EFFDET_EINVAL;
-    return ((Wo + g.TW - 1) / g.TW) * ((Ho + g.TH - 1) / g.TH);
+    const MbPlan p = mbconv_plan(dtype, H, W, Cin, mid, k, stride, true);
+    return p.form != MB_NONE ? p.parts : EFFDET_EINVAL;
 }
 
 static int mbconv_common(void* stream, int dtype, const void* X, const float* in_gate, void* Y, const void* W1,
@@ -903,29 +872,25 @@ static int mbconv_common(void* stream, int dtype, const void* X, const float* in
     if (!X || !Y || !W1 || !s1 || !t1 || !taps || !s2 || !t2 || B <= 0 || H <= 0 || W <= 0) return EFFDET_EINVAL;
     const int sym = take_pad_flag(dtype);
     if (Cin <= 0 || Cin % 8 || mid <= 0 || mid % 8 || (k != 3 && k != 5) || (stride != 1 && stride != 2) || dtype < 0 || dtype > 2) return EFFDET_EINVAL;
-    if (dtype == 2) {
-        // two-term bf16 (the "accurate" mode): the rolling-window forms with every operand in two terms; geometries outside them
-        // (no such layer in tf_efficientdet_d0 ... d2 at their sizes) are rejected - the caller then runs expand GEMM + depthwise
-        if (reinterpret_cast<uintptr_t>(X) % 16 || reinterpret_cast<uintptr_t>(Y) % 16 || reinterpret_cast<uintptr_t>(W1) % 16) return EFFDET_EINVAL;
-        hipStream_t st2 = reinterpret_cast<hipStream_t>(stream);
-        if (effdet_mbconv_roll_parts(H, W, Cin, mid, k, stride, 1) > 0)
-            return effdet_mbconv_roll_launch(st2, X, in_gate, Y, W1, s1, t1, taps, s2, t2, pool_partial, B, H, W, Cin, mid, k, stride, 1, sym);
-        if (!in_gate && effdet_mbconv_wide_parts(H, W, Cin, mid, k, stride, 1) > 0)
-            return effdet_mbconv_wide_launch(st2, X, Y, W1, s1, t1, taps, s2, t2, pool_partial, B, H, W, Cin, mid, k, stride, 1, sym);
-        return EFFDET_EINVAL;
+    // two-term bf16 (the "accurate" mode): 16-byte aligned operands
+    if (dtype == 2 && (reinterpret_cast<uintptr_t>(X) % 16 || reinterpret_cast<uintptr_t>(Y) % 16 || reinterpret_cast<uintptr_t>(W1) % 16)) return EFFDET_EINVAL;
+    const MbPlan plan = mbconv_plan(dtype, H, W, Cin, mid, k, stride, in_gate != nullptr);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    switch (plan.form) {
+        case MB_NONE: return EFFDET_EINVAL;
+        case MB_ROLL:
+            return effdet_mbconv_roll_launch(st, X, in_gate, Y, W1, s1, t1, taps, s2, t2, pool_partial, B, H, W, Cin, mid, k, stride, dtype == 2, sym);
+        case MB_WIDE:
+            return effdet_mbconv_wide_launch(st, X, Y, W1, s1, t1, taps, s2, t2, pool_partial, B, H, W, Cin, mid, k, stride, dtype == 2, sym);
+        default: break;
     }
     MbArgs a;
     a.X = X; a.in_gate = in_gate; a.Y = Y; a.W1 = W1; a.s1 = s1; a.t1 = t1; a.taps = taps; a.s2 = s2; a.t2 = t2; a.pool_partial = pool_partial;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.mid = mid; a.k = k; a.stride = stride;
     a.Ho = same_out(H, stride); a.Wo = same_out(W, stride);
-    a.pad_t = pad_before(H, k, stride, sym); a.pad_l = pad_before(W, k, stride, sym); a.sym = sym;
-#ifdef EFFDET_ABLATE
-    a.dbg = getenv("EFFDET_DEBUG_SKIP") ? atoi(getenv("EFFDET_DEBUG_SKIP")) : 0;
-#else
-    a.dbg = 0;
-#endif
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == 0 ? launch_mb<float>(st, a) : launch_mb<bf16_t>(st, a);
+    a.pad_t = pad_before(H, k, stride, sym); a.pad_l = pad_before(W, k, stride, sym);
+    if (plan.form == MB_DEEP) return dtype == 0 ? launch_deep<float>(st, a, plan.deep) : launch_deep<bf16_t>(st, a, plan.deep);
+    return dtype == 0 ? launch_front<float>(st, a, plan.tile) : launch_front<bf16_t>(st, a, plan.tile);
 }
 
 extern "C" int effdet_mbconv_expand_dw(void* stream, int dtype, const void* X, void* Y, const void* W1,

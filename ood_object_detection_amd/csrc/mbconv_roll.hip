@@ -35,36 +35,6 @@ struct RollArgs {
     int TWo, nstrips, band_rows, nbands, IWs, wpg, ngroups, ring_bytes, per_image;
 };
 
-// SiLU of four accumulator values on packed fp32 instructions (the BN shift already sits in the accumulator)
-typedef float f32x2_ __attribute__((ext_vector_type(2)));
-DEV f32x4 silu4_fast(const f32x4 x) {
-    const f32x2_ x0 = {x[0], x[1]}, x1 = {x[2], x[3]};
-    const f32x2_ t0 = x0 * -1.4426950408889634f, t1 = x1 * -1.4426950408889634f;
-    const f32x2_ d0 = f32x2_{__builtin_amdgcn_exp2f(t0[0]), __builtin_amdgcn_exp2f(t0[1])} + 1.0f;
-    const f32x2_ d1 = f32x2_{__builtin_amdgcn_exp2f(t1[0]), __builtin_amdgcn_exp2f(t1[1])} + 1.0f;
-    const f32x2_ y0 = x0 * f32x2_{__builtin_amdgcn_rcpf(d0[0]), __builtin_amdgcn_rcpf(d0[1])};
-    const f32x2_ y1 = x1 * f32x2_{__builtin_amdgcn_rcpf(d1[0]), __builtin_amdgcn_rcpf(d1[1])};
-    return f32x4{y0[0], y0[1], y1[0], y1[1]};
-}
-
-template <int V> struct IntC { static constexpr int value = V; };
-#ifndef ROLL_PFD2
-#define ROLL_PFD2 0
-#endif
-
-// Phase ablation for timing experiments: exists only in variant builds (`make variant TAG=.. UNIT=mbconv_roll VDEFS=-DROLL_ABLATE=n`,
-// libeffdet_hip_<TAG>.so, never loaded by the package); the product library is compiled with ROLL_ABLATE = 0.
-// 1: no depthwise arithmetic  2: no expand arithmetic  4: no Y stores  8: no X loads  16: SiLU -> identity  32: X loads always hit (row 0)
-#ifndef ROLL_ABLATE
-#define ROLL_ABLATE 0
-#endif
-#ifndef ROLL_SYNC
-#define ROLL_SYNC 0
-#endif
-DEV f32x4 roll_act(const f32x4 x) {
-    if constexpr ((ROLL_ABLATE & 16) != 0) return x; else return silu4_fast(x);
-}
-
 // Pixels a lane beyond the strip's last output may read past the end of a ring row (its window starts at pixel (16 NO - 1) S at
 // most; + 1: the hi lanes of the single last tap read the pixel after the window, against zero weights - which still must not
 // meet a NaN): behind the LAST slot that is past the wave's ring, so every wave's ring carries this many zeroed pad pixels
@@ -263,22 +233,21 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
         const_cast<char*>(reinterpret_cast<const char*>(p.X)) + (long long)b * p.H * p.W * cbytes, 0, p.H * p.W * cbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<char*>(p.Y) + (long long)b * p.Ho * p.Wo * mid * (int)sizeof(T), 0, p.Ho * p.Wo * mid * (int)sizeof(T), 0x00020000);
-    // One input row = MT x NKC operand fragments, loaded PFD output rows ahead of their use.  PFD = 2 where the registers allow
-    // (bf16, stride 1, at most 4 fragments per row): round 4's ablation builds (profiles/r04_roll_ablation.txt) showed the wait for
-    // the X rows - L2 hits, but fetched by every channel-tile wave and queued behind the previous row's output stores in the
-    // in-order vmcnt - to be the largest single item of a row step (block 1.1: 0.288 ms, 0.176 without the X loads)
-    constexpr int PFD = ROLL_PFD2 && !PAIR && S == 1 && MT * NKC <= 4 ? 2 : 1;
-    Frag<T> xq[PFD * S][MT][NKC];
+    // One input row = MT x NKC operand fragments, loaded one output row ahead of its use.  (Round 4's ablation builds,
+    // profiles/r04_roll_ablation.txt, showed the wait for the X rows - L2 hits, but fetched by every channel-tile wave and queued
+    // behind the previous row's output stores in the in-order vmcnt - to be the largest single item of a row step: block 1.1 0.288 ms,
+    // 0.176 without the X loads.  Loading two rows ahead where the registers allowed was measured and not kept.)
+    Frag<T> xq[S][MT][NKC];
     auto load_row = [&](int rel, Frag<T> (&dst)[MT][NKC]) {
         int iy = iy_top + rel;
         iy = iy < 0 ? 0 : (iy >= p.H ? p.H - 1 : iy);             // rows outside the image: any valid row (zeroed by the row mask)
-        const int rowoff = (ROLL_ABLATE & 32) ? 0 : iy * p.W * cbytes;      // wave-uniform: the buffer op's scalar offset  (ablation 32: every row = row 0, an L1 / L2 hit)
+        const int rowoff = iy * p.W * cbytes;                      // wave-uniform: the buffer op's scalar offset
 #pragma unroll
         for (int t = 0; t < MT; ++t)
 #pragma unroll
             for (int kc = 0; kc < NKC; ++kc) {
                 const int xo = kc + 1 < NKC ? xoff[t] + kc * CHB : xoffl[t];
-                const u32x4 v = (ROLL_ABLATE & 8) ? u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u} : __builtin_amdgcn_raw_buffer_load_b128(xrs, xo, rowoff, 0);
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(xrs, xo, rowoff, 0);
                 if constexpr (PAIR) {
                     // (an out-of-range offset + 16 stays out of range: OOB is far beyond num_records)
                     const u32x4 v2 = __builtin_amdgcn_raw_buffer_load_b128(xrs, xo + 16, rowoff, 0);
@@ -305,8 +274,8 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
                     if (j >= njw) continue;
                     f32x4 acc = sh1[j];
 #pragma unroll
-                    for (int kc = 0; kc < ((ROLL_ABLATE & 2) ? 0 : NKC); ++kc) mma_chunk(wf[j][kc], src[t][kc], acc);
-                    put(j, t, (ROLL_ABLATE & 16) ? (cmask[t] == 1.f ? acc : f32x4{0.f, 0.f, 0.f, 0.f}) : silu4_scaled(acc, cmask[t]));
+                    for (int kc = 0; kc < NKC; ++kc) mma_chunk(wf[j][kc], src[t][kc], acc);
+                    put(j, t, silu4_scaled(acc, cmask[t]));
                 }
         } else {
 #pragma unroll
@@ -318,7 +287,6 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
 
     // 4 channels of one output pixel -> Y (range-checked: an out-of-range offset drops the store; OOB + 16 is out of range too)
     auto store_out = [&](const f32x4 ov, int yo, int yrow_) {
-        if constexpr ((ROLL_ABLATE & 4) != 0) { if (ov[0] == 12345.678f) __builtin_amdgcn_raw_buffer_store_b32(1u, yrs, yo, yrow_, 0); return; }
         if constexpr (PAIR) {
             u32x2 oh, ol;
             pair_split4(ov, oh, ol);
@@ -342,25 +310,19 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
         expand_row(next_rel, next_rel * rowbytes, xq[0]);
     }
 #pragma unroll
-    for (int d = 0; d < PFD; ++d)
-#pragma unroll
-        for (int r = 0; r < S; ++r) load_row(next_rel + d * S + r, xq[d * S + r]);
+    for (int r = 0; r < S; ++r) load_row(next_rel + r, xq[r]);
     int yrow = oy_b * p.Wo * mid * (int)sizeof(T);            // byte offset of the output row inside the image (scalar offset)
     const int ypitch = p.Wo * mid * (int)sizeof(T);
     int oy = oy_b;
     // One output row.  PH = ring slot of the first row of its KS-row window.
-    auto step = [&](auto PHC, auto SLC) {
+    auto step = [&](auto PHC) {
         constexpr int PH = decltype(PHC)::value;
-        constexpr int SL = decltype(SLC)::value % PFD;          // register slot of this step's rows (fetched PFD iterations ago)
-        // ---- expand the S new input rows of this output row, then fetch the rows of the step PFD ahead into the slot just used
+        // ---- expand the S new input rows of this output row, then fetch the next step's rows into the registers just used
 #pragma unroll
-        for (int r = 0; r < S; ++r) expand_row(next_rel + r, ((PH + KS - S + r) % KS) * rowbytes, xq[SL * S + r]);
+        for (int r = 0; r < S; ++r) expand_row(next_rel + r, ((PH + KS - S + r) % KS) * rowbytes, xq[r]);
         next_rel += S;
-#if ROLL_SYNC
-        __builtin_amdgcn_s_barrier();                                // the workgroup's channel-tile waves ask for the same X row together
-#endif
 #pragma unroll
-        for (int r = 0; r < S; ++r) load_row(next_rel + (PFD - 1) * S + r, xq[SL * S + r]);      // past the band's end: clamped rows, never used
+        for (int r = 0; r < S; ++r) load_row(next_rel + r, xq[r]);      // past the band's end: clamped rows, never used
         __builtin_amdgcn_sched_barrier(0);
         // ---- depthwise: one output row out of the ring
         constexpr int OT = OTN < 2 ? OTN : 2;                   // output tiles in flight together
@@ -395,7 +357,7 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
             }
 #pragma unroll
             for (int u = 0; u < OTN; ++u) {
-                const f32x4 ov = roll_act(acc[u]);
+                const f32x4 ov = silu4_fast(acc[u]);
                 const int yo = yoff[u];
                 const float vm = yo == OOB ? 0.f : 1.f;
 #pragma unroll
@@ -433,14 +395,14 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
                     if (pr < NPAIR) {
                         const Frag<T> af = diag(pr);
 #pragma unroll
-                        for (int u = 0; u < ((ROLL_ABLATE & 1) ? 0 : OTN); ++u) mma_chunk(af, bq[g][u], acc[u]);
+                        for (int u = 0; u < OTN; ++u) mma_chunk(af, bq[g][u], acc[u]);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);              // batches stay batches: hoisting every read of the row would spill
             }
 #pragma unroll
             for (int u = 0; u < OTN; ++u) {
-                const f32x4 ov = roll_act(acc[u]);
+                const f32x4 ov = silu4_fast(acc[u]);
                 const int yo = yoff[u];
                 const float vm = yo == OOB ? 0.f : 1.f;
 #pragma unroll
@@ -464,7 +426,7 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
                     const char* const src = pair_addr(ta, tb, offa, offb) + j * RB1;
 #pragma unroll
                     for (int u = 0; u < OT; ++u) {
-                        if (u0 + u < OTN && !(ROLL_ABLATE & 1)) mma_chunk(af, ld_frag<T>(src + (u0 + u) * TILEB), acc[u]);
+                        if (u0 + u < OTN) mma_chunk(af, ld_frag<T>(src + (u0 + u) * TILEB), acc[u]);
                     }
                     // keep the scheduler from hoisting all 2 x 13 ring reads (4 registers each) to the top of the row
                     if constexpr (KS == 5) { if (pr % 4 == 3) __builtin_amdgcn_sched_barrier(0); }
@@ -472,7 +434,7 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
 #pragma unroll
                 for (int u = 0; u < OT; ++u) {
                     if (u0 + u < OTN) {
-                        const f32x4 ov = roll_act(acc[u]);
+                        const f32x4 ov = silu4_fast(acc[u]);
                         const int yo = yoff[u0 + u < OTN ? u0 + u : 0];
                         const float vm = yo == OOB ? 0.f : 1.f;
 #pragma unroll
@@ -488,29 +450,17 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
     };
 #pragma unroll 1
     while (oy < oy_e) {
-        // KS ring phases x PFD register slots, unrolled so that both are compile-time constants in every step
+        // the KS ring phases, unrolled so that the phase is a compile-time constant in every step
         if constexpr (KS == 3) {
-            step(IntC<0>{}, IntC<0>{});
-            if (oy < oy_e) step(IntC<(S) % 3>{}, IntC<1>{});
-            if (oy < oy_e) step(IntC<(2 * S) % 3>{}, IntC<2>{});
-            if constexpr (PFD == 2) {
-                if (oy < oy_e) step(IntC<0>{}, IntC<3>{});
-                if (oy < oy_e) step(IntC<(S) % 3>{}, IntC<4>{});
-                if (oy < oy_e) step(IntC<(2 * S) % 3>{}, IntC<5>{});
-            }
+            step(IntC<0>{});
+            if (oy < oy_e) step(IntC<(S) % 3>{});
+            if (oy < oy_e) step(IntC<(2 * S) % 3>{});
         } else {
-            step(IntC<0>{}, IntC<0>{});
-            if (oy < oy_e) step(IntC<(S) % 5>{}, IntC<1>{});
-            if (oy < oy_e) step(IntC<(2 * S) % 5>{}, IntC<2>{});
-            if (oy < oy_e) step(IntC<(3 * S) % 5>{}, IntC<3>{});
-            if (oy < oy_e) step(IntC<(4 * S) % 5>{}, IntC<4>{});
-            if constexpr (PFD == 2) {
-                if (oy < oy_e) step(IntC<0>{}, IntC<5>{});
-                if (oy < oy_e) step(IntC<(S) % 5>{}, IntC<6>{});
-                if (oy < oy_e) step(IntC<(2 * S) % 5>{}, IntC<7>{});
-                if (oy < oy_e) step(IntC<(3 * S) % 5>{}, IntC<8>{});
-                if (oy < oy_e) step(IntC<(4 * S) % 5>{}, IntC<9>{});
-            }
+            step(IntC<0>{});
+            if (oy < oy_e) step(IntC<(S) % 5>{});
+            if (oy < oy_e) step(IntC<(2 * S) % 5>{});
+            if (oy < oy_e) step(IntC<(3 * S) % 5>{});
+            if (oy < oy_e) step(IntC<(4 * S) % 5>{});
         }
     }
     if (p.pool_partial != nullptr) {
@@ -530,23 +480,64 @@ __global__ __launch_bounds__(512, (IsPair<T>::value ? (KS == 3 && NKC == 1 && MT
     }
 }
 
-struct RollGeometry { bool use; int TWo, nstrips, IWs, IWa, band_rows, nbands, wpg, ngroups, ring_bytes, nkc, nj; size_t lds; };
+typedef void (*RollKernel)(RollArgs);
+// kern: the instantiation that runs this geometry; null where the form does not apply
+struct RollGeometry { RollKernel kern; int TWo, nstrips, IWs, IWa, band_rows, nbands, wpg, ngroups, ring_bytes, nkc, nj; size_t lds; };
+
+template <int KS, int S, int NKC, typename T, int NJ = 1>
+RollKernel roll_kernel_for(int mt, int no) {
+    // MT = ceil(IWs / 16) input tiles, NO = ceil(TWo / 16) output tiles: stride 1 -> NO in {MT - 1, MT}; stride 2 -> MT in {2 NO - 1 .. 2 NO + 1}
+    if constexpr (S == 1) {
+        if (mt == 2) return no == 1 ? mbconv_roll_kernel<KS, S, NKC, 2, 1, T, NJ> : no == 2 ? mbconv_roll_kernel<KS, S, NKC, 2, 2, T, NJ> : nullptr;
+        if constexpr (NKC <= 4) {
+            if (mt == 3) return no == 2 ? mbconv_roll_kernel<KS, S, NKC, 3, 2, T, NJ> : no == 3 ? mbconv_roll_kernel<KS, S, NKC, 3, 3, T, NJ> : nullptr;
+        }
+        if constexpr (NKC <= 3 && KS == 3) {
+            if (mt == 4) return no == 3 ? mbconv_roll_kernel<KS, S, NKC, 4, 3, T, NJ> : no == 4 ? mbconv_roll_kernel<KS, S, NKC, 4, 4, T, NJ> : nullptr;
+        }
+    } else {
+        if constexpr (NKC <= 4) {
+            if (mt == 2) return no == 1 ? mbconv_roll_kernel<KS, S, NKC, 2, 1, T, NJ> : nullptr;
+        }
+        if constexpr (NKC == 1) {
+            if (mt == 3) return no == 1 ? mbconv_roll_kernel<KS, S, NKC, 3, 1, T, NJ> : no == 2 ? mbconv_roll_kernel<KS, S, NKC, 3, 2, T, NJ> : nullptr;
+            if constexpr (KS == 3) {
+                if (mt == 4) return no == 2 ? mbconv_roll_kernel<KS, S, NKC, 4, 2, T, NJ> : nullptr;
+            }
+        }
+    }
+    return nullptr;
+}
+
+template <int KS, int S, typename T>
+RollKernel roll_kernel_ks(const RollGeometry& g) {
+    const int mt = g.IWa / 16, no = (g.TWo + 15) / 16;
+    if (g.nkc == 2) return roll_kernel_for<KS, S, 2, T>(mt, no);
+    if (g.nkc != 1) return nullptr;
+    if constexpr (KS == 3) {
+        if (g.nj == 2) return roll_kernel_for<KS, S, 1, T, 2>(mt, no);
+    }
+    return g.nj == 1 ? roll_kernel_for<KS, S, 1, T>(mt, no) : nullptr;
+}
+
+RollKernel roll_kernel(const RollGeometry& g, int k, int stride, bool pair) {
+    if (pair) {
+        if (k == 3) return stride == 1 ? roll_kernel_ks<3, 1, bf16p_t>(g) : roll_kernel_ks<3, 2, bf16p_t>(g);
+        return stride == 1 ? roll_kernel_ks<5, 1, bf16p_t>(g) : roll_kernel_ks<5, 2, bf16p_t>(g);
+    }
+    if (k == 3) return stride == 1 ? roll_kernel_ks<3, 1, bf16_t>(g) : roll_kernel_ks<3, 2, bf16_t>(g);
+    return stride == 1 ? roll_kernel_ks<5, 1, bf16_t>(g) : roll_kernel_ks<5, 2, bf16_t>(g);
+}
+
 // Channel tiles per wave (kernel parameter NJ).  Measured at d0 / 640 / batch 64 (profiles/r04_roll_nj.txt): two tiles per wave take
 // block 1.0 (320 x 320, 32 -> 96 channels, 3 x 3 / s2: 64 bytes of X per pixel) from 0.360 to 0.328 ms; the 16- and 24-channel inputs of
 // the other 3 x 3 blocks gain nothing, three tiles per wave (128 registers, spills in the 48-pixel strips) lose 6 - 15 %.  So: two tiles
-// where a stride-2 3 x 3 block reads at least 64 bytes per input pixel and the tile count is even; ROLL_NJ_MAX widens that for A/B builds.
-#ifndef ROLL_NJ_MAX
-#define ROLL_NJ_MAX 0
-#endif
-#ifndef ROLL_NJ_PAIR
-#define ROLL_NJ_PAIR 1
-#endif
-
+// where a stride-2 3 x 3 block reads at least 64 bytes per input pixel and the tile count is even.
+//
 // Geometry depends on the map and channel sizes only - never on the batch - so that an image's result (including the order
 // in which its SE pool partials are summed) is the same at every batch size.
 RollGeometry pick_roll(int H, int W, int Cin, int mid, int k, int stride, bool pair = false) {
     RollGeometry g{};
-    g.use = false;
     g.nkc = (Cin + 31) / 32;                                    // K-chunks of 32 channels (64 bytes; two-term bf16: 128 bytes)
     // Inputs wider than 64 channels stay with mbconv.hip's band x channel-slice form.  Both ways of feeding such a layer to
     // 16-channel waves were built and measured on d0 (40 x 40 and 20 x 20 maps, round 2): X through each wave's own registers
@@ -578,10 +569,6 @@ RollGeometry pick_roll(int H, int W, int Cin, int mid, int k, int stride, bool p
         // packed multiplies / converts ~ 110 cycles, a 3 x 3 depthwise tile 5 MFMAs + the same SiLU + pool / store ~ 155; the old 64 : 136
         // put block 1.1 on five 48-pixel strips, 0.288 ms, where three 64-pixel strips run 0.262: profiles/r04_roll_nj.txt)
         long long cost = (long long)ns * ((iwa / 16) * stride * (g.nkc * 16 + 94) + ((two + 15) / 16) * (npair * 19 + 60));
-#ifdef ROLL_PAIR_WIDE    /* experiment (variant builds only): two-term mode takes the widest strips its registers allow - measured
-                            round 4: block 1.0 0.794 ms either way (28 or 44 strips x bands per image), 2.0 0.38 vs 0.30 ms */
-        if (pair) cost = ns;
-#endif
         if (best < 0 || cost < best) { best = cost; g.TWo = two; g.nstrips = ns; g.IWs = iws; g.IWa = iwa; }
     }
     if (best < 0) return g;
@@ -589,8 +576,7 @@ RollGeometry pick_roll(int H, int W, int Cin, int mid, int k, int stride, bool p
     if (k == 3 && g.nkc == 1) {
         // two-term mode (twice the X bytes per pixel): two tiles per wave wherever there are at least two (3 x 3, one K chunk), an odd
         // count leaves the last wave of a strip with one; bf16: stride-2 blocks reading >= 64 bytes per input pixel
-        if (ROLL_NJ_MAX == 0) { if (pair ? (ROLL_NJ_PAIR && mid / 16 >= 2) : (stride == 2 && Cin >= 32 && (mid / 16) % 2 == 0)) g.nj = 2; }
-        else for (int n = 2; n <= ROLL_NJ_MAX; ++n) if ((mid / 16) % n == 0) g.nj = n;
+        if (pair ? mid / 16 >= 2 : (stride == 2 && Cin >= 32 && (mid / 16) % 2 == 0)) g.nj = 2;
     }
     // per wave: nj x (KS slots + the zeroed pad)
     g.ring_bytes = g.nj * (k * g.IWa + roll_pad_px(k, stride, g.IWa / 16, (g.TWo + 15) / 16)) * (pair ? 64 : 32);
@@ -609,60 +595,8 @@ RollGeometry pick_roll(int H, int W, int Cin, int mid, int k, int stride, bool p
     g.nbands = (Ho + g.band_rows - 1) / g.band_rows;
     g.lds = (size_t)g.wpg * g.ring_bytes;
     if (g.lds > 160 * 1024) return g;                           // (cannot happen for the strip widths above; a launch would fail)
-    g.use = true;
+    g.kern = roll_kernel(g, k, stride, pair);
     return g;
-}
-
-template <int KS, int S, int NKC, typename T, int NJ = 1>
-void (*roll_kernel_for(int mt, int no))(RollArgs) {
-    // MT = ceil(IWs / 16) input tiles, NO = ceil(TWo / 16) output tiles: stride 1 -> NO in {MT - 1, MT}; stride 2 -> MT in {2 NO - 1 .. 2 NO + 1}
-    if constexpr (S == 1) {
-        if (mt == 2) return no == 1 ? mbconv_roll_kernel<KS, S, NKC, 2, 1, T, NJ> : no == 2 ? mbconv_roll_kernel<KS, S, NKC, 2, 2, T, NJ> : nullptr;
-        if constexpr (NKC <= 4) {
-            if (mt == 3) return no == 2 ? mbconv_roll_kernel<KS, S, NKC, 3, 2, T, NJ> : no == 3 ? mbconv_roll_kernel<KS, S, NKC, 3, 3, T, NJ> : nullptr;
-        }
-        if constexpr (NKC <= 3 && KS == 3) {
-            if (mt == 4) return no == 3 ? mbconv_roll_kernel<KS, S, NKC, 4, 3, T, NJ> : no == 4 ? mbconv_roll_kernel<KS, S, NKC, 4, 4, T, NJ> : nullptr;
-        }
-    } else {
-        if constexpr (NKC <= 4) {
-            if (mt == 2) return no == 1 ? mbconv_roll_kernel<KS, S, NKC, 2, 1, T, NJ> : nullptr;
-        }
-        if constexpr (NKC == 1) {
-            if (mt == 3) return no == 1 ? mbconv_roll_kernel<KS, S, NKC, 3, 1, T, NJ> : no == 2 ? mbconv_roll_kernel<KS, S, NKC, 3, 2, T, NJ> : nullptr;
-            if constexpr (KS == 3) {
-                if (mt == 4) return no == 2 ? mbconv_roll_kernel<KS, S, NKC, 4, 2, T, NJ> : nullptr;
-            }
-        }
-    }
-    return nullptr;
-}
-
-template <int KS, int S, typename T>
-int launch_roll_ks(hipStream_t st, const RollArgs& r, const RollGeometry& g) {
-    void (*kern)(RollArgs) = nullptr;
-    const int mt = g.IWa / 16, no = (g.TWo + 15) / 16;
-    switch (g.nkc) {
-        case 1:
-            if constexpr (KS == 3) {
-                if (g.nj == 2) { kern = roll_kernel_for<KS, S, 1, T, 2>(mt, no); break; }
-#if ROLL_NJ_MAX >= 3
-                if (g.nj == 3) { kern = roll_kernel_for<KS, S, 1, T, 3>(mt, no); break; }
-#endif
-            }
-            if (g.nj != 1) return EFFDET_EINVAL;
-            kern = roll_kernel_for<KS, S, 1, T>(mt, no); break;
-        case 2: kern = roll_kernel_for<KS, S, 2, T>(mt, no); break;
-        default: break;
-    }
-    if (kern == nullptr) return EFFDET_EINVAL;
-    if (g.lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return EFFDET_ELAUNCH;
-    }
-    const int rounds = (r.B + 7) / 8;
-    hipLaunchKernelGGL(kern, dim3(rounds * r.per_image * 8), dim3(g.wpg * 64), g.lds, st, r);
-    return effdet_check_launch();
 }
 
 }  // namespace
@@ -670,21 +604,21 @@ int launch_roll_ks(hipStream_t st, const RollArgs& r, const RollGeometry& g) {
 // internal (not part of the C ABI): used by mbconv.hip's launcher
 int effdet_mbconv_roll_parts(int H, int W, int Cin, int mid, int k, int stride, int pair) {
     const RollGeometry g = pick_roll(H, W, Cin, mid, k, stride, pair != 0);
-    return g.use ? g.nstrips * g.nbands : 0;
+    return g.kern ? g.nstrips * g.nbands : 0;
 }
 
 int effdet_mbconv_roll_launch(hipStream_t st, const void* X, const float* in_gate, void* Y, const void* W1, const float* s1, const float* t1,
                               const float* taps, const float* s2, const float* t2, float* pool_partial,
                               int B, int H, int W, int Cin, int mid, int k, int stride, int pair, int sym) {
     const RollGeometry g = pick_roll(H, W, Cin, mid, k, stride, pair != 0);
-    if (!g.use) return EFFDET_EINVAL;
+    if (!g.kern) return EFFDET_EINVAL;
     RollArgs r{X, Y, W1, in_gate, s1, t1, taps, s2, t2, pool_partial, B, H, W, Cin, mid, same_out(H, stride), same_out(W, stride),
                pad_before(H, k, stride, sym), pad_before(W, k, stride, sym), g.TWo, g.nstrips, g.band_rows, g.nbands, g.IWs,
                g.wpg, g.ngroups, g.ring_bytes, g.nstrips * g.nbands * g.ngroups};
-    if (pair) {
-        if (k == 3) return stride == 1 ? launch_roll_ks<3, 1, bf16p_t>(st, r, g) : launch_roll_ks<3, 2, bf16p_t>(st, r, g);
-        return stride == 1 ? launch_roll_ks<5, 1, bf16p_t>(st, r, g) : launch_roll_ks<5, 2, bf16p_t>(st, r, g);
+    if (g.lds > 64 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(g.kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return EFFDET_ELAUNCH;
     }
-    if (k == 3) return stride == 1 ? launch_roll_ks<3, 1, bf16_t>(st, r, g) : launch_roll_ks<3, 2, bf16_t>(st, r, g);
-    return stride == 1 ? launch_roll_ks<5, 1, bf16_t>(st, r, g) : launch_roll_ks<5, 2, bf16_t>(st, r, g);
+    hipLaunchKernelGGL(g.kern, dim3(((B + 7) / 8) * r.per_image * 8), dim3(g.wpg * 64), g.lds, st, r);
+    return effdet_check_launch();
 }

@@ -28,10 +28,6 @@
 // the load returns zeros and the store is dropped), as in mbconv_roll.hip, so the row loop has no exec-mask branches around
 // vector-memory operations and `s_waitcnt vmcnt(N)` stays counted.
 #include "common.h"
-#ifdef WIDE_TUNE
-#include <cstdio>
-#include <cstdlib>
-#endif
 
 namespace {
 
@@ -46,34 +42,11 @@ struct WideArgs {
     int* err_word;                                 // device-side failure word (abi.hip) or null
 };
 
-typedef float f32x2w __attribute__((ext_vector_type(2)));
-DEV f32x4 silu4_w(const f32x4 x) {
-    const f32x2w x0 = {x[0], x[1]}, x1 = {x[2], x[3]};
-    const f32x2w t0 = x0 * -1.4426950408889634f, t1 = x1 * -1.4426950408889634f;
-    const f32x2w d0 = f32x2w{__builtin_amdgcn_exp2f(t0[0]), __builtin_amdgcn_exp2f(t0[1])} + 1.0f;
-    const f32x2w d1 = f32x2w{__builtin_amdgcn_exp2f(t1[0]), __builtin_amdgcn_exp2f(t1[1])} + 1.0f;
-    const f32x2w y0 = x0 * f32x2w{__builtin_amdgcn_rcpf(d0[0]), __builtin_amdgcn_rcpf(d0[1])};
-    const f32x2w y1 = x1 * f32x2w{__builtin_amdgcn_rcpf(d1[0]), __builtin_amdgcn_rcpf(d1[1])};
-    return f32x4{y0[0], y0[1], y1[0], y1[1]};
-}
-
-template <int V> struct IntW { static constexpr int value = V; };
-
-// Phase ablation for tools/wide_ablate_gpu.sh: exists only in variant builds (`make variant TAG=.. VDEFS=-DWIDE_ABLATE=n`,
-// libeffdet_hip_<TAG>.so, never loaded by the package); the product library is compiled with WIDE_ABLATE = 0.
-// 1: no hand-off (no poll, no arrival count)  2: no depthwise arithmetic  4: no expand arithmetic  8: no X staging  16: SiLU -> identity
-#ifndef WIDE_ABLATE
-#define WIDE_ABLATE 0
-#endif
 // polls of an arrival counter before a wave gives up (and flags the failure); -DWIDE_SPIN_LIMIT=0 exists as a variant build for the
 // test of that report only (tests/test_kernels_gpu.py::test_wide_handoff_timeout_is_reported)
 #ifndef WIDE_SPIN_LIMIT
 #define WIDE_SPIN_LIMIT (1 << 22)
 #endif
-DEV f32x4 act4_w(const f32x4 x) {
-    if constexpr ((WIDE_ABLATE & 16) != 0) return x; else return silu4_w(x);
-}
-
 constexpr int WIDE_HDR = 64 + 1024;                // LDS header: arrival counters (64 B) + a 1 KiB dump row for idle staging lanes
 
 // KS taps per side, S stride, NKC = 64-byte K chunks of Cin, MT input tiles (16 px) per strip row, NO output tiles per strip
@@ -235,7 +208,6 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
     }
     u32x4 xs[S][NPL];
     auto issue = [&](int rel, u32x4 (&dst)[NPL]) {
-        if constexpr ((WIDE_ABLATE & 8) != 0) return;
         int iy = iy_top + rel;
         iy = iy < 0 ? 0 : (iy >= p.H ? p.H - 1 : iy);             // rows outside the image: any valid row (expand_row writes zeros for them)
         const int rowoff = iy * p.W * cbytes;                      // wave-uniform: the buffer op's scalar offset
@@ -244,15 +216,12 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
     };
     auto commit = [&](int rel, const u32x4 (&src)[NPL]) {
         const int so = (rel & (NSX - 1)) * p.xslot_bytes;
-        if constexpr ((WIDE_ABLATE & 8) != 0) return;
 #pragma unroll
         for (int j = 0; j < NPL; ++j) *reinterpret_cast<u32x4*>(lds + sloff[j] + (smine[j] ? so : 0)) = src[j];
-        if constexpr ((WIDE_ABLATE & 1) != 0) return;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // the wave's pieces are in LDS before its arrival is counted
         if (lane == 0) __hip_atomic_fetch_add(cnt + (rel & (NSX - 1)), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
     auto poll = [&](int rel) {
-        if constexpr ((WIDE_ABLATE & 1) != 0) return;
         const int target = p.nw * (rel / NSX + 1);
         int* c = cnt + (rel & (NSX - 1));
         bool arrived = false;
@@ -270,7 +239,7 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
     };
     auto expand_row = [&](int rel, int slot_bytes) {
         const int iy = iy_top + rel;
-        if ((WIDE_ABLATE & 4) != 0 || iy < 0 || iy >= p.H) {       // TF-SAME pads the EXPANDED map: rows outside the image are zeros
+        if (iy < 0 || iy >= p.H) {       // TF-SAME pads the EXPANDED map: rows outside the image are zeros
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
                 if constexpr (PAIR) *reinterpret_cast<f32x4*>(ring_e + slot_bytes + 16 * PXB * t + kg * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -294,17 +263,16 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
                 for (int kc = 0; kc < NKC; ++kc) xf[kc] = ld_frag<T>(xb + (kc + 1 < NKC ? kc * CHB : xlast));
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PAIR || (WIDE_ABLATE & 16) != 0) {
+            if constexpr (PAIR) {
                 // two-term: pixels beyond the strip's input width read whatever follows the X slot - float32 ring words that can be NaN
                 // patterns as bf16 pairs - and NaN * 0 stays NaN: those lanes are cleared bitwise (one AND mask register per tile)
                 // (elements are copied to scalars first: __builtin_bit_cast applied to an ext-vector element lvalue read element 0 for all four)
-                const f32x4 a_ = (WIDE_ABLATE & 16) ? acc : silu4_scaled(acc, 1.f);
+                const f32x4 a_ = silu4_scaled(acc, 1.f);
                 const unsigned cm = cmask[t];
                 const float e0 = a_[0], e1 = a_[1], e2 = a_[2], e3 = a_[3];
                 const f32x4 ev = {__builtin_bit_cast(float, __builtin_bit_cast(unsigned, e0) & cm), __builtin_bit_cast(float, __builtin_bit_cast(unsigned, e1) & cm),
                                   __builtin_bit_cast(float, __builtin_bit_cast(unsigned, e2) & cm), __builtin_bit_cast(float, __builtin_bit_cast(unsigned, e3) & cm)};
-                if constexpr (PAIR) *reinterpret_cast<f32x4*>(ring_e + slot_bytes + 16 * PXB * t + kg * 16) = ev;      // float32 ring
-                else row_store4<T>(ring_e + slot_bytes + 16 * PXB * t, 4 * kg, ev);
+                *reinterpret_cast<f32x4*>(ring_e + slot_bytes + 16 * PXB * t + kg * 16) = ev;      // float32 ring
             } else {
                 // bf16: the border mask rides in the SiLU's addend (+inf -> t * 0; what the masked lanes read - zeros from the staging,
                 // or bf16 activations behind the X slot - is finite): no mask instructions, one register per tile
@@ -358,7 +326,7 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
         if constexpr (PAIR) {
             // float32 depthwise on the vector ALU (see mbconv_roll.hip): one 16-byte ring read and two packed FMAs per tap and tile
 #pragma unroll
-            for (int dy = 0; dy < ((WIDE_ABLATE & 2) ? 0 : KS); ++dy) {
+            for (int dy = 0; dy < KS; ++dy) {
                 f32x4 e[KS][NO];
 #pragma unroll
                 for (int dx = 0; dx < KS; ++dx)
@@ -372,12 +340,9 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#ifndef WIDE_G
-#define WIDE_G 12
-#endif
-        constexpr int G = WIDE_G / NO < NPAIR ? WIDE_G / NO : NPAIR;     // (two-term: the same count of twice as large fragments, at twice the register budget)
+        constexpr int G = 12 / NO < NPAIR ? 12 / NO : NPAIR;     // (two-term: the same count of twice as large fragments, at twice the register budget)
 #pragma unroll
-        for (int p0 = 0; p0 < ((WIDE_ABLATE & 2) || PAIR ? 0 : NPAIR); p0 += G) {
+        for (int p0 = 0; p0 < (PAIR ? 0 : NPAIR); p0 += G) {
             Frag<T> bq[G][NO];
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -406,7 +371,7 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
         }
 #pragma unroll
         for (int u = 0; u < NO; ++u) {
-            const f32x4 ov = act4_w(acc[u]);
+            const f32x4 ov = silu4_fast(acc[u]);
             const bool last = u == NO - 1;
             if (last) {
 #pragma unroll
@@ -432,15 +397,15 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
 #pragma unroll 1
     while (oy < oy_e) {
         if constexpr (KS == 3) {
-            step(IntW<0>{});
-            if (oy < oy_e) step(IntW<(S) % 3>{});
-            if (oy < oy_e) step(IntW<(2 * S) % 3>{});
+            step(IntC<0>{});
+            if (oy < oy_e) step(IntC<(S) % 3>{});
+            if (oy < oy_e) step(IntC<(2 * S) % 3>{});
         } else {
-            step(IntW<0>{});
-            if (oy < oy_e) step(IntW<(S) % 5>{});
-            if (oy < oy_e) step(IntW<(2 * S) % 5>{});
-            if (oy < oy_e) step(IntW<(3 * S) % 5>{});
-            if (oy < oy_e) step(IntW<(4 * S) % 5>{});
+            step(IntC<0>{});
+            if (oy < oy_e) step(IntC<(S) % 5>{});
+            if (oy < oy_e) step(IntC<(2 * S) % 5>{});
+            if (oy < oy_e) step(IntC<(3 * S) % 5>{});
+            if (oy < oy_e) step(IntC<(4 * S) % 5>{});
         }
     }
     if (p.pool_partial != nullptr) {
@@ -457,23 +422,83 @@ __global__ __launch_bounds__((IsPair<T>::value ? 512 : 1024), (IsPair<T>::value 
     }
 }
 
+typedef void (*WideKernel)(WideArgs);
+// kern: the instantiation that runs this geometry; null where the form does not apply
 struct WideGeometry {
-    bool use; int TWo, nstrips, IWs, IWa, band_rows, nbands, nw, ngroups, ring_bytes, nkc, xpitch, xslot_bytes, npl, wg_per_cu; size_t lds;
+    WideKernel kern; int TWo, nstrips, IWs, IWa, band_rows, nbands, nw, ngroups, ring_bytes, nkc, xpitch, xslot_bytes, npl, wg_per_cu; size_t lds;
 };
+
+template <int KS, int S, int NKC, int MT, int NO, typename T>
+WideKernel wide_kernel_npl(int npl) {
+    if constexpr (IsPair<T>::value) {
+        switch (npl) {
+            case 1: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 1, T>;
+            case 2: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 2, T>;
+            case 3: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 3, T>;
+            case 4: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 4, T>;
+            default: return nullptr;
+        }
+    } else {
+        return npl == 1 ? mbconv_wide_kernel<KS, S, NKC, MT, NO, 1, T> : nullptr;
+    }
+}
+
+template <int KS, int S, int NKC, typename T>
+WideKernel wide_kernel_for(int mt, int no, int npl) {
+    // MT = ceil(IWs / 16) input tiles, NO = ceil(TWo / 16) output tiles
+    if constexpr (S == 1) {
+        if (mt == 2) return no == 1 ? wide_kernel_npl<KS, S, NKC, 2, 1, T>(npl) : no == 2 ? wide_kernel_npl<KS, S, NKC, 2, 2, T>(npl) : nullptr;
+        if (mt == 3) return no == 2 ? wide_kernel_npl<KS, S, NKC, 3, 2, T>(npl) : no == 3 ? wide_kernel_npl<KS, S, NKC, 3, 3, T>(npl) : nullptr;
+        if (mt == 4) return no == 3 ? wide_kernel_npl<KS, S, NKC, 4, 3, T>(npl) : no == 4 ? wide_kernel_npl<KS, S, NKC, 4, 4, T>(npl) : nullptr;
+    } else {
+        if (mt == 2) return no == 1 ? wide_kernel_npl<KS, S, NKC, 2, 1, T>(npl) : nullptr;
+        if (mt == 3) return no == 1 ? wide_kernel_npl<KS, S, NKC, 3, 1, T>(npl) : no == 2 ? wide_kernel_npl<KS, S, NKC, 3, 2, T>(npl) : nullptr;
+        if (mt == 4) return no == 2 ? wide_kernel_npl<KS, S, NKC, 4, 2, T>(npl) : nullptr;
+    }
+    return nullptr;
+}
+
+template <int KS, int S, typename T>
+WideKernel wide_kernel_ks(const WideGeometry& g) {
+    WideKernel kern = nullptr;
+    const int mt = g.IWa / 16, no = (g.TWo + 15) / 16;
+    if constexpr (IsPair<T>::value) {
+        if (mt != 2) return nullptr;                        // two-term strips are at most 32 input pixels wide
+        switch (g.nkc) {
+            case 3: kern = no == 1 ? wide_kernel_npl<KS, S, 3, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 3, 2, 2, T>(g.npl) : nullptr; break;
+            case 4: kern = no == 1 ? wide_kernel_npl<KS, S, 4, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 4, 2, 2, T>(g.npl) : nullptr; break;
+            case 5: kern = no == 1 ? wide_kernel_npl<KS, S, 5, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 5, 2, 2, T>(g.npl) : nullptr; break;
+            case 6: kern = no == 1 ? wide_kernel_npl<KS, S, 6, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 6, 2, 2, T>(g.npl) : nullptr; break;
+            default: break;
+        }
+    } else
+    switch (g.nkc) {
+        case 3: kern = wide_kernel_for<KS, S, 3, T>(mt, no, g.npl); break;
+        case 4: kern = wide_kernel_for<KS, S, 4, T>(mt, no, g.npl); break;
+        case 5: kern = wide_kernel_for<KS, S, 5, T>(mt, no, g.npl); break;
+        case 6: kern = wide_kernel_for<KS, S, 6, T>(mt, no, g.npl); break;
+        default: break;
+    }
+    return kern;
+}
+
+WideKernel wide_kernel(const WideGeometry& g, int k, int stride, bool pair) {
+    if (pair) {
+        if (k == 3) return stride == 1 ? wide_kernel_ks<3, 1, bf16p_t>(g) : wide_kernel_ks<3, 2, bf16p_t>(g);
+        return stride == 1 ? wide_kernel_ks<5, 1, bf16p_t>(g) : wide_kernel_ks<5, 2, bf16p_t>(g);
+    }
+    if (k == 3) return stride == 1 ? wide_kernel_ks<3, 1, bf16_t>(g) : wide_kernel_ks<3, 2, bf16_t>(g);
+    return stride == 1 ? wide_kernel_ks<5, 1, bf16_t>(g) : wide_kernel_ks<5, 2, bf16_t>(g);
+}
 
 // Geometry depends on the map and channel sizes only - never on the batch - so that an image's result (including the order
 // in which its SE pool partials are summed) is the same at every batch size.
 WideGeometry pick_wide(int H, int W, int Cin, int mid, int k, int stride, bool pair = false) {
     WideGeometry g{};
-    g.use = false;
     const int esz = pair ? 4 : 2, pxb = 16 * esz;                  // bytes per channel / per 16-channel ring pixel
     const int cbytes = Cin * esz;
     g.nkc = (Cin + 31) / 32;                                    // K-chunks of 32 channels (64 bytes; two-term bf16: 128 bytes)
-#ifdef WIDE_NARROW       /* experiment (variant builds only): the shared-X form for inputs of 8 ... 64 channels too */
-    if (g.nkc > 6 || mid % 16 || Cin % 8) return g;
-#else
     if ((g.nkc < 3 || g.nkc > 6) || mid % 16 || Cin % 8) return g;        // narrower inputs: mbconv_roll.hip; wider: the band x slice form
-#endif
     const int Ho = same_out(H, stride), Wo = same_out(W, stride);
     // one strip per row where the row fits 64 input pixels, else equal strips
     int best_ns = 0;
@@ -547,94 +572,9 @@ WideGeometry pick_wide(int H, int W, int Cin, int mid, int k, int stride, bool p
         }
     }
     if (best < 0) return g;
-#ifdef WIDE_TUNE
-    // geometry sweep of tools/wide_tune_gpu.sh (variant build only): EFFDET_WIDE_TUNE="nw,per_cu,nbands"
-    if (const char* tv = getenv("EFFDET_WIDE_TUNE")) {
-        int d = 0, pc = 0, nb = 0;
-        if (sscanf(tv, "%d,%d,%d", &d, &pc, &nb) == 3 && d >= 1 && d <= 16 && tiles % d == 0 && nb >= 1) {
-            const size_t l = WIDE_HDR + xbytes + (size_t)d * g.ring_bytes + tail_pad;
-            const int rows = (Ho + nb - 1) / nb;
-            if (l * pc <= budget && (g.IWs * (cbytes / 16) + d * 64 - 1) / (d * 64) <= 1 && d * pc <= 16) {
-                g.nw = d; g.wg_per_cu = pc; g.lds = l; g.band_rows = rows; g.nbands = (Ho + rows - 1) / rows;
-            }
-        }
-    }
-#endif
     g.ngroups = tiles / g.nw;
-    g.use = true;
+    g.kern = wide_kernel(g, k, stride, pair);
     return g;
-}
-
-template <int KS, int S, int NKC, int MT, int NO, typename T>
-void (*wide_kernel_npl(int npl))(WideArgs) {
-    if constexpr (IsPair<T>::value) {
-        switch (npl) {
-            case 1: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 1, T>;
-            case 2: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 2, T>;
-            case 3: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 3, T>;
-            case 4: return mbconv_wide_kernel<KS, S, NKC, MT, NO, 4, T>;
-            default: return nullptr;
-        }
-    } else {
-        return npl == 1 ? mbconv_wide_kernel<KS, S, NKC, MT, NO, 1, T> : nullptr;
-    }
-}
-
-template <int KS, int S, int NKC, typename T>
-void (*wide_kernel_for(int mt, int no, int npl))(WideArgs) {
-    // MT = ceil(IWs / 16) input tiles, NO = ceil(TWo / 16) output tiles
-    if constexpr (S == 1) {
-        if (mt == 2) return no == 1 ? wide_kernel_npl<KS, S, NKC, 2, 1, T>(npl) : no == 2 ? wide_kernel_npl<KS, S, NKC, 2, 2, T>(npl) : nullptr;
-        if (mt == 3) return no == 2 ? wide_kernel_npl<KS, S, NKC, 3, 2, T>(npl) : no == 3 ? wide_kernel_npl<KS, S, NKC, 3, 3, T>(npl) : nullptr;
-        if (mt == 4) return no == 3 ? wide_kernel_npl<KS, S, NKC, 4, 3, T>(npl) : no == 4 ? wide_kernel_npl<KS, S, NKC, 4, 4, T>(npl) : nullptr;
-    } else {
-        if (mt == 2) return no == 1 ? wide_kernel_npl<KS, S, NKC, 2, 1, T>(npl) : nullptr;
-        if (mt == 3) return no == 1 ? wide_kernel_npl<KS, S, NKC, 3, 1, T>(npl) : no == 2 ? wide_kernel_npl<KS, S, NKC, 3, 2, T>(npl) : nullptr;
-        if (mt == 4) return no == 2 ? wide_kernel_npl<KS, S, NKC, 4, 2, T>(npl) : nullptr;
-    }
-    return nullptr;
-}
-
-template <int KS, int S, typename T>
-int launch_wide_ks(hipStream_t st, const WideArgs& r, const WideGeometry& g) {
-    void (*kern)(WideArgs) = nullptr;
-    const int mt = g.IWa / 16, no = (g.TWo + 15) / 16;
-    if constexpr (IsPair<T>::value) {
-        if (mt != 2) return EFFDET_EINVAL;                        // two-term strips are at most 32 input pixels wide
-        switch (g.nkc) {
-            case 3: kern = no == 1 ? wide_kernel_npl<KS, S, 3, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 3, 2, 2, T>(g.npl) : nullptr; break;
-            case 4: kern = no == 1 ? wide_kernel_npl<KS, S, 4, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 4, 2, 2, T>(g.npl) : nullptr; break;
-            case 5: kern = no == 1 ? wide_kernel_npl<KS, S, 5, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 5, 2, 2, T>(g.npl) : nullptr; break;
-            case 6: kern = no == 1 ? wide_kernel_npl<KS, S, 6, 2, 1, T>(g.npl) : (no == 2 && S == 1) ? wide_kernel_npl<KS, S, 6, 2, 2, T>(g.npl) : nullptr; break;
-            default: break;
-        }
-    } else
-    switch (g.nkc) {
-#ifdef WIDE_NARROW
-        case 1: kern = wide_kernel_for<KS, S, 1, T>(mt, no, g.npl); break;
-        case 2: kern = wide_kernel_for<KS, S, 2, T>(mt, no, g.npl); break;
-#endif
-        case 3: kern = wide_kernel_for<KS, S, 3, T>(mt, no, g.npl); break;
-        case 4: kern = wide_kernel_for<KS, S, 4, T>(mt, no, g.npl); break;
-        case 5: kern = wide_kernel_for<KS, S, 5, T>(mt, no, g.npl); break;
-        case 6: kern = wide_kernel_for<KS, S, 6, T>(mt, no, g.npl); break;
-        default: break;
-    }
-    if (kern == nullptr) return EFFDET_EINVAL;
-    if (g.lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return EFFDET_ELAUNCH;
-    }
-    const int rounds = (r.B + 7) / 8;
-    hipLaunchKernelGGL(kern, dim3(rounds * r.per_image * 8), dim3(g.nw * 64), g.lds, st, r);
-    return effdet_check_launch();
-}
-
-bool wide_supported(const WideGeometry& g, int k, int stride) {
-    if (!g.use) return false;
-    const int mt = g.IWa / 16, no = (g.TWo + 15) / 16;
-    if (stride == 1) return (mt == 2 && (no == 1 || no == 2)) || (mt == 3 && (no == 2 || no == 3)) || (mt == 4 && (no == 3 || no == 4));
-    return (mt == 2 && no == 1) || (mt == 3 && (no == 1 || no == 2)) || (mt == 4 && no == 2);
 }
 
 }  // namespace
@@ -642,22 +582,14 @@ bool wide_supported(const WideGeometry& g, int k, int stride) {
 // internal (not part of the C ABI): used by mbconv.hip's launcher
 int effdet_mbconv_wide_parts(int H, int W, int Cin, int mid, int k, int stride, int pair) {
     const WideGeometry g = pick_wide(H, W, Cin, mid, k, stride, pair != 0);
-    return wide_supported(g, k, stride) ? g.nstrips * g.nbands : 0;
+    return g.kern ? g.nstrips * g.nbands : 0;
 }
 
 int effdet_mbconv_wide_launch(hipStream_t st, const void* X, void* Y, const void* W1, const float* s1, const float* t1,
                               const float* taps, const float* s2, const float* t2, float* pool_partial,
                               int B, int H, int W, int Cin, int mid, int k, int stride, int pair, int sym) {
     const WideGeometry g = pick_wide(H, W, Cin, mid, k, stride, pair != 0);
-    if (!wide_supported(g, k, stride)) return EFFDET_EINVAL;
-#ifdef WIDE_TUNE
-    static thread_local long long printed_ = -1;
-    const long long key_ = ((((long long)H * 4096 + W) * 4096 + Cin) * 8 + k) * 4 + stride;
-    if (getenv("EFFDET_GEOM_DEBUG") && printed_ != key_ && ((printed_ = key_), true))   // host-side print of the chosen geometry (tools/mbconv_layers.py)
-        fprintf(stderr, "mbconv_wide H=%d W=%d Cin=%d mid=%d k=%d s=%d: nw=%d groups=%d strips=%d bands=%d x %d rows, %d WG/CU, lds=%zu, MT=%d NO=%d NKC=%d, WGs(B=%d)=%d\n",
-                H, W, Cin, mid, k, stride, g.nw, g.ngroups, g.nstrips, g.nbands, g.band_rows, g.wg_per_cu, g.lds, g.IWa / 16, (g.TWo + 15) / 16,
-                g.nkc, B, ((B + 7) / 8) * 8 * g.nstrips * g.nbands * g.ngroups);
-#endif
+    if (!g.kern) return EFFDET_EINVAL;
     WideArgs r{};
     r.X = X; r.Y = Y; r.W1 = W1; r.s1 = s1; r.t1 = t1; r.taps = taps; r.s2 = s2; r.t2 = t2; r.pool_partial = pool_partial;
     r.B = B; r.H = H; r.W = W; r.Cin = Cin; r.mid = mid; r.Ho = same_out(H, stride); r.Wo = same_out(W, stride);
@@ -668,10 +600,10 @@ int effdet_mbconv_wide_launch(hipStream_t st, const void* X, void* Y, const void
     r.x_off = WIDE_HDR; r.ring_off = WIDE_HDR + 2 * stride * g.xslot_bytes; r.lds_bytes = (int)g.lds;
     r.fd_ppr = make_fastdiv(r.ppr);
     r.err_word = effdet_device_error_word();
-    if (pair) {
-        if (k == 3) return stride == 1 ? launch_wide_ks<3, 1, bf16p_t>(st, r, g) : launch_wide_ks<3, 2, bf16p_t>(st, r, g);
-        return stride == 1 ? launch_wide_ks<5, 1, bf16p_t>(st, r, g) : launch_wide_ks<5, 2, bf16p_t>(st, r, g);
+    if (g.lds > 64 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(g.kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return EFFDET_ELAUNCH;
     }
-    if (k == 3) return stride == 1 ? launch_wide_ks<3, 1, bf16_t>(st, r, g) : launch_wide_ks<3, 2, bf16_t>(st, r, g);
-    return stride == 1 ? launch_wide_ks<5, 1, bf16_t>(st, r, g) : launch_wide_ks<5, 2, bf16_t>(st, r, g);
+    hipLaunchKernelGGL(g.kern, dim3(((B + 7) / 8) * r.per_image * 8), dim3(g.nw * 64), g.lds, st, r);
+    return effdet_check_launch();
 }

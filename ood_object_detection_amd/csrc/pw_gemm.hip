@@ -34,24 +34,18 @@ struct PwArgs {
 
 template <int V> struct PwInt { static constexpr int value = V; };
 
-#ifndef PW_PF_SMALL
-#define PW_PF_SMALL 2            /* measured on d0 blocks 5.x: four stages 0.042 ms, two stages 0.035 ms */
-#endif
 constexpr int PW_PIX = 128;                      // pixels per workgroup: 4 waves x 2 MFMA tiles, or 8 waves x 1 (small maps)
-#ifndef PW_KCH_SMALL
-#define PW_KCH_SMALL 2
-#endif
 
 // PT 16-pixel tiles per wave, NTH threads: (2, 256) normally; (1, 512) when the launch has fewer than two workgroups per
 // CU (20x20 maps) - twice the waves per SIMD to hide the per-stage latencies, at the price of reading each W
 // fragment from LDS once per 16 instead of once per 32 pixels
 template <typename T, int BN, int PT, int NTH, bool GATED>
 DEV void pw_gemm_body(const PwArgs& p, const int bid) {
-    // 64-byte K-chunks per pipeline stage (PW_KCH_SMALL: the 512-thread small-map form; 4 in a variant build for A/B timing)
+    // two 64-byte K-chunks per pipeline stage
     // (two-term bf16: ONE 128-byte chunk = 32 K values in two terms per stage - the same bytes per pixel and stage, and the same
     // number of operand registers in the A ring, as the two 64-byte chunks of the other dtypes)
     constexpr bool PAIR = IsPair<T>::value;
-    constexpr int KCH = PAIR ? 1 : ((PT == 1 && NTH == 512) ? PW_KCH_SMALL : 2);
+    constexpr int KCH = PAIR ? 1 : 2;
     constexpr int EPC = VecTraits<T>::EPC;          // elements per operand piece
     constexpr int KPC = OpGeom<T>::KPC;             // elements per K-chunk
     constexpr int PB = OpGeom<T>::PIECE, CB = OpGeom<T>::CHUNK;   // bytes of a lane's operand piece / of a K-chunk (16 / 64; two-term: 32 / 128)
@@ -59,8 +53,8 @@ DEV void pw_gemm_body(const PwArgs& p, const int bid) {
     static_assert(NT % 2 == 0, "tile pairs");
     // A stages (128 bytes of K per pixel) in flight ahead of the one being multiplied: as many as the registers
     // left over by the accumulators allow - the late layers are latency bound, not bandwidth bound
-    // two stages everywhere; PW_PF_SMALL = 4 (a variant build) deepens the ring of the 512-thread small-map form - measured slower
-    constexpr int PF = (PT == 1 && NTH == 512) ? PW_PF_SMALL : 2;
+    // two stages everywhere (four in the 512-thread small-map form were measured slower on d0 blocks 5.x: 0.042 against 0.035 ms)
+    constexpr int PF = 2;
     constexpr int ROWB = KCH * CB + 16;             // bytes per LDS row: one stage of K + 16 pad
     constexpr int W_BYTES = BN * ROWB;
     __shared__ __attribute__((aligned(16))) char lds[2 * W_BYTES];
@@ -213,29 +207,16 @@ DEV void pw_gemm_body(const PwArgs& p, const int bid) {
         w_store((stg + 1) & 1, stg + 1 < nst ? stg + 1 : nst - 1);   // (after the last stage: a copy nobody reads)
         __syncthreads();
     };
-    // whole groups of PF + 1 stages without a single guard (so every wait in them is counted), then at most PF tail stages
-    static_assert(PF == 2 || PF == 4, "the stage groups below are written out for three- and five-slot A rings");
+    // whole groups of PF + 1 = 3 stages without a single guard (so every wait in them is counted), then at most PF tail stages
     int stg = 0;
     for (; stg + PF + 1 <= nst; stg += PF + 1) {
         stage(stg, PwInt<0>{});
         stage(stg + 1, PwInt<1>{});
         stage(stg + 2, PwInt<2>{});
-        if constexpr (PF == 4) {
-            stage(stg + 3, PwInt<3>{});
-            stage(stg + 4, PwInt<4>{});
-        }
     }
     if (stg < nst) {
         stage(stg, PwInt<0>{});
-        if (stg + 1 < nst) {
-            stage(stg + 1, PwInt<1>{});
-            if constexpr (PF == 4) {
-                if (stg + 2 < nst) {
-                    stage(stg + 2, PwInt<2>{});
-                    if (stg + 3 < nst) stage(stg + 3, PwInt<3>{});
-                }
-            }
-        }
+        if (stg + 1 < nst) stage(stg + 1, PwInt<1>{});
     }
 
     // ---- epilogue in registers: per 32-channel group J this lane holds channels [32J + 8*fpiece, +8) of its pixels

@@ -434,17 +434,14 @@ int effdet_stem_roll_launch(hipStream_t st, int in_dtype, const void* X, const f
     a.pad_t = pad_before(H, 3, 2, sym); a.pad_l = pad_before(W, 3, 2, sym);
     a.TWo = g.TWo; a.nstrips = g.nstrips; a.band_rows = g.band_rows; a.nbands = g.nbands; a.wpg = g.wpg; a.per_image = g.per_image;
     a.jsplit = 1;
+    // two 16-channel tiles per wave: the geometry takes C = 32 only, so every (image dtype, form) has its kernel
     void (*kern)(SrArgs) = nullptr;
-    const int nj = C / 16;
-#define SR_PICK(IN_, T_) (nj == 2 ? stem_roll_kernel<IN_, 2, T_> : nullptr)
-    if (pair) kern = in_dtype == 0 ? SR_PICK(0, bf16p_t) : SR_PICK(2, bf16p_t);
-    else kern = in_dtype == 0 ? SR_PICK(0, bf16_t) : in_dtype == 1 ? SR_PICK(1, bf16_t) : SR_PICK(2, bf16_t);
-#undef SR_PICK
+    if (pair) kern = in_dtype == 0 ? stem_roll_kernel<0, 2, bf16p_t> : stem_roll_kernel<2, 2, bf16p_t>;
+    else kern = in_dtype == 0 ? stem_roll_kernel<0, 2, bf16_t> : in_dtype == 1 ? stem_roll_kernel<1, 2, bf16_t> : stem_roll_kernel<2, 2, bf16_t>;
     if (g.lds > 64 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return EFFDET_ELAUNCH;
     }
-    if (kern == nullptr) return EFFDET_EINVAL;
     const int rounds = (B + 7) / 8;
     hipLaunchKernelGGL(kern, dim3(rounds * g.per_image * 8), dim3(g.wpg * 64), g.lds, st, a);
     return effdet_check_launch();

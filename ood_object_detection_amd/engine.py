@@ -165,25 +165,34 @@ class Engine(object):
         stem_c, stages = bb.arch
         plan = []
         Hs, Ws = _same_out(H, 2), _same_out(W, 2)
-        # geometry pass: buffer sizes
+        # geometry pass: buffer sizes, and each block's form - forms[si][bi] = (fused, SE pool-partial rows per image) - which the
+        # planning pass below reads (the library is asked once per block: the launch writes exactly the rows its query answered)
+        stem_parts = lib.effdet_stem_dw_parts(dtp, H, W, stem_c)       # the fused stem's rows (<= 0: no fused stem in this mode)
         io_max, mid_max, part_max, exp_max = B * Hs * Ws * stem_c, 0, 0, 0
+        forms = []
         h, w = Hs, Ws
         for blocks in stages:
+            forms.append([])
             for b in blocks:
                 ho, wo = _same_out(h, b['s']), _same_out(w, b['s'])
                 mid_max = max(mid_max, B * ho * wo * b['mid'])
+                dw_parts = lib.effdet_dwconv_blocks_per_image(ho, wo, b['mid'])
+                fused, rows = False, None
                 if b['type'] == 'ir':
                     nblk = lib.effdet_mbconv_tiles_per_image(dtp, h, w, b['cin'], b['mid'], b['k'], b['s'])
-                    if nblk <= 0:        # no fused geometry (very wide fp32 inputs): expand GEMM + depthwise kernels
+                    fused = nblk > 0
+                    if not fused:        # no fused geometry (very wide fp32 inputs): expand GEMM + depthwise kernels
                         # (accurate mode: the two-term MBConv kernels cover inputs up to 192 channels - every block of d0; wider
                         #  blocks take this unfused path too, with the expanded tensor in HBM)
-                        nblk = lib.effdet_dwconv_blocks_per_image(ho, wo, b['mid'])
+                        nblk = dw_parts
                         exp_max = max(exp_max, B * h * w * b['mid'])
                 else:
-                    nblk = max(lib.effdet_dwconv_blocks_per_image(ho, wo, b['mid']), lib.effdet_stem_dw_parts(dtp, H, W, stem_c))
+                    nblk = dw_parts
+                    rows = max(nblk, stem_parts)     # (block 0.0 may be run by the fused stem)
                 if nblk <= 0:
                     raise NotImplementedError('block geometry (mid=%d) is outside the built range' % b['mid'])
-                part_max = max(part_max, B * nblk * b['mid'])
+                forms[-1].append((fused, nblk))
+                part_max = max(part_max, B * (rows or nblk) * b['mid'])
                 io_max = max(io_max, B * ho * wo * b['cout'])
                 h, w = ho, wo
         ping = [self._new(io_max), self._new(io_max)]
@@ -193,13 +202,16 @@ class Engine(object):
         # applied while that kernel loads its input tile, so the narrow tensor in between never exists.
         b00, b10 = stages[0][0], (stages[1][0] if len(stages) > 1 else None)
         self._compose01 = bool(len(stages[0]) == 1 and b10 is not None and b00['type'] == 'ds' and not b00['residual']
-                               and b10['type'] == 'ir' and not b10['residual'] and b00['mid'] % 8 == 0 and
-                               lib.effdet_mbconv_gated_tiles_per_image(dtp, Hs, Ws, b00['mid'], b10['mid'], b10['k'], b10['s']) > 0)
+                               and b10['type'] == 'ir' and not b10['residual'] and b00['mid'] % 8 == 0)
+        gated10 = 0                              # SE pool-partial rows per image of the composed block 1.0
+        if self._compose01:
+            gated10 = lib.effdet_mbconv_gated_tiles_per_image(dtp, Hs, Ws, b00['mid'], b10['mid'], b10['k'], b10['s'])
+            self._compose01 = gated10 > 0
         dbuf2 = None
         if self._compose01:
             h1, w1_ = _same_out(Hs, b10['s']), _same_out(Ws, b10['s'])
             dbuf2 = self._new(B * h1 * w1_ * b10['mid'])
-            part_max = max(part_max, B * lib.effdet_mbconv_gated_tiles_per_image(dtp, Hs, Ws, b00['mid'], b10['mid'], b10['k'], b10['s']) * b10['mid'])
+            part_max = max(part_max, B * gated10 * b10['mid'])
         ebuf = self._new(exp_max) if exp_max else None
         partial = self._new(part_max, dtype=torch.float32)
         composed = None          # (W_proj folded, t3) of block 0.0 while block 1.0 is being planned
@@ -211,7 +223,7 @@ class Engine(object):
         s, t = self._f32(s), self._f32(t)
         b00 = stages[0][0]
         self._fuse_stem = (b00['type'] == 'ds' and b00['k'] == 3 and b00['s'] == 1 and stem_c <= 64)
-        if self._fuse_stem and self.pair and lib.effdet_stem_dw_parts(dtp, H, W, stem_c) <= 0:
+        if self._fuse_stem and self.pair and stem_parts <= 0:
             self._fuse_stem = False              # accurate mode outside the fused stem's form (32 channels, even left pad): stem conv + depthwise
         if self._fuse_stem:
             # conv_stem + bn1 + SiLU + blocks.0.0.conv_dw + bn1 + SiLU in one launch (stem map stays in LDS)
@@ -261,7 +273,7 @@ class Engine(object):
                         t1 = t1.to(self.device) + s1.to(self.device) * (we @ t3c)
                         w1 = self._w(wcomb)
                         s1, t1 = self._f32(s1), self._f32(t1)
-                        nblk = lib.effdet_mbconv_gated_tiles_per_image(dtp, h, w, cmid, b['mid'], b['k'], b['s'])
+                        nblk = gated10
                         plan.append((lib.effdet_mbconv_expand_dw_gated,
                                      (dtp, dbuf.data_ptr(), gate.data_ptr(), dbuf2.data_ptr(), w1.data_ptr(), s1.data_ptr(), t1.data_ptr(),
                                       taps.data_ptr(), s2.data_ptr(), t2.data_ptr(), partial.data_ptr(),
@@ -270,42 +282,38 @@ class Engine(object):
                                           flops=2 * B * (h * w * cmid * b['mid'] + b['k'] * b['k'] * ho * wo * b['mid']))))
                         composed = None
                         mid_buf = dbuf2
-                        pw_out, bn_out = m.conv_pwl, m.bn3
                     else:
-                      w1 = self._w(m.conv_pw.weight.reshape(b['mid'], b['cin']))
-                      s1, t1 = self._f32(s1), self._f32(t1)
-                      nblk = lib.effdet_mbconv_tiles_per_image(dtp, h, w, b['cin'], b['mid'], b['k'], b['s'])
-                      mid_buf = dbuf
-                    if mid_buf is dbuf2:
-                        pass
-                    elif nblk > 0:
-                        plan.append((lib.effdet_mbconv_expand_dw,
-                                     (dtp, cur.data_ptr(), dbuf.data_ptr(), w1.data_ptr(), s1.data_ptr(), t1.data_ptr(),
-                                      taps.data_ptr(), s2.data_ptr(), t2.data_ptr(), partial.data_ptr(),
-                                      B, h, w, b['cin'], b['mid'], b['k'], b['s']), what + '.conv_pw+conv_dw',
-                                     dict(kind='mbconv', bytes=B * (h * w * b['cin'] + ho * wo * b['mid']) * es + b['mid'] * b['cin'] * es,
-                                          flops=2 * B * (h * w * b['cin'] * b['mid'] + b['k'] * b['k'] * ho * wo * b['mid']))))
-                    else:
-                        nblk = lib.effdet_dwconv_blocks_per_image(ho, wo, b['mid'])
-                        plan.append((lib.effdet_pw_gemm_bn_act,
-                                     (dt, cur.data_ptr(), B * h * w, b['cin'], w1.data_ptr(), b['mid'], s1.data_ptr(),
-                                      t1.data_ptr(), 1, None, None, 0, ebuf.data_ptr(), 0, 0), what + '.conv_pw',
-                                     self._gemm_meta(B * h * w, b['cin'], b['mid'])))
-                        plan.append((lib.effdet_dwconv_bn_act,
-                                     (dtp, ebuf.data_ptr(), dbuf.data_ptr(), taps.data_ptr(), s2.data_ptr(), t2.data_ptr(), 1,
-                                      partial.data_ptr(), B, h, w, b['mid'], b['k'], b['s']), what + '.conv_dw',
-                                     dict(kind='dwconv', bytes=B * (h * w + ho * wo) * b['mid'] * es,
-                                          flops=2 * b['k'] * b['k'] * B * ho * wo * b['mid'])))
+                        w1 = self._w(m.conv_pw.weight.reshape(b['mid'], b['cin']))
+                        s1, t1 = self._f32(s1), self._f32(t1)
+                        fused, nblk = forms[si][bi]
+                        mid_buf = dbuf
+                        if fused:
+                            plan.append((lib.effdet_mbconv_expand_dw,
+                                         (dtp, cur.data_ptr(), dbuf.data_ptr(), w1.data_ptr(), s1.data_ptr(), t1.data_ptr(),
+                                          taps.data_ptr(), s2.data_ptr(), t2.data_ptr(), partial.data_ptr(),
+                                          B, h, w, b['cin'], b['mid'], b['k'], b['s']), what + '.conv_pw+conv_dw',
+                                         dict(kind='mbconv', bytes=B * (h * w * b['cin'] + ho * wo * b['mid']) * es + b['mid'] * b['cin'] * es,
+                                              flops=2 * B * (h * w * b['cin'] * b['mid'] + b['k'] * b['k'] * ho * wo * b['mid']))))
+                        else:
+                            plan.append((lib.effdet_pw_gemm_bn_act,
+                                         (dt, cur.data_ptr(), B * h * w, b['cin'], w1.data_ptr(), b['mid'], s1.data_ptr(),
+                                          t1.data_ptr(), 1, None, None, 0, ebuf.data_ptr(), 0, 0), what + '.conv_pw',
+                                         self._gemm_meta(B * h * w, b['cin'], b['mid'])))
+                            plan.append((lib.effdet_dwconv_bn_act,
+                                         (dtp, ebuf.data_ptr(), dbuf.data_ptr(), taps.data_ptr(), s2.data_ptr(), t2.data_ptr(), 1,
+                                          partial.data_ptr(), B, h, w, b['mid'], b['k'], b['s']), what + '.conv_dw',
+                                         dict(kind='dwconv', bytes=B * (h * w + ho * wo) * b['mid'] * es,
+                                              flops=2 * b['k'] * b['k'] * B * ho * wo * b['mid'])))
                     pw_out, bn_out = m.conv_pwl, m.bn3
                 elif si == 0 and bi == 0 and self._fuse_stem:
-                    nblk = lib.effdet_stem_dw_parts(dt, H, W, stem_c)     # launched by run_backbone (takes x)
+                    nblk = stem_parts                    # launched by run_backbone (takes x)
                     pw_out, bn_out = m.conv_pw, m.bn2
                     mid_buf = dbuf
                 else:
                     s2, t2 = self._fold(m.bn1)
                     taps = self._f32(self._dw_taps(m.conv_dw.weight))
                     s2, t2 = self._f32(s2), self._f32(t2)
-                    nblk = lib.effdet_dwconv_blocks_per_image(ho, wo, b['mid'])
+                    nblk = forms[si][bi][1]
                     plan.append((lib.effdet_dwconv_bn_act,
                                  (dtp, cur.data_ptr(), dbuf.data_ptr(), taps.data_ptr(), s2.data_ptr(), t2.data_ptr(), 1,
                                   partial.data_ptr(), B, h, w, b['mid'], b['k'], b['s']), what + '.conv_dw',
