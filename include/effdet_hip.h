@@ -410,6 +410,16 @@ int effdet_train_gemm_tn_scaled(void* stream, const float* dY, const float* X, c
 int effdet_train_dwconv_bwd_dx_silu(void* stream, const float* dY, const float* taps, const float* Z, float* dX,
                                     int B, int H, int W, int C, int k, int stride);
 
+/* ---- ProjectionNet training (effdet/efficientdet.py:762: bias-free Linear + ReLU chain), dense float32 rows ------------------
+ * gemm_nt_relu: C[M,N] = relu(A[M,K] W[N,K]^T)               hidden-layer forward (the pre-activation is not kept)
+ * gemm_nt_mask: C[M,N] = (A[M,K] W[N,K]^T) * [mask[M,N] > 0]   input gradient of a Linear fed by a ReLU, W passed transposed and
+ *               mask = that ReLU's output: the ReLU backward (0 where the pre-activation is exactly 0) in the GEMM's epilogue
+ * relu_mask:    out[i] = g[i] * [y[i] > 0] over n floats       the same mask on its own (double backward of gemm_nt_mask)
+ * The weight gradient is effdet_train_gemm_tn (its extra column of sums is not needed). */
+int effdet_train_gemm_nt_relu(void* stream, const float* A, const float* W, float* C, long long M, int K, int N);
+int effdet_train_gemm_nt_mask(void* stream, const float* A, const float* W, const float* mask, float* C, long long M, int K, int N);
+int effdet_train_relu_mask(void* stream, const float* g, const float* y, float* out, long long n);
+
 /* ---- the head towers over the whole pyramid in one launch per layer (effdet/efficientdet.py:438-452: conv weights shared by
  * the levels, BatchNorm per level).  "Packed pyramid" = float32 [sum_l B*Hs[l]*Ws[l]][C], level-major: the NHWC tensors of the L
  * levels (L <= 8) one behind the other.  A 1x1 conv over it is ONE GEMM: effdet_train_gemm_nt_levels / _tn_levels are

@@ -154,6 +154,9 @@ SIGNATURES = {
                                            c_ll, c_int, c_int]),
     'effdet_train_gemm_tn_scaled': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_int, c_int, c_void_p, c_void_p, c_ll]),
     'effdet_train_dwconv_bwd_dx_silu': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'effdet_train_gemm_nt_relu': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int]),
+    'effdet_train_gemm_nt_mask': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int]),
+    'effdet_train_relu_mask': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
     'effdet_train_prep_table': (c_int, [c_void_p, c_void_p, c_int, c_ll]),
     'effdet_train_grads_table': (c_int, [c_void_p, c_void_p, c_int, c_int]),
     'effdet_train_bn_var_finalize': (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

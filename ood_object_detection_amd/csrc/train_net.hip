@@ -77,6 +77,7 @@ struct GemmNtArgs {
     float* C2;                                 // optional second output with the row map of C: silu(C)
     const float* R;                            // optional residual with the row map of C, added after the bias
     const float* a_scale; long long a_scale_rpi;   // optional per-image scale of A's columns (SE gate [img][K]), img = row / a_scale_rpi
+    const float* mask;                         // EPI = 2: [M][N] with the row map of C; C = 0 where mask <= 0
 };
 
 // VW: widest aligned load the rows allow (4 = 16 bytes, 2 = 8 bytes: e.g. the 810-channel class head, 1 = scalar)
@@ -107,7 +108,16 @@ DEV Frag<float> ld_k4(const float* row, int k, int K) {
 // step - operands are fetched TWO steps ahead into two register stages that ping-pong (addresses clamped to the last quad of K,
 // the out-of-range lanes zeroed where the A fragment is built; the SE gate travels with the stage), so the waits are counted
 // and a wave keeps 12 - 16 KB on the wire.  The general loop below issues every load under `k + 3 < K` and waits for it at once.
-template <int VEC, int KS, bool FAST = false>
+// EPI (epilogue of the ProjectionNet MLP, applied last): 0 none; 1 C = relu(C) (Linear + ReLU forward, only the output kept);
+// 2 C = C * [mask > 0] (input gradient of a Linear fed by a ReLU: the mask is that ReLU's output, torch's threshold backward).
+template <int EPI>
+DEV float epi_one(float v, const float* mk) {
+    if constexpr (EPI == 1) return v < 0.f ? 0.f : v;
+    else if constexpr (EPI == 2) return *mk > 0.f ? v : 0.f;
+    else return v;
+}
+
+template <int VEC, int KS, bool FAST = false, int EPI = 0>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
     constexpr int RT = 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -248,6 +258,14 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
                     if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
                     if (p.R) v += *reinterpret_cast<const f32x4*>(p.R + coff + n);
                     if (p.accumulate) v += *reinterpret_cast<const f32x4*>(crow + n);
+                    if constexpr (EPI == 1) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = epi_one<1>(v[r], nullptr);
+                    } else if constexpr (EPI == 2) {
+                        const f32x4 mk = *reinterpret_cast<const f32x4*>(p.mask + coff + n);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = mk[r] > 0.f ? v[r] : 0.f;
+                    }
                     *reinterpret_cast<f32x4*>(crow + n) = v;
                     if (p.C2) {
                         f32x4 q;
@@ -266,6 +284,10 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
                         if (p.bias) v += *reinterpret_cast<const f32x2*>(p.bias + n + 2 * h);
                         if (p.R) v += *reinterpret_cast<const f32x2*>(p.R + coff + n + 2 * h);
                         if (p.accumulate) v += *reinterpret_cast<const f32x2*>(crow + n + 2 * h);
+                        if constexpr (EPI != 0) {
+                            v[0] = epi_one<EPI>(v[0], p.mask + coff + n + 2 * h);
+                            v[1] = epi_one<EPI>(v[1], p.mask + coff + n + 2 * h + 1);
+                        }
                         *reinterpret_cast<f32x2*>(crow + n + 2 * h) = v;
                         if (p.C2) *reinterpret_cast<f32x2*>(p.C2 + coff + n + 2 * h) = f32x2{silu_train(v[0]), silu_train(v[1])};
                     }
@@ -279,6 +301,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
                     if (p.bias) v += p.bias[n + r];
                     if (p.R) v += p.R[coff + n + r];
                     if (p.accumulate) v += crow[n + r];
+                    if constexpr (EPI != 0) v = epi_one<EPI>(v, p.mask + coff + n + r);
                     crow[n + r] = v;
                     if (p.C2) p.C2[coff + n + r] = silu_train(v);
                 }
@@ -1501,6 +1524,7 @@ extern "C" int effdet_train_grads_table(void* stream, const void* table, int n, 
 // ================================================================================================================
 // C ABI
 // ================================================================================================================
+template <int EPI = 0>
 static int launch_gemm_nt(hipStream_t st, GemmNtArgs& p) {
     const float* A = p.A; const float* W = p.W; const float* bias = p.bias; float* C = p.C; float* C2 = p.C2;
     const long long M = p.M; const int K = p.K, N = p.N;
@@ -1514,10 +1538,12 @@ static int launch_gemm_nt(hipStream_t st, GemmNtArgs& p) {
     p.vec_out = N % 4 == 0 && p.cm.ld % 4 == 0 && p.cm.img_stride % 4 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
                 (bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 16 == 0) &&
                 (C2 == nullptr || reinterpret_cast<uintptr_t>(C2) % 16 == 0) &&
-                (p.R == nullptr || reinterpret_cast<uintptr_t>(p.R) % 16 == 0);
+                (p.R == nullptr || reinterpret_cast<uintptr_t>(p.R) % 16 == 0) &&
+                (p.mask == nullptr || reinterpret_cast<uintptr_t>(p.mask) % 16 == 0);
     if (!p.vec_out && N % 2 == 0 && p.cm.ld % 2 == 0 && p.cm.img_stride % 2 == 0 && reinterpret_cast<uintptr_t>(C) % 8 == 0 &&
         (bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 8 == 0) && (C2 == nullptr || reinterpret_cast<uintptr_t>(C2) % 8 == 0) &&
-        (p.R == nullptr || reinterpret_cast<uintptr_t>(p.R) % 8 == 0)) p.vec_out = 2;
+        (p.R == nullptr || reinterpret_cast<uintptr_t>(p.R) % 8 == 0) &&
+        (p.mask == nullptr || reinterpret_cast<uintptr_t>(p.mask) % 8 == 0)) p.vec_out = 2;
     if (gx * ((N + 63) / 64) > 0x7fffffffLL) return EFFDET_EINVAL;
     const dim3 grid((unsigned)(gx * ((N + 63) / 64)));
     const bool vec2 = K % 2 == 0 && p.am.ld % 2 == 0 && p.am.img_stride % 2 == 0 &&
@@ -1525,18 +1551,18 @@ static int launch_gemm_nt(hipStream_t st, GemmNtArgs& p) {
     const bool fast = vec && K >= 4 && p.am.nlev == 0 && p.am.img_stride == 0 && M < 0x7fffffffLL &&
                       (!p.a_scale || (reinterpret_cast<uintptr_t>(p.a_scale) % 16 == 0 && p.a_scale_rpi < 0x7fffffffLL));
     if (fast) {
-        if (splitk) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_nt_kernel<4, 1, true>), grid, dim3(256), 0, st, p);
+        if (splitk) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, true, EPI>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gemm_nt_kernel<4, 1, true, EPI>), grid, dim3(256), 0, st, p);
         return effdet_check_launch();
     }
     if (splitk) {
-        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<4, 4>), grid, dim3(256), 0, st, p);
-        else if (vec2) hipLaunchKernelGGL((gemm_nt_kernel<2, 4>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_nt_kernel<1, 4>), grid, dim3(256), 0, st, p);
+        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, false, EPI>), grid, dim3(256), 0, st, p);
+        else if (vec2) hipLaunchKernelGGL((gemm_nt_kernel<2, 4, false, EPI>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gemm_nt_kernel<1, 4, false, EPI>), grid, dim3(256), 0, st, p);
     } else {
-        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<4, 1>), grid, dim3(256), 0, st, p);
-        else if (vec2) hipLaunchKernelGGL((gemm_nt_kernel<2, 1>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_nt_kernel<1, 1>), grid, dim3(256), 0, st, p);
+        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<4, 1, false, EPI>), grid, dim3(256), 0, st, p);
+        else if (vec2) hipLaunchKernelGGL((gemm_nt_kernel<2, 1, false, EPI>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((gemm_nt_kernel<1, 1, false, EPI>), grid, dim3(256), 0, st, p);
     }
     return effdet_check_launch();
 }
@@ -1548,7 +1574,7 @@ extern "C" int effdet_train_gemm_nt(void* stream, const float* A, long long a_rp
     if (!A || !W || !C || M <= 0 || K <= 0 || N <= 0) return EFFDET_EINVAL;
     GemmNtArgs p;
     p.A = A; p.W = W; p.bias = bias; p.C = C; p.M = M; p.K = K; p.N = N; p.accumulate = accumulate; p.C2 = C2;
-    p.R = nullptr; p.a_scale = nullptr; p.a_scale_rpi = 1;
+    p.R = nullptr; p.a_scale = nullptr; p.a_scale_rpi = 1; p.mask = nullptr;
     p.am = make_rowmap(a_rpi, a_img_stride, a_ld, M, K);
     p.cm = make_rowmap(c_rpi, c_img_stride, c_ld, M, N);
     return launch_gemm_nt(reinterpret_cast<hipStream_t>(stream), p);
@@ -1563,10 +1589,36 @@ extern "C" int effdet_train_gemm_nt_fused(void* stream, const float* A, const fl
     if (a_scale && (K % 4 || reinterpret_cast<uintptr_t>(a_scale) % 16)) return EFFDET_EINVAL;
     GemmNtArgs p;
     p.A = A; p.W = W; p.bias = bias; p.C = C; p.M = M; p.K = K; p.N = N; p.accumulate = 0; p.C2 = C2;
-    p.R = R; p.a_scale = a_scale; p.a_scale_rpi = a_scale ? a_scale_rows : 1;
+    p.R = R; p.a_scale = a_scale; p.a_scale_rpi = a_scale ? a_scale_rows : 1; p.mask = nullptr;
     p.am = make_rowmap(0, 0, 0, M, K);
     p.cm = make_rowmap(0, 0, 0, M, N);
     return launch_gemm_nt(reinterpret_cast<hipStream_t>(stream), p);
+}
+
+// The bias-free Linear + ReLU chain of ProjectionNet (effdet/efficientdet.py:762), dense rows:
+//   gemm_nt_relu: C = relu(A W^T)                       hidden layer forward; only the activation is kept
+//   gemm_nt_mask: C = (A W^T) * [mask > 0], mask [M][N]  dX of the next layer with the ReLU backward in its epilogue
+extern "C" int effdet_train_gemm_nt_relu(void* stream, const float* A, const float* W, float* C, long long M, int K, int N) {
+    EFFDET_ENTER();
+    if (!A || !W || !C || M <= 0 || K <= 0 || N <= 0) return EFFDET_EINVAL;
+    GemmNtArgs p;
+    p.A = A; p.W = W; p.bias = nullptr; p.C = C; p.M = M; p.K = K; p.N = N; p.accumulate = 0; p.C2 = nullptr;
+    p.R = nullptr; p.a_scale = nullptr; p.a_scale_rpi = 1; p.mask = nullptr;
+    p.am = make_rowmap(0, 0, 0, M, K);
+    p.cm = make_rowmap(0, 0, 0, M, N);
+    return launch_gemm_nt<1>(reinterpret_cast<hipStream_t>(stream), p);
+}
+
+extern "C" int effdet_train_gemm_nt_mask(void* stream, const float* A, const float* W, const float* mask, float* C, long long M,
+                                         int K, int N) {
+    EFFDET_ENTER();
+    if (!A || !W || !mask || !C || M <= 0 || K <= 0 || N <= 0) return EFFDET_EINVAL;
+    GemmNtArgs p;
+    p.A = A; p.W = W; p.bias = nullptr; p.C = C; p.M = M; p.K = K; p.N = N; p.accumulate = 0; p.C2 = nullptr;
+    p.R = nullptr; p.a_scale = nullptr; p.a_scale_rpi = 1; p.mask = mask;
+    p.am = make_rowmap(0, 0, 0, M, K);
+    p.cm = make_rowmap(0, 0, 0, M, N);
+    return launch_gemm_nt<2>(reinterpret_cast<hipStream_t>(stream), p);
 }
 
 // The same GEMM over the rows of a level-major packed pyramid (train_levels.hip); the side flagged `*_packed` is the image-major
@@ -1581,7 +1633,7 @@ extern "C" int effdet_train_gemm_nt_levels(void* stream, const float* A, int a_p
     const long long M = make_levels_rowmap(lm, B, L, Hs, Ws, pk_img_stride > 0 ? pk_img_stride : 1, pk_ld > 0 ? pk_ld : 1);
     if (M <= 0) return EFFDET_EINVAL;
     p.A = A; p.W = W; p.bias = bias; p.C = C; p.M = M; p.K = K; p.N = N; p.accumulate = 0; p.C2 = C2;
-    p.R = nullptr; p.a_scale = nullptr; p.a_scale_rpi = 1;
+    p.R = nullptr; p.a_scale = nullptr; p.a_scale_rpi = 1; p.mask = nullptr;
     p.am = a_packed ? lm : make_rowmap(0, 0, 0, M, K);
     p.cm = c_packed ? lm : make_rowmap(0, 0, 0, M, N);
     if ((a_packed && pk_ld < K) || (c_packed && pk_ld < N)) return EFFDET_EINVAL;
@@ -1851,6 +1903,39 @@ extern "C" int effdet_train_ew(void* stream, int op, float* out, const float* a,
     const long long blocks = (n / 4 + 255) / 256;
     if (blocks > 0x7fffffffLL) return EFFDET_EINVAL;
     hipLaunchKernelGGL(ew_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+    return effdet_check_launch();
+}
+
+// out = g * [y > 0] over n floats (four per thread, 16-byte accesses when every pointer allows): the ReLU backward where it
+// cannot ride in a GEMM epilogue (the double backward of effdet_train_gemm_nt_mask)
+namespace {
+struct ReluMaskArgs { const float* g; const float* y; float* out; long long n; int vec; };
+__global__ __launch_bounds__(256) void relu_mask_kernel(ReluMaskArgs p) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= p.n) return;
+    if (p.vec && i + 3 < p.n) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(p.g + i);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(p.y + i);
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = y[r] > 0.f ? g[r] : 0.f;
+        *reinterpret_cast<f32x4*>(p.out + i) = o;
+        return;
+    }
+    for (long long j = i; j < i + 4 && j < p.n; ++j) p.out[j] = p.y[j] > 0.f ? p.g[j] : 0.f;
+}
+
+}  // namespace
+
+extern "C" int effdet_train_relu_mask(void* stream, const float* g, const float* y, float* out, long long n) {
+    EFFDET_ENTER();
+    if (!g || !y || !out || n <= 0) return EFFDET_EINVAL;
+    const long long blocks = (n + 1023) / 1024;
+    if (blocks > 0x7fffffffLL) return EFFDET_EINVAL;
+    const int vec = reinterpret_cast<uintptr_t>(g) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    ReluMaskArgs p{g, y, out, n, vec};
+    hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
     return effdet_check_launch();
 }
 

@@ -1,5 +1,7 @@
 """`AnchorNet` and `ProjectionNet` (reference: effdet/efficientdet.py:697-830), the two small networks the fork's
-few-shot episode code (infer.py) puts next to `MetaHead`.  Forward passes only, on the HIP kernels:
+few-shot episode code (infer.py) puts next to `MetaHead`, on the HIP kernels.  `ProjectionNet` is also differentiable (float32,
+to second order): with gradients wanted its forward is the autograd closure of effdet/meta_ops.py (`projection_forward`); the
+rest is forward only:
 
 * `AnchorNet`: a HeadNet-shaped tower (SeparableConv + per-level BatchNorm (eval statistics) + Swish, then a
   SeparableConv to 9 outputs) -> `effdet_sepconv_fused`, one launch per layer for all levels.
@@ -143,16 +145,25 @@ class ProjectionNet(nn.Module):
         self.projection = nn.Sequential(*layers)
 
     def forward(self, x):
-        """x [..., fpn_channels + 42] -> [..., width / 2]: bias-free Linear + ReLU chain as MFMA GEMMs."""
+        """x [..., fpn_channels + 42] -> [..., width / 2]: bias-free Linear + ReLU chain as MFMA GEMMs.  With gradients wanted
+        (grad mode on and x or a weight requiring grad) the chain is made of the autograd Functions of effdet/meta_ops.py
+        (float32; differentiable twice, like the reference's nn.Sequential), else it runs the fused inference kernels."""
         if x.device.type != 'cuda' or x.dtype not in _DT:
             raise RuntimeError('ProjectionNet runs on the GPU in float32 / bfloat16 only (no CPU fallback)')
+        linears = [m for m in self.projection if isinstance(m, nn.Linear)]
+        lead = x.shape[:-1]
+        if torch.is_grad_enabled() and (x.requires_grad or any(lin.weight.requires_grad for lin in linears)):
+            if x.dtype != torch.float32 or any(lin.weight.dtype != torch.float32 for lin in linears):
+                raise RuntimeError('the differentiable ProjectionNet path is float32 (the reference trains in fp32); use '
+                                   'torch.no_grad() for bfloat16 inference')
+            from . import meta_ops
+            y = meta_ops.projection_forward(x.reshape(-1, x.shape[-1]), [lin.weight.to(device=x.device) for lin in linears])
+            return y.reshape(*lead, y.shape[-1])
         lib = _lib.load()
         dev, dtype, dt = x.device, x.dtype, _DT[x.dtype]
-        lead = x.shape[:-1]
         cur = x.reshape(-1, x.shape[-1])
         M = cur.shape[0]
         st = torch.cuda.current_stream(dev).cuda_stream
-        linears = [m for m in self.projection if isinstance(m, nn.Linear)]
         for i, lin in enumerate(linears):
             K, N = lin.in_features, lin.out_features
             Kp = (K + 7) // 8 * 8                      # the GEMM walks K in 16-byte pieces: zero-pad 106 -> 112

@@ -14,6 +14,13 @@ kernels cover (SiLU: up to its second derivative, i.e. exactly the double backwa
     DwBwdDw     tap correlation [9, C]    backward: DwConv(X, h), DwBwdDx(G, h)
     ColSum / RowBcast / MulCh / ColDot / Mul / Add / Silu / SiluBwd / SiluBwd2
 
+and, for ProjectionNet's bias-free Linear + ReLU chain (`projection_forward`):
+
+    ProjLinear  y = T W^T (relu'd)        backward: LinearMask(g, W^T, T) | Linear(g, W^T), MmTNRelu(g, T) | MmTN(g, T)
+    LinearMask  (A W^T) * [Y > 0]         backward: Linear(ReluMask(gg, Y), W^T), MmTN(ReluMask(gg, Y), A)
+    MmTNRelu    G^T relu(Y)               backward: Linear(Y, P), LinearMask(G, P^T, Y)
+    ReluMask    g * [Y > 0]               backward: ReluMask(gg, Y)
+
 All tensors are contiguous float32 on one GPU; activations are [M, C] or [B, H, W, C] (NHWC).  Parameter-sized algebra
 (transposes, the [C]-vectors of batch-norm statistics) stays in PyTorch, as in the pretrain step.  No CPU fallback.
 """
@@ -194,6 +201,98 @@ class SiluBwd2(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             raise NotImplementedError('third-order derivative of SiLU: the MetaHead is differentiable to second order (MAML)')
         return None, (SiluBwd2.apply(Z, g, B) if ctx.needs_input_grad[1] else None), (SiluBwd2.apply(Z, A, g) if ctx.needs_input_grad[2] else None)
+
+
+class ReluMask(torch.autograd.Function):
+    """G * [Y > 0]: the backward of a ReLU whose output is Y (Y itself gets no gradient: relu'' is 0 almost everywhere)"""
+    @staticmethod
+    def forward(ctx, G, Y):
+        G, Y = _c(G), _c(Y)
+        ctx.save_for_backward(Y)
+        o = ops_for(G.device)
+        out = torch.empty_like(G)
+        _lib.check(o.lib.effdet_train_relu_mask(o.st(), G.data_ptr(), Y.data_ptr(), out.data_ptr(), G.numel()), 'effdet_train_relu_mask')
+        return out
+
+    @staticmethod
+    def backward(ctx, gg):
+        (Y,) = ctx.saved_tensors
+        return ReluMask.apply(gg, Y), None
+
+
+class LinearMask(torch.autograd.Function):
+    """(A W^T) * [Y > 0] in one launch: the input gradient of a Linear fed by a ReLU with output Y (W passed transposed)"""
+    @staticmethod
+    def forward(ctx, A, W, Y):
+        A, W, Y = _c(A), _c(W), _c(Y)
+        ctx.save_for_backward(A, W, Y)
+        o = ops_for(A.device)
+        (M, K), N = A.shape, W.shape[0]
+        out = o.new(M, N)
+        _lib.check(o.lib.effdet_train_gemm_nt_mask(o.st(), A.data_ptr(), W.data_ptr(), Y.data_ptr(), out.data_ptr(), M, K, N),
+                   'effdet_train_gemm_nt_mask')
+        return out
+
+    @staticmethod
+    def backward(ctx, gg):
+        A, W, Y = ctx.saved_tensors
+        g = ReluMask.apply(gg, Y)
+        return (Linear.apply(g, W.t().contiguous(), None) if ctx.needs_input_grad[0] else None,
+                MmTN.apply(g, A) if ctx.needs_input_grad[1] else None, None)
+
+
+class MmTNRelu(torch.autograd.Function):
+    """G [M, N], Y [M, K] a ReLU output -> G^T relu(Y) = G^T Y [N, K]; the gradient for Y goes through the ReLU"""
+    @staticmethod
+    def forward(ctx, G, Y):
+        G, Y = _c(G), _c(Y)
+        ctx.save_for_backward(G, Y)
+        return ops_for(G.device).gemm_tn(G, Y, G.shape[1], Y.shape[1])[0].clone()
+
+    @staticmethod
+    def backward(ctx, P):
+        G, Y = ctx.saved_tensors
+        return (Linear.apply(Y, P, None) if ctx.needs_input_grad[0] else None,                   # Y P^T         [M, N]
+                LinearMask.apply(G, P.t().contiguous(), Y) if ctx.needs_input_grad[1] else None)  # (G P) [Y > 0] [M, K]
+
+
+class ProjLinear(torch.autograd.Function):
+    """One bias-free layer of ProjectionNet's MLP (effdet/efficientdet.py:762): T [M, K], W [N, K] -> T W^T, relu'd when relu_out.
+    A hidden layer's output feeds only the next layer, which takes the ReLU as its own (relu_in: T is that ReLU's output, so
+    relu(T) = T): its backward returns the gradient of the PRE-activation, masked in the dX GEMM's epilogue, and the ReLU costs no
+    pass of its own in either direction.  To second order every gradient a hidden output receives goes through a masked path
+    (LinearMask, MmTNRelu), so it is that of its pre-activation - what the meta phase's create_graph=True needs.  Third order is
+    not closed: the G-gradient of MmTNRelu (Linear(Y, P)) would send an unmasked gradient into Y."""
+    @staticmethod
+    def forward(ctx, T, W, relu_in, relu_out):
+        T, W = _c(T), _c(W)
+        ctx.save_for_backward(T, W)
+        ctx.relu_in = relu_in
+        o = ops_for(T.device)
+        if not relu_out:
+            return o.gemm_nt(T, W)
+        (M, K), N = T.shape, W.shape[0]
+        out = o.new(M, N)
+        _lib.check(o.lib.effdet_train_gemm_nt_relu(o.st(), T.data_ptr(), W.data_ptr(), out.data_ptr(), M, K, N), 'effdet_train_gemm_nt_relu')
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        T, W = ctx.saved_tensors
+        gT = gW = None
+        if ctx.needs_input_grad[0]:
+            gT = LinearMask.apply(g, W.t().contiguous(), T) if ctx.relu_in else Linear.apply(g, W.t().contiguous(), None)
+        if ctx.needs_input_grad[1]:
+            gW = MmTNRelu.apply(g, T) if ctx.relu_in else MmTN.apply(g, T)
+        return gT, gW, None, None
+
+
+def projection_forward(x2d, weights):
+    """ProjectionNet.forward on the primitives above: x2d [M, K] float32, weights = the Linear weights in order -> [M, N_last]"""
+    t = x2d
+    for i, w in enumerate(weights):
+        t = ProjLinear.apply(t, w, i > 0, i + 1 < len(weights))
+    return t
 
 
 def _dw_dims(X):
