@@ -285,6 +285,14 @@ int effdet_label_anchors(void* stream, const float* anchors, const float* gt_box
                          int B, int Mmax, long long N, float match_threshold, long long* cls_t, float* box_t,
                          float* num_positives, long long* match, void* workspace, long long workspace_bytes);
 
+/* The `task_cls` branch of AnchorLabeler.batch_label_anchors (effdet/anchors.py:396-403), run before effdet_label_anchors
+ * on the same padded tensors: per image, every row whose IoU (same arithmetic as above; boxlist1 = the rows of class
+ * task_cls) with some row of class task_cls is > iou_threshold (the reference: 0.9) gets class task_cls, in place.
+ * The decision reads the classes as they were on entry.  Padding rows (class -1, zero box) have IoU 0 and never change;
+ * an image without a row of class task_cls is left alone.  task_cls >= 0, 0 < Mmax <= 512.  One launch for the batch. */
+int effdet_relabel_task_cls(void* stream, const float* gt_boxes, long long* gt_cls, int B, int Mmax,
+                            long long task_cls, float iou_threshold);
+
 /* ProjectionNet.weighted_median (effdet/efficientdet.py:748-760): per column of embds [n][d] (n <= 1024), the value at
  * which the cumulative confidence (in ascending value order) first reaches half of sum(confs); conf_sum[0] = that sum. */
 int effdet_weighted_median(void* stream, const float* embds, const float* confs, int n, int d, float* med, float* conf_sum);

@@ -91,6 +91,7 @@ SIGNATURES = {
     'effdet_label_anchors_workspace_bytes': (c_ll, [c_int, c_int, c_ll]),
     'effdet_label_anchors': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_float, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_relabel_task_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_float]),
     'effdet_train_gemm_nt': (c_int, [c_void_p, c_void_p, c_ll, c_ll, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_ll,
                                      c_ll, c_int, c_int, c_int, c_void_p]),
     'effdet_train_gemm_tn_workspace_floats': (c_ll, [c_ll, c_int, c_int]),

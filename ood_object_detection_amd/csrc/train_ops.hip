@@ -9,6 +9,8 @@
 //                           IouSimilarity (region_similarity_calculator.py:24-73) -> ArgMaxMatcher with thresholds
 //                           0.5/0.5 and force_match_for_each_row (argmax_matcher.py:116-146) -> class targets - 1,
 //                           FasterRcnnBoxCoder.encode (box_coder.py:81-110, eps 1e-8), num_positives.
+//   effdet_relabel_task_cls the `task_cls` branch in front of it (effdet/anchors.py:396-403): boxes whose IoU with a box
+//                           of the task class exceeds 0.9 take that class.
 //
 // Head outputs use the packed layout of the inference path: cls [B, N, C], box [B, N, 4]; targets are the
 // per-level reference tensors flattened and concatenated in the same anchor order: cls_t [B, N] int64,
@@ -258,7 +260,44 @@ __global__ __launch_bounds__(LT) void label_targets_kernel(LabelArgs p) {
     if (threadIdx.x == 0 && s != 0.f) atomicAdd(&p.num_pos[b], s);       // integer-valued floats: order independent
 }
 
+// task_cls relabelling (effdet/anchors.py:396-403) in front of the assignment: one block per image.  The classes are read
+// into LDS first, so the decision uses the classes as they were (the reference builds its mask before it writes): a box
+// that has just been relabelled does not act as a task box.  The reference's condition "at least one box is not of the
+// task class" needs no test of its own - where every box is of the task class the assignment below changes nothing.
+// Padding rows (class -1, zero box) have intersection 0 with everything: IoU 0, never relabelled; they are not task boxes.
+__global__ __launch_bounds__(LT) void relabel_task_kernel(const float* gt_boxes, long long* gt_cls, int Mmax, long long task_cls,
+                                                          float thr) {
+    __shared__ long long cls[MAXGT];
+    const int b = blockIdx.x;
+    long long* gc = gt_cls + (long long)b * Mmax;
+    const float* gb = gt_boxes + (long long)b * Mmax * 4;
+    for (int j = threadIdx.x; j < Mmax; j += LT) cls[j] = gc[j];
+    __syncthreads();
+    for (int j = threadIdx.x; j < Mmax; j += LT) {
+        if (cls[j] == task_cls) continue;
+        const float* a = gb + j * 4;
+        const float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+        const float aa = (a2 - a0) * (a3 - a1);
+        bool hit = false;
+        for (int i = 0; i < Mmax && !hit; ++i) {
+            if (cls[i] != task_cls) continue;
+            const float* g = gb + i * 4;                                  // boxlist1 = the task boxes, boxlist2 = all boxes
+            hit = iou_yxyx(g, (g[2] - g[0]) * (g[3] - g[1]), a0, a1, a2, a3, aa) > thr;
+        }
+        if (hit) gc[j] = task_cls;
+    }
+}
+
 }  // namespace
+
+extern "C" int effdet_relabel_task_cls(void* stream, const float* gt_boxes, long long* gt_cls, int B, int Mmax,
+                                       long long task_cls, float iou_threshold) {
+    EFFDET_ENTER();
+    if (!gt_boxes || !gt_cls || B <= 0 || Mmax <= 0 || Mmax > MAXGT || task_cls < 0) return EFFDET_EINVAL;
+    hipLaunchKernelGGL(relabel_task_kernel, dim3(B), dim3(LT), 0, reinterpret_cast<hipStream_t>(stream), gt_boxes, gt_cls, Mmax,
+                       task_cls, iou_threshold);
+    return effdet_check_launch();
+}
 
 extern "C" long long effdet_detection_loss_workspace_floats(int B, long long N, int C) {
     if (B <= 0 || N <= 0 || C <= 0) return EFFDET_EINVAL;

@@ -190,8 +190,11 @@ class AnchorLabeler(object):
         return cls_out, box_out
 
     def batch_label_anchors(self, gt_boxes, gt_classes, filter_valid=True, task_cls=None):
-        if task_cls is not None:
-            raise NotImplementedError('task_cls relabelling (effdet/anchors.py:397-404) is not built')
+        """task_cls (effdet/anchors.py:396-403, used by dataloader.py:210 for the projection images): per image, every box
+        whose IoU with some box of class `task_cls` is > 0.9 becomes class `task_cls` before the assignment - decided on
+        the device by `effdet_relabel_task_cls`, one launch for the batch.  Like the reference, the new classes are written
+        into the caller's `gt_classes[i]` tensors.  An image without a box of class `task_cls` is left alone (the reference
+        raises there, on the `max` of an empty tensor; dataloader.py never produces one)."""
         lib = _lib.load()
         boxes = self.anchors.boxes
         if boxes.device.type != 'cuda':
@@ -209,7 +212,17 @@ class AnchorLabeler(object):
             allb = torch.cat([b.to(device=dev, dtype=torch.float32).reshape(-1, 4) for b, m in zip(gt_boxes, lens) if m], 0)
             allc = torch.cat([c.to(device=dev, dtype=torch.int64).reshape(-1) for c, m in zip(gt_classes, lens) if m], 0)
             gb.view(-1, 4)[rows] = allb
-            gc.view(-1)[rows] = allc if filter_valid else allc.clamp(min=0)
+            if task_cls is None:
+                gc.view(-1)[rows] = allc if filter_valid else allc.clamp(min=0)
+            else:
+                gc.view(-1)[rows] = allc                     # the relabelling sees the classes as given
+                _lib.check(lib.effdet_relabel_task_cls(_stream(boxes), gb.data_ptr(), gc.data_ptr(), B, Mmax, int(task_cls), 0.9),
+                           'effdet_relabel_task_cls')
+                newc = gc.view(-1)[rows]
+                for c, part in zip([c for c, m in zip(gt_classes, lens) if m], newc.split([m for m in lens if m])):
+                    c.copy_(part.reshape(c.shape))           # anchors.py:403 writes into the caller's tensor
+                if not filter_valid:
+                    gc.view(-1)[rows] = newc.clamp(min=0)
         N = boxes.shape[0]
         cls_t = torch.empty(B, N, dtype=torch.int64, device=dev)
         box_t = torch.empty(B, N, 4, dtype=torch.float32, device=dev)

@@ -435,7 +435,10 @@ class EfficientDet(nn.Module):
         if fast_weights is not None or ret_activs:
             raise NotImplementedError('fast_weights / ret_activs belong to the MetaHead path')
         if mode in _TRAIN_MODES and self.wants_autograd():
-            return _run_train(self, x, mode)
+            # 'not_cls' of a bfloat16 model stays on the inference kernels (the training engine is float32; infer.py's
+            # validation passes call it on whatever dtype the model has)
+            if mode != 'not_cls' or self.backbone.conv_stem.weight.dtype == torch.float32:
+                return _run_train(self, x, mode)
         return _run(self, x, mode)
 
     def wants_autograd(self):
@@ -447,12 +450,12 @@ class EfficientDet(nn.Module):
         return self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
 
-_TRAIN_MODES = ('full_net', 'bb', 'fpn_and_head')
+_TRAIN_MODES = ('full_net', 'bb', 'fpn_and_head', 'not_cls')
 
 
 def _run_train(model, x, mode):
     """Differentiable forward on the training engine (train_engine.py); outputs carry autograd history."""
-    from ..train_engine import TrainEngine, run_backbone, run_fpn_heads
+    from ..train_engine import TrainEngine, run_backbone, run_fpn_heads, run_not_cls
     eng = model._train_engine
     if eng is None or eng.dev != model.backbone.conv_stem.weight.device or eng.signature != model.train_signature():
         eng = model._train_engine = TrainEngine(model)
@@ -461,6 +464,8 @@ def _run_train(model, x, mode):
         return run_backbone(eng, x)
     if mode == 'fpn_and_head':
         return run_fpn_heads(eng, list(x))
+    if mode == 'not_cls':                                  # efficientdet.py:905-908: (activs, x_box); class_net is not touched
+        return run_not_cls(eng, list(x))
     return run_fpn_heads(eng, run_backbone(eng, x))
 
 

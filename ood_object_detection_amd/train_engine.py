@@ -12,8 +12,9 @@ deterministic, and bitwise reproducible (all reductions are fixed-order).
 Division of labour: every activation-sized operation (anything O(B*H*W*C)) is a HIP kernel of csrc/train_net.hip (plus
 the forward kernels effdet_dwconv_bn_act / effdet_maxpool_same / effdet_se_gate); PyTorch does parameter-sized glue only
 (folding BN into conv weights, transposing weights, the closed-form chain rule from the kernels' raw sums to
-d weight / d gamma / d beta / d edge_weights) and owns memory, streams and the autograd graph the two stage
-functions (`BackboneFn`, `FpnHeadFn`) plug into, so `loss.backward()` fills `.grad` exactly like the reference.
+d weight / d gamma / d beta / d edge_weights) and owns memory, streams and the autograd graph the stage
+functions (`BackboneFn`, `FpnHeadFn`, and `NotClsFn` for infer.py's `mode='not_cls'`: BiFPN + box head with the pyramid handed
+out) plug into, so `loss.backward()` fills `.grad` exactly like the reference.
 There is no CPU fallback.
 """
 import ctypes
@@ -483,8 +484,8 @@ class _Ops(object):
 
 
 class TrainEngine(object):
-    """Stage functions `bb_forward/backward`, `fh_forward/backward` over one model (its parameters are read live, so an
-    optimizer step needs no re-preparation)."""
+    """Stage functions `bb_forward/backward`, `fh_forward/backward`, `nc_forward/backward` over one model (its parameters are
+    read live, so an optimizer step needs no re-preparation)."""
 
     def __init__(self, model):
         p0 = model.backbone.conv_stem.weight
@@ -506,7 +507,9 @@ class TrainEngine(object):
         self.bb_pad = (1 << 24) if getattr(model.backbone, 'pad_type', 'same') == '' else 0
         self.fpn_pad = (1 << 24) if cfg.pad_type == '' else 0
         self._ones = {}
-        self._tables = {'bb': _StageTables(self.ops), 'fh': _StageTables(self.ops)}
+        # 'nc' (mode='not_cls': BiFPN + box head, pyramid handed out) keeps tables of its own: a captured PretrainStep graph replays
+        # the raw addresses of the 'fh' set, and a stage that records a subset of 'fh' (no class head) must not freeze that set
+        self._tables = {'bb': _StageTables(self.ops), 'fh': _StageTables(self.ops), 'nc': _StageTables(self.ops)}
         self._stage = None                          # the stage whose forward / backward is running (None: called from outside, e.g. meta_grad)
         import os
         self.use_tables = os.environ.get('EFFDET_TRAIN_TABLES', '1') != '0'     # 0: every derived weight / gradient conv by conv (debugging)
@@ -779,17 +782,28 @@ class TrainEngine(object):
             return grads
         return self._in_stage('bb', run)
 
-    def fh_forward(self, feats, want_cls=True, want_box=True):
-        """feats: backbone feature maps (NHWC).  -> (cls_all [B,N,C], box_all [B,N,4], saved)"""
+    def fh_forward(self, feats, want_cls=True, want_box=True, want_pyr=False, stage='fh'):
+        """feats: backbone feature maps (NHWC).  -> (cls_all [B,N,C], box_all [B,N,4], saved); want_pyr: saved['pyr'] holds the
+        pyramid (NHWC tensors of this call alone).  stage: the table set to use ('fh', or 'nc' for the 'not_cls' stage)"""
         def run():
             if self.use_tables:
-                self._tables['fh'].run_prep()
-            return self._fh_forward(feats, want_cls, want_box)
-        return self._in_stage('fh', run)
+                self._tables[stage].run_prep()
+            return self._fh_forward(feats, want_cls, want_box, want_pyr)
+        return self._in_stage(stage, run)
 
-    def fh_backward(self, g_cls, g_box, saved, need_dfeats=True):
-        """-> (d feats list (NHWC), {param name: grad})"""
-        return self._in_stage('fh', self._fh_backward, g_cls, g_box, saved, need_dfeats)
+    def fh_backward(self, g_cls, g_box, saved, need_dfeats=True, g_pyr=None, stage='fh'):
+        """g_pyr: d loss / d pyramid level (NHWC, None allowed per level), added to what the heads send down.
+        -> (d feats list (NHWC), {param name: grad})"""
+        return self._in_stage(stage, self._fh_backward, g_cls, g_box, saved, need_dfeats, g_pyr)
+
+    def nc_forward(self, feats):
+        """mode='not_cls' (efficientdet.py:905-908): BiFPN + box head.  -> (pyramid NHWC list, box_all [B,N,4], saved)"""
+        _, box_all, saved = self.fh_forward(feats, want_cls=False, want_box=True, want_pyr=True, stage='nc')
+        return saved.pop('pyr'), box_all, saved
+
+    def nc_backward(self, g_pyr, g_box, saved, need_dfeats=True):
+        """g_pyr: one gradient per pyramid level (NHWC), g_box [B,N,4]; any of them None.  -> (d feats list, {param name: grad})"""
+        return self.fh_backward(None, g_box, saved, need_dfeats, g_pyr=g_pyr, stage='nc')
 
     def _bb_forward(self, x):
         """x: [B,3,H,W] float32 (normalised) or uint8 (raw; loader normalisation applied).  -> (feats NHWC list, saved)"""
@@ -950,7 +964,7 @@ class TrainEngine(object):
             dy = self._convbn_bwd(rec['conv'], dy, grads)
         return dy
 
-    def _fh_forward(self, feats, want_cls=True, want_box=True):
+    def _fh_forward(self, feats, want_cls=True, want_box=True, want_pyr=False):
         """feats: backbone feature maps (NHWC).  -> (cls_all [B,N,C], box_all [B,N,4], saved)"""
         model, ops, F, L = self.model, self.ops, self.F, self.L
         fpn = model.fpn
@@ -1014,6 +1028,8 @@ class TrainEngine(object):
         saved['pyr_ids'] = list(ids)
         saved['n_tensors'] = len(tensors)
         saved['levels'] = [(t['t'].shape[1], t['t'].shape[2]) for t in pyr]
+        if want_pyr:
+            saved['pyr'] = [t['t'] for t in pyr]
         # ---- heads
         B = feats[0].shape[0]
         hw = saved['levels']
@@ -1126,7 +1142,7 @@ class TrainEngine(object):
             da = dw_grads(rec, dd, '%sconv_rep.%d.' % (name, r))
         return da
 
-    def _fh_backward(self, g_cls, g_box, saved, need_dfeats=True):
+    def _fh_backward(self, g_cls, g_box, saved, need_dfeats=True, g_pyr=None):
         """-> (d feats list (NHWC), {param name: grad})"""
         ops, L = self.ops, self.L
         grads = {}
@@ -1148,6 +1164,10 @@ class TrainEngine(object):
         if dpyr is not None:
             for l, d in enumerate(lv.split(dpyr)):
                 add_to(saved['pyr_ids'][l], d)
+        if g_pyr is not None:
+            for l, g in enumerate(g_pyr):
+                if g is not None:
+                    add_to(saved['pyr_ids'][l], g.contiguous())
         for nrec in reversed(saved['nodes']):
             dy = dt[nrec['out_id']]
             if dy is None:
@@ -1243,6 +1263,39 @@ class FpnHeadFn(torch.autograd.Function):
         return (None, None, None) + tuple(out) + tuple(_param_grads(ctx, grads, 3 + ctx.n_feats))
 
 
+class NotClsFn(torch.autograd.Function):
+    """backbone features (NHWC) -> the pyramid levels (NHWC) and the packed box head output [B,N,4] (mode='not_cls');
+    gradients for the BiFPN / box head parameters and the features.  The class head is no part of this node.  First order only."""
+
+    @staticmethod
+    def forward(ctx, eng, names, n_feats, *tensors):
+        feats = [t.contiguous() for t in tensors[:n_feats]]
+        pyr, box_all, saved = eng.nc_forward(feats)
+        ctx.eng, ctx.saved, ctx.names, ctx.n_feats, ctx.params = eng, saved, names, n_feats, tensors[n_feats:]
+        ctx.set_materialize_grads(False)         # a level (or the boxes) the loss does not read arrives as None, not as zeros
+        return tuple(pyr) + (box_all,)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gouts):
+        need = [bool(ctx.needs_input_grad[3 + i]) for i in range(ctx.n_feats)]
+        dfeats, grads = ctx.eng.nc_backward(list(gouts[:-1]), gouts[-1], ctx.saved, need_dfeats=any(need))
+        ctx.saved = None
+        out = [d if n else None for d, n in zip(dfeats, need)]
+        return (None, None, None) + tuple(out) + tuple(_param_grads(ctx, grads, 3 + ctx.n_feats))
+
+
+def _level_views(t, K, hw, A):
+    """packed head output [B, N, K] -> per-level NCHW-shaped views [B, A*K, h, w]"""
+    out, off = [], 0
+    B = t.shape[0]
+    for h, w in hw:
+        v = t[:, off * A:(off + h * w) * A, :].reshape(B, h, w, A * K)
+        out.append(v.permute(0, 3, 1, 2))
+        off += h * w
+    return out
+
+
 def run_backbone(eng, x):
     """-> NCHW-shaped views of the NHWC feature maps, attached to the autograd graph"""
     pl = _param_list(eng.model.backbone, '')
@@ -1260,15 +1313,16 @@ def run_fpn_heads(eng, feats_nchw):
     hw = [(f.shape[2], f.shape[3]) for f in feats_nchw]
     while len(hw) < eng.L:
         hw.append((_same_out(hw[-1][0], 2), _same_out(hw[-1][1], 2)))
-    A = eng.A
+    return _level_views(cls_all, model.config.num_classes, hw, eng.A), _level_views(box_all, 4, hw, eng.A)
 
-    def views(t, K):
-        out, off = [], 0
-        B = t.shape[0]
-        for h, w in hw:
-            v = t[:, off * A:(off + h * w) * A, :].reshape(B, h, w, A * K)
-            out.append(v.permute(0, 3, 1, 2))
-            off += h * w
-        return out
 
-    return views(cls_all, model.config.num_classes), views(box_all, 4)
+def run_not_cls(eng, feats_nchw):
+    """-> (activs: the pyramid as NCHW-shaped views [B,F,h,w], x_box: box head outputs [B,4A,h,w]), attached to the autograd graph"""
+    model = eng.model
+    pl = _param_list(model.fpn, 'fpn.') + _param_list(model.box_net, 'box_net.')
+    names = [n for n, _ in pl]
+    feats = [f.permute(0, 2, 3, 1) for f in feats_nchw]
+    out = NotClsFn.apply(eng, names, len(feats), *(feats + [p for _, p in pl]))
+    pyr, box_all = out[:-1], out[-1]
+    hw = [(t.shape[1], t.shape[2]) for t in pyr]
+    return [t.permute(0, 3, 1, 2) for t in pyr], _level_views(box_all, 4, hw, eng.A)

@@ -17,6 +17,7 @@ Fixtures written
     loss.npz                  loss.loss_fn values and autograd gradients
     evaluation.npz            ObjectDetectionEvaluator mAP / CorLoc on seeded detections
     labeler.npz               anchors.AnchorLabeler.batch_label_anchors
+    labeler_task_cls.npz      the same with task_cls (anchors.py:396-403): relabelled classes and targets
     config.npz                model_config.get_efficientdet_config + fpn_config.bifpn_config dumps
     bifpn_head.npz            EfficientDet(config) forward (reference BiFpn/HeadNet code on stub
                               conv layers and the oracle backbone): key/shape list + outputs
@@ -214,6 +215,59 @@ def gen_labeler():
         out['gt_boxes%d' % i], out['gt_cls%d' % i] = gt_boxes[i], gt_cls[i]
     out['npos'] = torch.stack(npos)
     save('labeler', **out)
+
+
+def gen_labeler_task_cls():
+    """batch_label_anchors(..., task_cls=c): the reference's own statements anchors.py:397-403 (through
+    target_assigner._similarity_calc.compare), then TargetAssigner.assign per image as gen_labeler does."""
+    from effdet.anchors import Anchors, AnchorLabeler
+    from effdet.object_detection import BoxList
+    anchors = Anchors(3, 7, 3, [(1.0, 1.0), (1.4, 0.7), (0.7, 1.4)], 4.0, (128, 128))
+    lab = AnchorLabeler(anchors, num_classes=6, match_threshold=0.5)
+    task_cls = 3
+    f = lambda rows: torch.tensor(rows, dtype=torch.float32).reshape(-1, 4)
+    l = lambda vals: torch.tensor(vals, dtype=torch.int64)
+    images = [
+        # task box; class 5 with IoU 0.95 (relabelled); class 2 with IoU 0.85 (kept); class -1 with IoU 0.925 (the reference
+        # relabels it too: its mask does not look at the class); class 1 far away
+        (f([[10, 10, 50, 50], [10, 10, 48, 50], [10, 10, 44, 50], [10, 10, 47, 50], [70, 70, 120, 110]]), l([3, 5, 2, -1, 1])),
+        # every box of the task class: the branch is skipped
+        (f([[5, 5, 40, 40], [6, 5, 40, 40], [60, 20, 100, 90]]), l([3, 3, 3])),
+        # one task box and several disjoint others
+        (f([[20, 20, 60, 70], [64, 20, 100, 60], [2, 80, 18, 120], [70, 72, 126, 126], [0, 0, 16, 16]]), l([3, 1, 6, 2, 4])),
+        # empty image
+        (f([]), l([])),
+        # two task boxes; a box near the second one only (IoU 0.92), one at IoU 0.88 to the first, and a relabelled box's
+        # neighbour (IoU 0.96 to the relabelled box, 0.8832 to the task box) that must stay: no chaining
+        (f([[8, 8, 58, 58], [64, 60, 114, 110], [64, 60, 110, 110], [8, 8, 52, 58], [64, 60, 108.16, 110]]), l([3, 3, 4, 6, 1])),
+    ]
+    out = {'task_cls': np.int64(task_cls), 'n_images': np.int64(len(images))}
+    npos, margin = [], 1.0
+    for i, (boxes, classes) in enumerate(images):
+        out['gt_boxes%d' % i], out['gt_cls%d' % i] = boxes.clone(), classes.clone()
+        gt_classes = [classes.clone()]
+        gt_boxes = [boxes]
+        k = 0
+        task_obj_mask = gt_classes[k] == task_cls                                        # anchors.py:397
+        if (~task_obj_mask).sum() > 0:                                                   # :398
+            gt_box_list = BoxList(gt_boxes[k])
+            task_obj_list = BoxList(gt_boxes[k][task_obj_mask])
+            box_sims = lab.target_assigner._similarity_calc.compare(task_obj_list, gt_box_list)
+            overlapping_boxes, __ = (box_sims > 0.9).max(0)
+            gt_classes[k][overlapping_boxes] = task_cls                                  # :403
+            margin = min(margin, float((box_sims - 0.9).abs().min()))
+        out['relabelled%d' % i] = gt_classes[k]
+        valid = gt_classes[k] > -1
+        c, b, m = lab.target_assigner.assign(BoxList(anchors.boxes), BoxList(gt_boxes[k][valid]), gt_classes[k][valid])
+        out['cls_flat%d' % i] = (c - 1).long()
+        out['box_flat%d' % i] = b.contiguous()
+        npos.append((m.match_results > -1).float().sum())
+    # the comparison is strict and float32 rounding must not decide a case
+    assert margin > 1e-4, margin
+    rel = [out['relabelled%d' % i].tolist() for i in range(len(images))]
+    assert rel == [[3, 3, 2, 3, 1], [3, 3, 3], [3, 1, 6, 2, 4], [], [3, 3, 3, 6, 1]], rel
+    out['npos'] = torch.stack(npos)
+    save('labeler_task_cls', **out)
 
 
 def gen_config():
@@ -473,6 +527,6 @@ def gen_evaluation():
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ['anchors', 'post_process', 'decode', 'soft_nms', 'generate_detections', 'loss',
-                             'labeler', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'meta_nets', 'aux_losses']
+                             'labeler', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'meta_nets', 'aux_losses']
     for w in which:
         globals()['gen_' + w]()

@@ -19,8 +19,13 @@ def main(root, out):
     traces = glob.glob(os.path.join(root, '**', '*kernel_trace.csv'), recursive=True)
     agg = defaultdict(lambda: [0, 0])
     by_grid = defaultdict(lambda: [0, 0])
+    gap = float(os.environ.get('ROCPROF_AFTER_GAP_MS', 0)) * 1e6      # > 0: only the dispatches after the last idle gap that long
     for f in traces:
-        for r in csv.DictReader(open(f)):
+        rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r['Start_Timestamp']))
+        if gap > 0:
+            cut = [i for i in range(1, len(rows)) if int(rows[i]['Start_Timestamp']) - int(rows[i - 1]['End_Timestamp']) > gap]
+            rows = rows[cut[-1]:] if cut else rows
+        for r in rows:
             k = short(r.get('Kernel_Name', '?'))
             dur = int(r['End_Timestamp']) - int(r['Start_Timestamp'])
             agg[k][0] += 1
@@ -30,7 +35,9 @@ def main(root, out):
             by_grid[(k[:60], g)][1] += dur
     if agg:
         tot = sum(v[1] for v in agg.values())
-        lines.append('# rocprofv3 --kernel-trace: per kernel (all dispatches of the run)')
+        lines.append('# rocprofv3 --kernel-trace: per kernel (%s): %d dispatches, %.1f us of kernel time'
+                     % ('the dispatches after the last idle gap > %s ms' % os.environ['ROCPROF_AFTER_GAP_MS'] if gap > 0 else
+                        'all dispatches of the run', sum(v[0] for v in agg.values()), tot / 1e3))
         lines.append('%-112s %8s %12s %10s %6s' % ('kernel', 'calls', 'total_us', 'avg_us', '%'))
         for k, (n, t) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
             lines.append('%-112s %8d %12.1f %10.2f %6.2f' % (k, n, t / 1e3, t / 1e3 / n, 100.0 * t / tot))
