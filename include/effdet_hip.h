@@ -539,6 +539,40 @@ int effdet_ood_image_score(void* stream, const float* energy, int B, long long N
  * counts[0] = #{(i,j): pos_i > neg_j}, counts[1] = #{pos_i == neg_j};  AUROC = (counts[0] + counts[1]/2) / (n_pos*n_neg). */
 int effdet_auroc_counts(void* stream, const float* pos, const float* neg, int n_pos, int n_neg, unsigned long long* counts);
 
+/* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
+
+/* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at
+ * confs[l] + b * image_strides[l] (elements).  outs[l] [B][keeps[l]] int32 receives the indices of the keeps[l] largest,
+ * ascending; equal confidences at the cut go to the lower index; keeps[l] == counts[l] keeps all.  The pointer / size
+ * arrays are host arrays of num_levels (<= 8) entries.  One launch, one workgroup per (image, level). */
+int effdet_episode_select(void* stream, int B, int num_levels, const void* const* confs, const long long* image_strides,
+                          const int* counts, const int* keeps, void* const* outs);
+
+/* ProjectionNet feed rows of the selected anchors: feed [B][R][Kp], R = sum keeps[l], row =
+ * [F embedding | anch_enc[a] (8) | lev_enc[first_level + l] (6) | cell enc (28) | zeros], and conf_out [B][R].
+ * activs[l]: [B][W][W][F] memory, image stride activ_strides[l]; confs[l]: [B][W][W][A], image stride conf_strides[l];
+ * sels[l]: [B][keeps[l]] int32 as written by the select above (an index outside the level is clamped into it).
+ * Square maps of widths[l] <= cell_rows cells; the cell encoding is the reference's expression (infer.py:370-371). */
+int effdet_episode_feed(void* stream, int B, int num_levels, const void* const* activs, const long long* activ_strides,
+                        const void* const* confs, const long long* conf_strides, const void* const* sels, const int* keeps,
+                        const int* widths, const float* anch_enc, const float* lev_enc, int lev_rows, const float* cell_enc,
+                        int cell_rows, int first_level, int A, int F, int Kp, float* feed, float* conf_out);
+
+/* Clustering of the n = m * p projected rows embds [n][d] of m images (p consecutive rows each) without any n x n matrix:
+ * soft_thresh = sigmoid(dot_mult * (conf + dot_add)) (dots != NULL: a device pointer to {dot_mult, dot_add}, read instead
+ * of the two arguments); proto0 / avg_init0: first per-image prototypes and their init-cluster means - 1/m;
+ * valid = avg_init0 > mean(avg_init0) (use_thresh == 0) or > valid_threshold; proto / avg_init: second pick;
+ * target_clust [m]; sim / nearest [n]: max and argmax (use_max) or mean (nearest = -1) cosine similarity to the second
+ * prototypes; target = soft_thresh * target_clust[nearest] * sim (use_max) or soft_thresh * sim.  An empty valid set
+ * gives NaN target_clust, as the reference; n_valid[0] reports it.  m <= 64, d <= 512, m * d <= 16384, n % m == 0.
+ * The workspace size (floats) comes from the query below (-1: unsupported shape). */
+long long effdet_episode_cluster_workspace_floats(int n, int d, int m);
+int effdet_episode_cluster(void* stream, const float* embds, const float* confs, int n, int d, int m, float dot_mult,
+                           float dot_add, const float* dots, int use_thresh, float valid_threshold, int use_max,
+                           float* workspace, long long workspace_floats, float* soft_thresh, long long* proto0,
+                           float* avg_init0, unsigned char* valid, int* n_valid, long long* proto, float* avg_init,
+                           float* target_clust, float* sim, long long* nearest, float* target);
+
 #ifdef __cplusplus
 }
 #endif

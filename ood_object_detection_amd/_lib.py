@@ -165,6 +165,13 @@ SIGNATURES = {
     'effdet_train_bn_bwd_sums': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_ll]),
     'effdet_gather_ood': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p]),
+    'effdet_episode_select': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_int), P(c_int), P(c_void_p)]),
+    'effdet_episode_feed': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_void_p), P(c_ll), P(c_void_p), P(c_int), P(c_int),
+                                    c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'effdet_episode_cluster_workspace_floats': (c_ll, [c_int, c_int, c_int]),
+    'effdet_episode_cluster': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_float,
+                                       c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

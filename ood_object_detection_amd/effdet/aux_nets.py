@@ -168,7 +168,10 @@ class ProjectionNet(nn.Module):
             K, N = lin.in_features, lin.out_features
             Kp = (K + 7) // 8 * 8                      # the GEMM walks K in 16-byte pieces: zero-pad 106 -> 112
             a = cur
-            if Kp != K or not a.is_contiguous():
+            # episode.projection_feed hands over a [..., :K] view of a [..., Kp] buffer whose tail is zero: the GEMM reads it in place
+            pitched = (i == 0 and getattr(x, '_effdet_zero_tail', False) and cur.dim() == 2 and cur.stride() == (Kp, 1)
+                       and cur.data_ptr() % 16 == 0)
+            if not pitched and (Kp != K or not a.is_contiguous()):
                 a = torch.zeros(M, Kp, dtype=dtype, device=dev)
                 a[:, :K] = cur
             w = torch.zeros(N, Kp, dtype=dtype, device=dev)

@@ -1,0 +1,199 @@
+"""The few-shot episode stage between the MetaHead's outputs and `ood.novelty_score` (infer.py:362-447 projection phase,
+:566-654 meta phase) on the HIP kernels of csrc/episode.hip:
+
+    sel = select_anchors(confs)                                   # the anchors above the 0.875 confidence quantile, per level and image
+    feed, conf = projection_feed(activs, confs, sel, proj_net)    # [embedding | anchor enc | level enc | cell enc] rows
+    out = cluster(proj_net(feed).reshape(-1, d), conf.reshape(-1), B, dot_mult, dot_add)
+    t = target_from_selection(proj_embds, conf.reshape(-1), out, dot_mult, dot_add)     # the same target, with autograd history
+
+float32 GPU tensors only, no CPU fallback.  Nothing here synchronises with the host and no allocation depends on a device value,
+so the whole chain can be captured in one `torch.cuda.graph`.  The n x n matrices of the script (`sim_mat`, `thresh_mat`,
+`weighted_sim`) are never formed: every use of them is rank-1 or n x m (see csrc/episode.hip)."""
+import ctypes
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+QUANTILE_NUM, QUANTILE_DEN = 7, 8          # 0.875 (infer.py:385 / :588)
+
+
+def kept_per_level(h: int, w: int, num_anchors: int = 9) -> int:
+    """Anchors per image the episode code keeps on an h x w level: all of them when h <= 4 (infer.py:381-382), else what
+    `res_conf > torch.quantile(res_conf, 0.875)` keeps on tie-free data, N - 1 - floor(0.875 (N - 1))."""
+    n = int(num_anchors) * int(h) * int(w)
+    if h <= 4:
+        return n
+    return n - 1 - (QUANTILE_NUM * (n - 1)) // QUANTILE_DEN
+
+
+def _check(t, dim, what):
+    if not torch.is_tensor(t) or t.device.type != 'cuda' or t.dtype != torch.float32 or t.dim() != dim:
+        raise RuntimeError('%s: expected a float32 %d-d GPU tensor (no CPU fallback)' % (what, dim))
+
+
+def _nhwc(t):
+    """[B, C, H, W] -> (tensor that owns [B, H, W, C] memory, image stride); the MetaHead's permuted views are taken as they are"""
+    B, C, H, W = t.shape
+    v = t.detach().permute(0, 2, 3, 1)
+    if not (v.stride(3) == 1 and v.stride(2) == C and v.stride(1) == W * C and (B == 1 or v.stride(0) >= H * W * C)):
+        v = v.contiguous()
+    return v, (v.stride(0) if B > 1 else H * W * C)
+
+
+def _ptrs(vals):
+    return (ctypes.c_void_p * len(vals))(*vals)
+
+
+def _lls(vals):
+    return (ctypes.c_longlong * len(vals))(*vals)
+
+
+def _ints(vals):
+    return (ctypes.c_int * len(vals))(*vals)
+
+
+def select_anchors(confs):
+    """confs[l] [B, A, H, W] (the MetaHead's outputs, views of [B, H, W, A] memory are not copied) -> per level int32
+    [B, kept_per_level(H, W, A)]: the kept anchors' indices in (y, x, a) order, ascending - the order boolean-mask indexing with
+    the reference's `res_conf > quantile` mask gives, and on tie-free data the same set.  Equal confidences at the cut resolve to
+    the lower index (the project's top-k convention), so every image keeps exactly kept_per_level anchors.  The reference's tie
+    loop (infer.py:387-390) hard-codes 25 images and never terminates otherwise; it is not reproduced."""
+    if not confs or len(confs) > 8:
+        raise ValueError('between 1 and 8 levels')
+    lib = _lib.load()
+    keepalive, ptr, stride, count, keep, outs = [], [], [], [], [], []
+    B = confs[0].shape[0]
+    for c in confs:
+        _check(c, 4, 'select_anchors')
+        if c.shape[0] != B:
+            raise ValueError('levels disagree on the batch size')
+        v, s = _nhwc(c)
+        _, A, H, W = c.shape
+        keepalive.append(v)
+        ptr.append(v.data_ptr()); stride.append(s); count.append(A * H * W); keep.append(kept_per_level(H, W, A))
+        outs.append(torch.empty(B, keep[-1], dtype=torch.int32, device=c.device))
+    st = torch.cuda.current_stream(confs[0].device).cuda_stream
+    _lib.check(lib.effdet_episode_select(st, B, len(confs), _ptrs(ptr), _lls(stride), _ints(count), _ints(keep),
+                                         _ptrs([o.data_ptr() for o in outs])), 'effdet_episode_select')
+    return outs
+
+
+def projection_feed(activs, confs, sel, proj_net, first_level=0):
+    """-> (feed [B, R, F + 42], conf [B, R]), R = sum of the kept anchors over the levels, concatenated per image as infer.py:418 /
+    :606 do.  A feed row is [F embedding | anch_enc[a] (8) | lev_enc[first_level + l] (6) | cell enc (28)] (:366-378), copied
+    bit for bit; `first_level` is 0 in the projection phase and supp_level_offset in the meta phase.  activs[l] [B, F, H, W] and
+    confs[l] [B, A, H, W] are the MetaHead's outputs (ret_activs=True), sel the result of select_anchors; square maps of at most
+    80 cells a side.  Both results are copies without autograd history (FLAGS.proj_stop_grad).  `feed` is a view of a zero-padded [B, R, ceil8(F + 42)] buffer that ProjectionNet's inference path consumes
+    without its re-pack copy."""
+    nl = len(confs)
+    if nl == 0 or nl > 8 or len(activs) != nl or len(sel) != nl:
+        raise ValueError('activs, confs and sel must list the same 1 to 8 levels')
+    lib = _lib.load()
+    dev = confs[0].device
+    B, A = confs[0].shape[:2]
+    Fc = activs[0].shape[1]
+    anch, lev, cell = (t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in (proj_net.anch_enc, proj_net.lev_enc, proj_net.cell_enc))
+    if A > anch.shape[0] or anch.shape[1] != 8 or lev.shape[1] != 6 or cell.shape[1] != 14:
+        raise ValueError('unexpected encoding tables')
+    if first_level < 0 or first_level + nl > lev.shape[0]:
+        raise ValueError('level encodings exist for levels 0 .. %d' % (lev.shape[0] - 1))
+    keepalive, aptr, astr, cptr, cstr, sptr, keeps, widths = [], [], [], [], [], [], [], []
+    for a, c, s in zip(activs, confs, sel):
+        _check(a, 4, 'projection_feed'); _check(c, 4, 'projection_feed')
+        H, W = c.shape[2:]
+        if H != W or H > cell.shape[0] or a.shape != (B, Fc, H, W) or c.shape[:2] != (B, A):
+            raise ValueError('square maps of at most %d cells a side, one batch size and width for all levels' % cell.shape[0])
+        if s.device != dev or s.dtype != torch.int32 or s.dim() != 2 or s.shape[0] != B or s.shape[1] > A * H * W or s.shape[1] == 0:
+            raise ValueError('sel[l] must be the int32 [B, keep] GPU tensor select_anchors returns')
+        av, ast = _nhwc(a)
+        cv, cst = _nhwc(c)
+        sv = s.contiguous()
+        keepalive += [av, cv, sv]
+        aptr.append(av.data_ptr()); astr.append(ast); cptr.append(cv.data_ptr()); cstr.append(cst)
+        sptr.append(sv.data_ptr()); keeps.append(sv.shape[1]); widths.append(W)
+    R, K = sum(keeps), Fc + 42
+    Kp = (K + 7) // 8 * 8
+    feed = torch.empty(B, R, Kp, dtype=torch.float32, device=dev)
+    conf = torch.empty(B, R, dtype=torch.float32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.effdet_episode_feed(st, B, nl, _ptrs(aptr), _lls(astr), _ptrs(cptr), _lls(cstr), _ptrs(sptr), _ints(keeps),
+                                       _ints(widths), anch.data_ptr(), lev.data_ptr(), lev.shape[0], cell.data_ptr(), cell.shape[0],
+                                       int(first_level), A, Fc, Kp, feed.data_ptr(), conf.data_ptr()), 'effdet_episode_feed')
+    view = feed[..., :K]
+    view._effdet_zero_tail = True            # ProjectionNet.forward: the row pitch is ceil8(K) and the tail is zero
+    return view, conf
+
+
+def _dots(dot_mult, dot_add, dev):
+    """Python numbers travel by value; tensors (proj_net.dot_mult / dot_add) stay on the device, so nothing synchronises"""
+    if torch.is_tensor(dot_mult) or torch.is_tensor(dot_add):
+        pair = [torch.as_tensor(v).detach().to(device=dev, dtype=torch.float32).reshape(()) for v in (dot_mult, dot_add)]
+        return 0.0, 0.0, torch.stack(pair).contiguous()
+    return float(dot_mult), float(dot_add), None
+
+
+def cluster(proj_embds, confs, num_images, dot_mult, dot_add, valid_threshold=None, sim_target='max'):
+    """infer.py:423-447 (valid_threshold=None: `valid = avg_init > avg_init.mean()`, :438) / :605-654 (a float: `avg_init >
+    FLAGS.sim_thresh`, :631).  proj_embds [n, d] un-normalised ProjectionNet outputs, n = num_images * rows, confs [n] logits;
+    dot_mult / dot_add numbers or (GPU) tensors.  Returns dict(soft_thresh [n]; proto0 [m] int64 (first `max_idxs`), avg_init0 [m];
+    valid [m] bool, n_valid [1] int32; proto [m] int64 (second `max_idxs`), avg_init [m], target_clust [m]; sim [n]
+    (`all_max_sims_clust`, or the mean for 'avg'); nearest [n] int64 (`all_max_idxs`; -1 for 'avg'); target [n] (:648 / :652)).
+    An empty valid set gives NaN target_clust / target as in the reference; n_valid says so.  argmax ties go to the lower index.
+    num_images <= 64, d <= 512, num_images * d <= 16384."""
+    _check(proj_embds, 2, 'cluster')
+    if sim_target not in ('avg', 'max'):
+        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    lib = _lib.load()
+    e = proj_embds.detach().contiguous()
+    n, d = e.shape
+    m = int(num_images)
+    dev = e.device
+    if not torch.is_tensor(confs) or confs.device != dev or confs.dtype != torch.float32 or confs.numel() != n:
+        raise RuntimeError('cluster: confs must be a float32 GPU tensor of n elements (no CPU fallback)')
+    c = confs.detach().reshape(n).contiguous()
+    ws_floats = lib.effdet_episode_cluster_workspace_floats(n, d, m) if m > 0 and n > 0 else -1
+    if ws_floats < 0:
+        raise ValueError('need n %% num_images == 0, num_images <= 64, d <= 512 and num_images * d <= 16384')
+    dm, da, dots = _dots(dot_mult, dot_add, dev)
+    ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
+    fn = torch.empty(4, n, dtype=torch.float32, device=dev)              # soft_thresh, sim, target, (spare)
+    fm = torch.empty(3, m, dtype=torch.float32, device=dev)              # avg_init0, avg_init, target_clust
+    im = torch.empty(2, m, dtype=torch.int64, device=dev)
+    nearest = torch.empty(n, dtype=torch.int64, device=dev)
+    valid = torch.empty(m, dtype=torch.bool, device=dev)
+    n_valid = torch.empty(1, dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.effdet_episode_cluster(st, e.data_ptr(), c.data_ptr(), n, d, m, dm, da, dots.data_ptr() if dots is not None else None,
+                                          0 if valid_threshold is None else 1, 0.0 if valid_threshold is None else float(valid_threshold),
+                                          1 if sim_target == 'max' else 0, ws.data_ptr(), ws_floats, fn[0].data_ptr(), im[0].data_ptr(),
+                                          fm[0].data_ptr(), valid.data_ptr(), n_valid.data_ptr(), im[1].data_ptr(), fm[1].data_ptr(),
+                                          fm[2].data_ptr(), fn[1].data_ptr(), nearest.data_ptr(), fn[2].data_ptr()),
+               'effdet_episode_cluster')
+    return {'soft_thresh': fn[0], 'proto0': im[0], 'avg_init0': fm[0], 'valid': valid, 'n_valid': n_valid, 'proto': im[1],
+            'avg_init': fm[1], 'target_clust': fm[2], 'sim': fn[1], 'nearest': nearest, 'target': fn[2]}
+
+
+def target_from_selection(proj_embds, confs, out, dot_mult, dot_add, sim_target='max'):
+    """The differentiable remainder: `target_clust`, `sim` and `target` re-derived from the indices `cluster` returned, as plain
+    torch row gathers and row dot products on [n, d] (no n x n), so training code gets them with autograd history, also under
+    create_graph=True.  The discrete decisions (prototypes, valid set, nearest prototype) are constants here, as they are
+    non-differentiable in the reference.  Returns dict(soft_thresh, target_clust [m], sim [n], target [n])."""
+    _check(proj_embds, 2, 'target_from_selection')
+    if sim_target not in ('avg', 'max'):
+        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    e = F.normalize(proj_embds, p=2)
+    soft_thresh = (dot_mult * (confs.reshape(-1) + dot_add)).sigmoid()
+    valid = out['valid'].to(e.dtype)
+    cmean = (e[out['proto0']] * valid[:, None]).sum(0) / valid.sum()      # mean of the valid first prototypes (NaN when none is)
+    protos = e[out['proto']]
+    target_clust = protos @ cmean
+    if sim_target == 'max':
+        nearest = out['nearest']
+        sim = (e * protos[nearest]).sum(1)
+        target = soft_thresh * target_clust[nearest] * sim
+    else:
+        sim = e @ protos.mean(0)
+        target = soft_thresh * sim
+    return {'soft_thresh': soft_thresh, 'target_clust': target_clust, 'sim': sim, 'target': target}

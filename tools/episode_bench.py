@@ -1,0 +1,110 @@
+#!/usr/bin/env python
+"""Time of the episode stage (anchor selection + ProjectionNet feed + clustering, ood_object_detection_amd/episode.py) against the
+literal torch composition of infer.py:362-447 / :566-654 (tests/_episode_ref.py, torch's own kernels on the same GPU).  The
+ProjectionNet itself is common to both and left out: both sides cluster the same embeddings.
+
+    python3 tools/episode_bench.py                    meta-phase default (25 images, P5-P7 of 256 px: 756 anchors -> 252 rows, F 160, d 256)
+    python3 tools/episode_bench.py --phase proj       projection-phase default (P3-P7: 12 276 anchors -> 1 692 rows per image, 42 300 rows)
+
+The two paths alternate, `--rounds` windows of `--iters` iterations each (HIP events around a window, host launch overhead
+included); the report is the median window and the min .. max spread per path.  Needs the GPU: there is no fallback."""
+import argparse
+import os
+import statistics
+import sys
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+import torch  # noqa: E402
+
+import _episode_ref as ref  # noqa: E402
+from ood_object_detection_amd import episode  # noqa: E402
+from ood_object_detection_amd.effdet.aux_nets import ProjectionNet  # noqa: E402
+
+A = 9
+
+
+def window(fn, iters):
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(iters):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--phase', choices=['meta', 'proj'], default='meta')
+    ap.add_argument('--images', type=int, default=25)
+    ap.add_argument('--fpn', type=int, default=160)
+    ap.add_argument('--width', type=int, default=512)
+    ap.add_argument('--iters', type=int, default=100)
+    ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--no-literal', action='store_true', help='time the new path alone')
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'episode_bench needs the GPU'
+    dev = 'cuda:0'
+    sides, first = ([8, 4, 2], 2) if a.phase == 'meta' else ([32, 16, 8, 4, 2], 0)
+    B, Fc, d = a.images, a.fpn, a.width // 2
+    torch.manual_seed(0)
+    net = ProjectionNet(types.SimpleNamespace(fpn_channels=Fc), a.width).to(dev)
+    gen = torch.Generator().manual_seed(1)
+    activs = [torch.randn(B, s, s, Fc, generator=gen).to(dev).permute(0, 3, 1, 2) for s in sides]
+    confs = [(ref.tie_free_confs(s, B, A * s * s) - 1.0).to(dev).view(B, s, s, A).permute(0, 3, 1, 2) for s in sides]
+    rows = sum(episode.kept_per_level(s, s) for s in sides)
+    n = B * rows
+    x, _ = ref.clustered_rows(2, B, rows, d)
+    embds = x.to(dev)
+    thr = 0.3 if a.phase == 'meta' else None
+
+    def new_path():
+        sel = episode.select_anchors(confs)
+        feed, conf = episode.projection_feed(activs, confs, sel, net, first_level=first)
+        return feed, episode.cluster(embds, conf.reshape(-1), B, 3., 3., valid_threshold=thr)
+
+    def literal_path():
+        feed, conf, _ = ref.episode_feed(activs, confs, net.anch_enc, net.lev_enc, net.cell_enc, first)
+        return feed, ref.cluster_literal(embds, conf.reshape(-1), 3., 3., B, thr, 'max')
+
+    print('%s phase: %d images x %d anchors -> %d rows each, n = %d, F %d, d %d; one n x n float32 matrix is %.1f MB'
+          % (a.phase, B, sum(A * s * s for s in sides), rows, n, Fc, d, n * n * 4 / 1e6))
+    free = torch.cuda.mem_get_info()[0]
+    literal = not a.no_literal
+    if literal and 8 * n * n * 4 > free:
+        print('literal form: not run (its n x n temporaries do not fit the %.0f GB free)' % (free / 1e9))
+        literal = False
+    with torch.no_grad():
+        f_new, o_new = new_path()
+        if literal:
+            f_lit, o_lit = literal_path()
+            torch.cuda.synchronize()
+            agree = o_new['nearest'] == o_lit['nearest']             # near-tied prototypes may be named differently in float32
+            print('same outputs: feed bit-equal %s, prototypes equal %s, nearest prototype differs on %d of %d rows, target max diff '
+                  'on the others %.2e'
+                  % (torch.equal(f_new, f_lit), torch.equal(o_new['proto'], o_lit['proto']), int((~agree).sum()), n,
+                     float(((o_new['target'] - o_lit['target']) * agree).abs().max())))
+            del f_lit, o_lit
+        for _ in range(3):
+            window(new_path, 5)
+            if literal:
+                window(literal_path, 5)
+        t_new, t_lit = [], []
+        for _ in range(a.rounds):
+            t_new.append(window(new_path, a.iters))
+            if literal:
+                t_lit.append(window(literal_path, a.iters))
+    print('new path  (select + feed + cluster, 9 HIP launches): median %.1f us, spread %.1f .. %.1f us  (%d windows of %d)'
+          % (statistics.median(t_new), min(t_new), max(t_new), a.rounds, a.iters))
+    if literal:
+        print('literal torch composition:                           median %.1f us, spread %.1f .. %.1f us'
+              % (statistics.median(t_lit), min(t_lit), max(t_lit)))
+        print('ratio literal / new: %.2f' % (statistics.median(t_lit) / statistics.median(t_new)))
+
+
+if __name__ == '__main__':
+    main()
