@@ -285,6 +285,15 @@ int effdet_label_anchors(void* stream, const float* anchors, const float* gt_box
                          int B, int Mmax, long long N, float match_threshold, long long* cls_t, float* box_t,
                          float* num_positives, long long* match, void* workspace, long long workspace_bytes);
 
+/* The same assignment for the reference's filter_valid=False (effdet/data/loader.py:84): every row takes part whatever
+ * its class, so a row of class c <= -1 is matched like any other (a zero box is forced onto anchor 0) and gives class
+ * target c - 1, i.e. -2 for the usual -1, which effdet_detection_loss ignores.  Only rows of class EFFDET_LABEL_PAD are
+ * the caller's own padding and invisible; `match` indexes the rows that are not.  Same workspace as above. */
+#define EFFDET_LABEL_PAD (-0x7fffffffffffffffLL - 1)
+int effdet_label_anchors_rows(void* stream, const float* anchors, const float* gt_boxes, const long long* gt_cls,
+                              int B, int Mmax, long long N, float match_threshold, long long* cls_t, float* box_t,
+                              float* num_positives, long long* match, void* workspace, long long workspace_bytes);
+
 /* The `task_cls` branch of AnchorLabeler.batch_label_anchors (effdet/anchors.py:396-403), run before effdet_label_anchors
  * on the same padded tensors: per image, every row whose IoU (same arithmetic as above; boxlist1 = the rows of class
  * task_cls) with some row of class task_cls is > iou_threshold (the reference: 0.9) gets class task_cls, in place.

@@ -12,6 +12,8 @@ CSRC = os.path.join(_HERE, 'csrc')
 
 _lib = None
 
+LABEL_PAD = -2 ** 63        # EFFDET_LABEL_PAD: the class of a padding row for effdet_label_anchors_rows
+
 c_void_p, c_int, c_ll, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double
 P = ctypes.POINTER
 
@@ -91,6 +93,8 @@ SIGNATURES = {
     'effdet_label_anchors_workspace_bytes': (c_ll, [c_int, c_int, c_ll]),
     'effdet_label_anchors': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_float, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_label_anchors_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_float, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_ll]),
     'effdet_relabel_task_cls': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_float]),
     'effdet_train_gemm_nt': (c_int, [c_void_p, c_void_p, c_ll, c_ll, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_ll,
                                      c_ll, c_int, c_int, c_int, c_void_p]),

@@ -143,6 +143,7 @@ struct LabelArgs {
     const float* anchors; const float* gt_boxes; const long long* gt_cls;
     int B, Mmax; long long N; float thr;
     long long* cls_t; float* box_t; float* num_pos; long long* match_out;
+    long long pad_max;                 // rows of class <= pad_max are padding: -1, or EFFDET_LABEL_PAD for the `_rows` entry
     int* match0;                       // [B][N]
     int* force_row;                    // [B][N] (0x7F7F7F7F = not forced)
     unsigned long long* best;          // [B][Mmax][nblk] per-block best (iou, lowest anchor) of every gt row
@@ -164,7 +165,7 @@ DEV int load_gt(const LabelArgs& p, int b, float (*gb)[4], float* garea, long lo
         int m = 0;
         for (int i = 0; i < p.Mmax && m < MAXGT; ++i) {
             const long long c = p.gt_cls[(long long)b * p.Mmax + i];
-            if (c > -1) {
+            if (c > p.pad_max) {
                 const float* g = p.gt_boxes + ((long long)b * p.Mmax + i) * 4;
                 gb[m][0] = g[0]; gb[m][1] = g[1]; gb[m][2] = g[2]; gb[m][3] = g[3];
                 garea[m] = (g[2] - g[0]) * (g[3] - g[1]);
@@ -332,17 +333,17 @@ extern "C" long long effdet_label_anchors_workspace_bytes(int B, int Mmax, long 
     return (long long)B * N * 8 + (long long)B * (Mmax > 0 ? Mmax : 1) * nblk * 8;
 }
 
-extern "C" int effdet_label_anchors(void* stream, const float* anchors, const float* gt_boxes, const long long* gt_cls,
-                                    int B, int Mmax, long long N, float match_threshold,
-                                    long long* cls_t, float* box_t, float* num_positives, long long* match,
-                                    void* workspace, long long workspace_bytes) {
-    EFFDET_ENTER();
+namespace {
+
+int label_anchors(void* stream, const float* anchors, const float* gt_boxes, const long long* gt_cls, int B, int Mmax, long long N,
+                  float match_threshold, long long pad_max, long long* cls_t, float* box_t, float* num_positives, long long* match,
+                  void* workspace, long long workspace_bytes) {
     if (!anchors || !cls_t || !box_t || !num_positives || !workspace || B <= 0 || Mmax < 0 || Mmax > MAXGT || N <= 0) return EFFDET_EINVAL;
     if (Mmax > 0 && (!gt_boxes || !gt_cls)) return EFFDET_EINVAL;
     if (workspace_bytes < effdet_label_anchors_workspace_bytes(B, Mmax, N)) return EFFDET_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     LabelArgs a{anchors, gt_boxes, gt_cls, B, Mmax, N, match_threshold, cls_t, box_t, num_positives, match,
-                nullptr, nullptr, nullptr, (int)((N + LT - 1) / LT)};
+                pad_max, nullptr, nullptr, nullptr, (int)((N + LT - 1) / LT)};
     char* ws = reinterpret_cast<char*>(workspace);
     a.match0 = reinterpret_cast<int*>(ws);
     a.force_row = reinterpret_cast<int*>(ws + (size_t)B * N * 4);
@@ -353,6 +354,28 @@ extern "C" int effdet_label_anchors(void* stream, const float* anchors, const fl
     if (Mmax > 0) hipLaunchKernelGGL(label_force_kernel, dim3(B), dim3(LT), 0, st, a);
     hipLaunchKernelGGL(label_targets_kernel, dim3(a.nblk, B), dim3(LT), 0, st, a);
     return effdet_check_launch();
+}
+
+}  // namespace
+
+extern "C" int effdet_label_anchors(void* stream, const float* anchors, const float* gt_boxes, const long long* gt_cls,
+                                    int B, int Mmax, long long N, float match_threshold,
+                                    long long* cls_t, float* box_t, float* num_positives, long long* match,
+                                    void* workspace, long long workspace_bytes) {
+    EFFDET_ENTER();
+    return label_anchors(stream, anchors, gt_boxes, gt_cls, B, Mmax, N, match_threshold, -1, cls_t, box_t, num_positives, match,
+                         workspace, workspace_bytes);
+}
+
+// filter_valid=False of the reference (effdet/data/loader.py:84): every row takes part, whatever its class - a row of class
+// -1 gives class target -2, which the loss ignores.  Only rows of class EFFDET_LABEL_PAD are the caller's padding.
+extern "C" int effdet_label_anchors_rows(void* stream, const float* anchors, const float* gt_boxes, const long long* gt_cls,
+                                         int B, int Mmax, long long N, float match_threshold,
+                                         long long* cls_t, float* box_t, float* num_positives, long long* match,
+                                         void* workspace, long long workspace_bytes) {
+    EFFDET_ENTER();
+    return label_anchors(stream, anchors, gt_boxes, gt_cls, B, Mmax, N, match_threshold, EFFDET_LABEL_PAD, cls_t, box_t,
+                         num_positives, match, workspace, workspace_bytes);
 }
 
 // ------------------------------------------------------------------------------------------------

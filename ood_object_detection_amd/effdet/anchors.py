@@ -194,7 +194,11 @@ class AnchorLabeler(object):
         whose IoU with some box of class `task_cls` is > 0.9 becomes class `task_cls` before the assignment - decided on
         the device by `effdet_relabel_task_cls`, one launch for the batch.  Like the reference, the new classes are written
         into the caller's `gt_classes[i]` tensors.  An image without a box of class `task_cls` is left alone (the reference
-        raises there, on the `max` of an empty tensor; dataloader.py never produces one)."""
+        raises there, on the `max` of an empty tensor; dataloader.py never produces one).
+
+        filter_valid=False (effdet/data/loader.py:84) keeps every row the caller passes, like the reference: a row of class
+        -1 is matched like any other (its zero box is forced onto anchor 0) and gives class target -2, which the loss
+        ignores.  Only this method's own padding up to the longest image stays invisible (`effdet_label_anchors_rows`)."""
         lib = _lib.load()
         boxes = self.anchors.boxes
         if boxes.device.type != 'cuda':
@@ -205,7 +209,7 @@ class AnchorLabeler(object):
         lens = [int(b.shape[0]) for b in gt_boxes]
         Mmax = max(lens + [1])
         gb = torch.zeros(B, Mmax, 4, dtype=torch.float32, device=dev)
-        gc = torch.full((B, Mmax), -1, dtype=torch.int64, device=dev)
+        gc = torch.full((B, Mmax), -1 if filter_valid else _lib.LABEL_PAD, dtype=torch.int64, device=dev)
         if sum(lens):
             # one scatter for the whole batch (the lengths are host values): rows i * Mmax + j <- the j-th box of image i
             rows = torch.tensor([i * Mmax + j for i, m in enumerate(lens) for j in range(m)], dtype=torch.int64).to(dev)
@@ -213,7 +217,7 @@ class AnchorLabeler(object):
             allc = torch.cat([c.to(device=dev, dtype=torch.int64).reshape(-1) for c, m in zip(gt_classes, lens) if m], 0)
             gb.view(-1, 4)[rows] = allb
             if task_cls is None:
-                gc.view(-1)[rows] = allc if filter_valid else allc.clamp(min=0)
+                gc.view(-1)[rows] = allc
             else:
                 gc.view(-1)[rows] = allc                     # the relabelling sees the classes as given
                 _lib.check(lib.effdet_relabel_task_cls(_stream(boxes), gb.data_ptr(), gc.data_ptr(), B, Mmax, int(task_cls), 0.9),
@@ -221,8 +225,6 @@ class AnchorLabeler(object):
                 newc = gc.view(-1)[rows]
                 for c, part in zip([c for c, m in zip(gt_classes, lens) if m], newc.split([m for m in lens if m])):
                     c.copy_(part.reshape(c.shape))           # anchors.py:403 writes into the caller's tensor
-                if not filter_valid:
-                    gc.view(-1)[rows] = newc.clamp(min=0)
         N = boxes.shape[0]
         cls_t = torch.empty(B, N, dtype=torch.int64, device=dev)
         box_t = torch.empty(B, N, 4, dtype=torch.float32, device=dev)
@@ -230,9 +232,10 @@ class AnchorLabeler(object):
         nbytes = lib.effdet_label_anchors_workspace_bytes(B, Mmax, N)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         anchors_f = boxes.float().contiguous()
-        _lib.check(lib.effdet_label_anchors(_stream(boxes), anchors_f.data_ptr(), gb.data_ptr(), gc.data_ptr(), B, Mmax, N,
-                                            float(self.match_threshold), cls_t.data_ptr(), box_t.data_ptr(), npos.data_ptr(),
-                                            None, ws.data_ptr(), nbytes), 'effdet_label_anchors')
+        entry = lib.effdet_label_anchors if filter_valid else lib.effdet_label_anchors_rows
+        _lib.check(entry(_stream(boxes), anchors_f.data_ptr(), gb.data_ptr(), gc.data_ptr(), B, Mmax, N,
+                         float(self.match_threshold), cls_t.data_ptr(), box_t.data_ptr(), npos.data_ptr(),
+                         None, ws.data_ptr(), nbytes), 'effdet_label_anchors')
         cls_out, box_out = self._unpack(cls_t, box_t)
         return cls_out, box_out, npos
 

@@ -18,6 +18,11 @@ Follows, by reference file:line
   effdet/evaluation/metrics.py:92-106                compute_cor_loc
   effdet/evaluation/object_detection_evaluation.py:205-273  per-class AP for classes with ground truth, nanmean -> mAP, mean CorLoc
 
+Equal scores (the reference leaves their order to numpy's unstable sort; the device documents a rule): detections are taken
+in a stable descending order, i.e. of two detections with the same score the one given first comes first - inside an image
+for the greedy matching, and in the order (image, position) for the precision / recall curve.  With distinct scores this is
+the reference's order.
+
 Pinned: tests/golden/evaluation.npz was produced by the reference's own ObjectDetectionEvaluator (tools/make_golden.py).
 """
 import numpy as np
@@ -56,7 +61,7 @@ def per_image(det_boxes, det_scores, det_classes, gt_boxes, gt_classes, num_clas
             scores_c.append(np.array([], dtype=float))
             tp_c.append(np.array([], dtype=bool))
             continue
-        order = np.argsort(s)[::-1]
+        order = np.argsort(-s, kind='stable')
         d, s = d[order], s[order]
         tp = np.zeros(len(s), dtype=bool)
         if g.size > 0:
@@ -79,7 +84,7 @@ def average_precision(scores, tp, num_gt):
     scores, tp = np.asarray(scores, dtype=float), np.asarray(tp, dtype=float)
     if scores.size == 0:
         return 0.0
-    order = np.argsort(scores)[::-1]
+    order = np.argsort(-scores, kind='stable')
     t = tp[order]
     ctp = np.cumsum(t)
     cfp = np.cumsum((t <= 0).astype(float))

@@ -116,3 +116,72 @@ def meta_lists(init, extra, L, R):
     bw = [init['class_net.bn_rep.%d.%d.bn.weight' % (r, lev)] for lev in range(L) for r in range(R)]
     bb = [init['class_net.bn_rep.%d.%d.bn.bias' % (r, lev)] for lev in range(L) for r in range(R)]
     return dw, pw, pb, pred, bw, bb
+
+
+def eval_case_dense(seed, n_img, C, M, n_det, cls=1):
+    """seeded evaluation inputs that fill the matching kernel: every image has exactly M ground-truth boxes, all of class `cls`
+    (so every lane, every wave and, for M > 256, the second loop trip hold candidates), 10 x 10 integer boxes on a 30-pixel grid
+    with about one in six a duplicate of the box before it.  Detections, scores distinct and descending: exact copies of
+    ground truth, boxes built at IoU exactly 0.5 with one ground-truth box ([y, x, y + 10, x + 20] against [y, x, y + 10,
+    x + 10]: 100 / 200), random boxes, invalid boxes, and classes outside 1..C (0, C + 1, negative).  Same dict layout as
+    eval_case (1-based classes)."""
+    rs = np.random.RandomState(seed)
+    images = []
+    for _ in range(n_img):
+        gt = np.zeros((M, 4), np.float32)
+        for k in range(M):
+            if k > 0 and rs.uniform() < 1.0 / 6:
+                gt[k] = gt[k - 1]
+            else:
+                y, x = 30.0 * (k // 20), 30.0 * (k % 20)
+                gt[k] = (y, x, y + 10, x + 10)
+        gc = np.full(M, cls, np.int64)
+        det, dc = [], []
+        for _k in range(n_det):
+            r = rs.uniform()
+            j = rs.randint(0, M)
+            c = cls
+            if r < 0.35:
+                box = gt[j].copy()
+            elif r < 0.6:
+                box = gt[j] + np.array([0, 0, 0, 10], np.float32)
+            elif r < 0.7:
+                box = gt[j] + np.array([0, 0, 0, 11], np.float32)                       # IoU 100 / 210: below the threshold
+            elif r < 0.85:
+                yy, xx = rs.uniform(0, 400), rs.uniform(0, 560)
+                box = np.array([yy, xx, yy + rs.uniform(5, 40), xx + rs.uniform(5, 40)], np.float32)
+            elif r < 0.9:
+                box = gt[j][[2, 1, 0, 3]].copy()                                         # invalid: ymax < ymin
+            else:
+                box = gt[j].copy()
+                c = [0, C + 1, -3, cls % C + 1][rs.randint(0, 4)]                        # dropped, or a class without ground truth
+            det.append(box)
+            dc.append(c)
+        sc = np.sort(rs.permutation(100000)[:n_det].astype(np.float32) / 100000.0)[::-1].copy()
+        images.append(dict(gt_boxes=gt, gt_classes=gc, det_boxes=np.stack(det).astype(np.float32).reshape(-1, 4),
+                           det_scores=sc, det_classes=np.asarray(dc, np.int64)))
+    return images
+
+
+def label_case(seed, B, Mmax, size, num_classes=90):
+    """seeded labeler inputs in the padded C-ABI layout: gt_boxes [B, Mmax, 4] float32 yxyx, gt_cls [B, Mmax] int64.  Box
+    counts per image are mixed from 0 to Mmax (image 0 is full, image 1 empty when there is one); the valid rows sit at random
+    positions with padding rows (class -1, zero box) between them; about one valid row in twelve keeps its box and gets
+    class -1; boxes are 2 px to size / 2 wide and high, some are copies of the row before them (tied IoU everywhere)."""
+    rs = np.random.RandomState(seed)
+    gb = np.zeros((B, Mmax, 4), np.float32)
+    gc = np.full((B, Mmax), -1, np.int64)
+    for b in range(B):
+        n = Mmax if b == 0 else (0 if b == 1 else rs.randint(0, Mmax + 1))
+        pos = np.sort(rs.permutation(Mmax)[:n])
+        prev = None
+        for p in pos:
+            if prev is not None and rs.uniform() < 0.05:
+                box = prev
+            else:
+                h, w = rs.uniform(2, size / 2, 2) if rs.uniform() < 0.7 else rs.uniform(2, 12, 2)
+                y0, x0 = rs.uniform(0, size - h), rs.uniform(0, size - w)
+                box = np.array([y0, x0, y0 + h, x0 + w], np.float32)
+            gb[b, p] = prev = box
+            gc[b, p] = -1 if (Mmax > 2 and rs.uniform() < 1.0 / 12) else rs.randint(1, num_classes + 1)
+    return gb, gc

@@ -17,6 +17,9 @@ Fixtures written
     loss.npz                  loss.loss_fn values and autograd gradients
     evaluation.npz            ObjectDetectionEvaluator mAP / CorLoc on seeded detections
     labeler.npz               anchors.AnchorLabeler.batch_label_anchors
+    labeler_edges.npz         TargetAssigner.assign on edge cases (ties, shared best anchor, IoU 0 / 1, zero area, rows of
+                              class -1 with and without filter_valid, 40 boxes); compact: int16 matches, box targets at
+                              the matched anchors only
     labeler_task_cls.npz      the same with task_cls (anchors.py:396-403): relabelled classes and targets
     config.npz                model_config.get_efficientdet_config + fpn_config.bifpn_config dumps
     bifpn_head.npz            EfficientDet(config) forward (reference BiFpn/HeadNet code on stub
@@ -215,6 +218,81 @@ def gen_labeler():
         out['gt_boxes%d' % i], out['gt_cls%d' % i] = gt_boxes[i], gt_cls[i]
     out['npos'] = torch.stack(npos)
     save('labeler', **out)
+
+
+def save_reproducible(name, **arrays):
+    """like save(), with fixed zip timestamps: running the generator again gives the same bytes"""
+    import io
+    import zipfile
+    path = os.path.join(OUT, name + '.npz')
+    with zipfile.ZipFile(path, 'w') as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asarray(v.detach().numpy() if torch.is_tensor(v) else v, order='C'),
+                                      allow_pickle=False)
+            info = zipfile.ZipInfo(k + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+    print('%-28s %8.1f KB' % (name + '.npz', os.path.getsize(path) / 1024.))
+
+
+def gen_labeler_edges():
+    """TargetAssigner.assign (what batch_label_anchors calls per image, see gen_labeler) on inputs chosen for the decisions
+    random boxes never reach.  Every image is assigned twice: `fv1` on the rows of class > -1 (filter_valid=True) and `fv0`
+    on all rows (filter_valid=False, effdet/data/loader.py:84)."""
+    from effdet.anchors import Anchors, AnchorLabeler
+    from effdet.object_detection import BoxList
+    anchors = Anchors(3, 7, 3, [(1.0, 1.0), (1.4, 0.7), (0.7, 1.4)], 4.0, (128, 128))
+    lab = AnchorLabeler(anchors, num_classes=6, match_threshold=0.5)
+    A = anchors.boxes
+    sim = lambda b: lab.target_assigner._similarity_calc.compare(BoxList(b), BoxList(A))
+    f = lambda rows: torch.tensor(rows, dtype=torch.float32).reshape(-1, 4)
+    l = lambda vals: torch.tensor(vals, dtype=torch.int64)
+    # an anchor with integer corners inside the image: level 3, octave 0, aspect (1, 1) -> 32 x 32 around (36, 36)
+    k_int = int(((A == torch.tensor([20., 20., 52., 52.])).all(1)).nonzero()[0])
+    rs = np.random.RandomState(12)
+    n = 40
+    y0, x0 = rs.uniform(0, 100, n), rs.uniform(0, 100, n)
+    h, w = rs.uniform(6, 60, n), rs.uniform(6, 60, n)
+    h[::4], w[::4] = rs.uniform(2, 4, 10), rs.uniform(2, 4, 10)                  # tiny boxes
+    many = f(np.stack([y0, x0, np.minimum(y0 + h, 128), np.minimum(x0 + w, 128)], 1).astype(np.float32))
+    images = [
+        ('a', f([[30, 30, 70, 80], [30, 30, 70, 80], [90, 10, 120, 50]]), l([2, 5, 1])),      # identical boxes, two labels
+        ('b', f([[20, 20, 52, 52], [21, 21, 51, 51]]), l([1, 4])),                            # one best anchor for two rows
+        ('c', f([[10, 12, 60, 70], [2000, 2000, 2040, 2040]]), l([3, 6])),                    # IoU 0 with every anchor
+        ('d', f([[40, 40, 40, 40], [64, 16, 100, 16], [50, 50, 90, 100]]), l([2, 3, 4])),     # zero-area boxes
+        ('e', torch.cat([A[k_int:k_int + 1], f([[70, 60, 110, 120]])]), l([6, 2])),           # a box equal to an anchor
+        ('f', f([[10, 12, 60, 70], [0, 0, 0, 0], [0, 0, 0, 0]]), l([3, -1, -1])),             # the loader's padding rows
+        ('g', f([[8, 8, 58, 58], [60, 56, 112, 120], [0, 0, 0, 0], [20, 70, 50, 110]]), l([1, -1, -1, 5])),   # class -1, real box
+        ('h', many, l(rs.randint(1, 7, n))),
+        ('i', f([]), l([])),
+    ]
+    s = sim(images[0][1])
+    assert torch.equal(s[0], s[1])
+    s = sim(images[1][1])
+    assert int(s[0].argmax()) == int(s[1].argmax()) == k_int and float(s[1].max()) < 1.0
+    assert float(sim(images[2][1])[1].max()) == 0.0
+    assert float(sim(images[3][1])[:2].max()) == 0.0
+    assert float(sim(images[4][1])[0, k_int]) == 1.0
+    out = {'tags': np.array([t for t, _, _ in images])}
+    for tag, boxes, classes in images:
+        out['gt_boxes_' + tag], out['gt_cls_' + tag] = boxes, classes
+        for fv in (1, 0):
+            keep = classes > -1 if fv else torch.ones_like(classes, dtype=torch.bool)
+            c, b, m = lab.target_assigner.assign(BoxList(A), BoxList(boxes[keep]), classes[keep])
+            mr = m.match_results
+            key = '%s_fv%d' % (tag, fv)
+            out['match_' + key] = mr.to(torch.int16)
+            out['cls_' + key] = (c - 1).long().to(torch.int16)
+            assert bool((b[mr < 0] == 0).all())
+            out['box_' + key] = b[mr > -1].contiguous()
+            out['npos_' + key] = (mr > -1).float().sum()
+    # what the issue's CPU run of the reference saw for (f): anchor 0 forced by row 1, class target -2
+    assert int(out['match_f_fv0'][0]) == 1 and int(out['cls_f_fv0'][0]) == -2 and int(out['cls_f_fv1'][0]) == -1
+    assert int(out['npos_f_fv0']) == int(out['npos_f_fv1']) + 1
+    assert not bool((out['match_a_fv1'] == 1).any())                             # the second identical row owns nothing
+    save_reproducible('labeler_edges', **out)
 
 
 def gen_labeler_task_cls():
@@ -527,6 +605,6 @@ def gen_evaluation():
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ['anchors', 'post_process', 'decode', 'soft_nms', 'generate_detections', 'loss',
-                             'labeler', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'meta_nets', 'aux_losses']
+                             'labeler', 'labeler_edges', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'meta_nets', 'aux_losses']
     for w in which:
         globals()['gen_' + w]()
