@@ -93,6 +93,46 @@ int effdet_resize_pad_u8(void* stream, const unsigned char* src, int h, int w, u
                          const int* fill_rgb, unsigned char* workspace);
 int effdet_normalize_u8(void* stream, int out_dtype, const unsigned char* X, const float* mean, const float* stdv,
                         void* Y, int B, int C, long long hw);
+
+/* The image transforms of effdet/data/transforms.py for a whole ragged batch in one launch: ResizePad (:75-107),
+ * RandomFlip + RandomResizePad (:170-276) and ProjResizePad's pixel path (:143-148).  Per image, in this order: mirror the stored
+ * frame (flip_h / flip_v), take the crop rectangle (cx0, cy0, cw, ch) of the mirrored frame, resample it to sw x sh with
+ * Pillow's 8-bit filter (0 = BILINEAR, 1 = BICUBIC; bounds clamp to the crop, as img.crop(..).resize(..) does), take the
+ * window that starts at (ox, oy) of the resampled image and paste its min(S, sw - ox) x min(S, sh - oy) pixels top-left on
+ * an S x S canvas of the fill colour.  src: uint8 HWC [h][w][3], pitch 3 * w, ANY byte alignment (the aligned 32-bit words
+ * that cover a row are loaded).  Output: planar uint8 [B][3][S][S], image pitch dst_image_stride bytes (<= 0: 3 * S * S).
+ * The coefficient tables are computed on the device in fp64 exactly as Pillow's precompute_coeffs / normalize_coeffs_8bpc
+ * do; results are bit-identical to PIL and do not depend on the batch an image travels in.  No workspace.
+ * desc: device array of B descriptors; desc_host: the same B descriptors in host memory (read during the call only: argument
+ * checks and the LDS size of the launch).  fill_rgb: host array of 3 ints.  Limits: cw <= 64 * sw and ch <= 64 * sh (a 64 : 1
+ * reduction per axis), sizes up to 2^20, B <= 65535, S <= 16384; beyond them -22. */
+typedef struct EffdetResampleDesc {
+    const unsigned char* src;
+    int h, w;
+    int flip_h, flip_v;
+    int cx0, cy0, cw, ch;
+    int filter;
+    int sw, sh;
+    int ox, oy;
+    int reserved;
+} EffdetResampleDesc;                /* 64 bytes */
+int effdet_resample_batch_u8(void* stream, const EffdetResampleDesc* desc, const EffdetResampleDesc* desc_host, int B,
+                             unsigned char* dst, long long dst_image_stride, int S, const int* fill_rgb);
+
+/* The box arithmetic of the same transforms (transforms.py:96-103, 150-158, 216-227, 250-260) in float32, one rounding per
+ * reference operation: flip (x' = img_w - x with the two x columns swapped; y likewise), subtract (pre_y, pre_x), multiply by
+ * scale, subtract (post_y, post_x), clip to [0, clip_h] x [0, clip_w], keep the rows with ymin < ymax and xmin < xmax.
+ * boxes [B][Mmax][4] yxyx, classes [B][Mmax] int64, padding rows = class -1 with a zero box (what effdet_label_anchors reads);
+ * Mmax <= 512.  out_boxes / out_classes: the kept rows in their original order, then padding rows; counts [B] int32;
+ * valid [B][Mmax] bytes (0 / 1) aligned with the INPUT rows (anno['valid_indices']).  Outputs must not alias inputs. */
+typedef struct EffdetBoxParams {
+    float img_w, img_h;
+    int flip_h, flip_v;
+    float pre_y, pre_x, scale, post_y, post_x, clip_h, clip_w;
+    int reserved;
+} EffdetBoxParams;                   /* 48 bytes */
+int effdet_transform_boxes(void* stream, const float* boxes, const long long* classes, const EffdetBoxParams* params,
+                           int B, int Mmax, float* out_boxes, long long* out_classes, int* counts, unsigned char* valid);
 int effdet_stem_conv_u8(void* stream, int out_dtype, const unsigned char* X, const float* mean, const float* stdv,
                         const float* Wt, const float* scale, const float* shift, void* Y, int B, int H, int W, int Cout);
 int effdet_stem_dw_fused_u8(void* stream, int dtype, const unsigned char* X, const float* mean, const float* stdv,

@@ -28,6 +28,8 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
     'effdet_resize_pad_u8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'effdet_resample_batch_u8': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_ll, c_int, c_void_p]),
+    'effdet_transform_boxes': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_normalize_u8': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll]),
     'effdet_stem_conv_u8': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int, c_int, c_int, c_int]),

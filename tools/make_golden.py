@@ -29,6 +29,12 @@ Fixtures written
     meta_nets.npz             the reference's own MetaHead / AnchorNet / ProjectionNet classes
                               (efficientdet.py:569-830) on seeded weights and inputs: forwards, fast_weights,
                               level_offset, separate head, weighted_median, encoding tables
+    transforms.npz            data/transforms.py: transforms_coco_train / _eval / _projection on seeded noise images and boxes
+                              (inputs: tests/_pil_ref.py::transform_case): output images, boxes, classes, valid_indices,
+                              img_scale, and the parameters PIL was called with (flip, filter, sizes, offsets, crop box)
+                              Train cases 0-11 are S = 64, eval / projection S = 32; train cases 12 and 13 are S = 128
+                              because the consumer check feeds them to a PretrainStep, and 128 px is the smallest
+                              input an EfficientDet-D0 with its five pyramid levels takes
 """
 import hashlib
 import json
@@ -602,9 +608,85 @@ def gen_evaluation():
     save('evaluation', **out)
 
 
+def gen_transforms():
+    """The reference's own transform pipelines (effdet/data/transforms.py:304-368) under a seeded `random` / `np.random`.  What PIL
+    is asked to do is recorded by wrapping Image.transpose / resize / crop for the duration of a call."""
+    import random
+    from PIL import Image
+    import _pil_ref as R
+    from effdet.data.transforms import transforms_coco_train, transforms_coco_eval, transforms_projection
+    calls = []
+    orig = {n: getattr(Image.Image, n) for n in ('transpose', 'resize', 'crop')}
+
+    def wrap(name):
+        def f(self, *a, **k):
+            calls.append((name, a))
+            return orig[name](self, *a, **k)
+        return f
+
+    def run(tf, kind, seed, S, **kw):
+        img, boxes, cls = R.transform_case(kind, seed)
+        random.seed(seed)
+        np.random.seed(seed)
+        anno = dict(bbox=boxes.copy(), cls=cls.copy(), target_size=S, **kw)
+        del calls[:]
+        for n in orig:
+            setattr(Image.Image, n, wrap(n))
+        try:
+            if kind == 'train':
+                out, anno = tf(Image.fromarray(img), anno, R.TRAIN_SCALE)
+            else:
+                out, anno = tf(Image.fromarray(img), anno)
+        finally:
+            for n, fn in orig.items():
+                setattr(Image.Image, n, fn)
+        flip = int(any(n == 'transpose' for n, _ in calls))
+        (sw, sh), filt = [a for n, a in calls if n == 'resize'][0][:2]
+        crop = [a[0] for n, a in calls if n == 'crop']
+        res = {'img': out, 'obox': anno['bbox'].astype(np.float32), 'ocls': anno['cls'].astype(np.int64),
+               'img_scale': np.float64(anno['img_scale'])}
+        if 'valid_indices' in anno:
+            res['valid'] = anno['valid_indices']
+        return res, flip, int(sw), int(sh), {Image.BILINEAR: 0, Image.BICUBIC: 1}[filt], crop
+
+    out, seen = {}, set()
+    tf = transforms_coco_train(R.TRAIN_S, use_prefetcher=True)
+    tf128 = transforms_coco_train(R.TRAIN128_S, use_prefetcher=True)
+    for seed in R.TRAIN_SEEDS + R.TRAIN128_SEEDS:
+        if seed == R.TRAIN128_SEEDS[0]:                               # the four properties hold among the S = 64 cases alone
+            assert seen >= {'filter0', 'filter1', 'flip0', 'flip1', 'ox', 'oy', 'lost'}, seen
+        res, flip, sw, sh, filt, crop = run(tf128 if seed in R.TRAIN128_SEEDS else tf, 'train', seed,
+                                            R.TRAIN128_S if seed in R.TRAIN128_SEEDS else R.TRAIN_S)
+        ox, oy = crop[0][0], crop[0][1]                               # RandomResizePad crops the window after the resize
+        res['params'] = np.array([flip, filt, sw, sh, ox, oy], np.int64)
+        out.update({'train%d_%s' % (seed, k): v for k, v in res.items()})
+        seen |= {'filter%d' % filt, 'flip%d' % flip} | ({'ox'} if ox > 0 else set()) | ({'oy'} if oy > 0 else set())
+        if len(res['obox']) < R.N_BOXES:
+            seen.add('lost')
+    assert seen >= {'filter0', 'filter1', 'flip0', 'flip1', 'ox', 'oy', 'lost'}, seen
+    tf = transforms_coco_eval(R.SMALL_S, interpolation='bilinear', use_prefetcher=True)
+    for seed in R.EVAL_SEEDS:
+        res, flip, sw, sh, filt, crop = run(tf, 'eval', seed, R.SMALL_S)
+        assert not flip and not crop and filt == 0
+        out.update({'eval%d_%s' % (seed, k): v for k, v in res.items()})
+    tf = transforms_projection(R.SMALL_S, interpolation='bilinear', use_prefetcher=True)
+    inner = 0
+    for seed in R.PROJ_SEEDS:
+        res, flip, sw, sh, filt, crop = run(tf, 'proj', seed, R.SMALL_S, cls_id=1)
+        img = R.transform_case('proj', seed)[0]
+        x0, y0, x1, y1 = [int(v) for v in crop[0]]
+        assert all(isinstance(v, int) for v in crop[0]) and 0 <= x0 < x1 <= img.shape[1] and 0 <= y0 < y1 <= img.shape[0]
+        inner += (x0 > 0 or y0 > 0) and (x1 < img.shape[1] or y1 < img.shape[0])
+        res['params'] = np.array([flip, filt, sw, sh, x0, y0, x1, y1], np.int64)
+        out.update({'proj%d_%s' % (seed, k): v for k, v in res.items()})
+    assert inner >= 1, 'no projection case crops strictly inside the image'
+    save_reproducible('transforms', **out)
+    assert os.path.getsize(os.path.join(OUT, 'transforms.npz')) < 300 * 1024
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ['anchors', 'post_process', 'decode', 'soft_nms', 'generate_detections', 'loss',
-                             'labeler', 'labeler_edges', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'meta_nets', 'aux_losses']
+                             'labeler', 'labeler_edges', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'meta_nets', 'aux_losses', 'transforms']
     for w in which:
         globals()['gen_' + w]()
