@@ -622,6 +622,35 @@ int effdet_episode_cluster(void* stream, const float* embds, const float* confs,
                            float* avg_init0, unsigned char* valid, int* n_valid, long long* proto, float* avg_init,
                            float* target_clust, float* sim, long long* nearest, float* target);
 
+/* The projection phase's losses (infer.py:448-498) on the decisions of the cluster call above, forward and backward, without
+ * any n x n matrix.  embds [n][d], confs [n], labs [n] int64 (-2 / -1 / class ids); the task class is cls_id, or
+ * cls_id_dev[0] when cls_id_dev (a device pointer) is not NULL; dot_mult / dot_add / dots as for the cluster call.
+ * proto0 / valid / proto [m] and nearest [n] (NULL allowed when use_max == 0) are the cluster call's results or the caller's
+ * own decisions: proto0 / proto are clamped into [0, n) and nearest into [0, m) before use, so a bad index gives a wrong
+ * number, never an out-of-range access.  loss_mode 0 'separate', 1 'same', 2 'no_conf' (read when use_max != 0 only).
+ * Forward: losses [3] = clust_loss, embds_loss (both cosine_loss means, hinge at 0) and obj_loss (BCE-with-logits sum on
+ * dot_mult (conf + dot_add) against labs > -1); inner_target [n]; stats [6] = task mean, task min, other-object mean,
+ * other-object max, no-object mean, no-object max of inner_target (both entries of an empty group are NaN); counts [3]
+ * the three group sizes.  An empty valid set gives NaN target_clust and so NaN clust_loss, as the reference does.
+ * Backward: grad_losses [3] device floats, the upstream gradients of the three losses; d_embds [n][d], d_confs [n],
+ * d_dots [2] = d dot_mult, d dot_add are overwritten.  It must be given the workspace the forward call with the same
+ * arguments left behind (its first part holds inv, s, sim, target_clust, cmean and the prototypes).  The sum over the
+ * rows into the prototype rows runs over a fixed split of the rows and an ordered second stage, without atomics: two
+ * calls give the same bits.  n >= m, m <= 64, d <= 512, m * d <= 16384; the workspace is O(n + 32 m d) floats, its size
+ * comes from the query (-1: unsupported shape). */
+long long effdet_episode_proj_loss_workspace_floats(int n, int d, int m);
+int effdet_episode_proj_loss(void* stream, const float* embds, const float* confs, const long long* labs, int n, int d, int m,
+                             long long cls_id, const long long* cls_id_dev, float dot_mult, float dot_add, const float* dots,
+                             const long long* proto0, const unsigned char* valid, const long long* proto,
+                             const long long* nearest, int use_max, int loss_mode, float margin, float* workspace,
+                             long long workspace_floats, float* losses, float* inner_target, float* stats, int* counts);
+int effdet_episode_proj_loss_backward(void* stream, const float* embds, const float* confs, const long long* labs, int n, int d,
+                                      int m, long long cls_id, const long long* cls_id_dev, float dot_mult, float dot_add,
+                                      const float* dots, const long long* proto0, const unsigned char* valid,
+                                      const long long* proto, const long long* nearest, int use_max, int loss_mode,
+                                      float margin, const float* grad_losses, float* workspace, long long workspace_floats,
+                                      float* d_embds, float* d_confs, float* d_dots);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,13 @@ SIGNATURES = {
     'effdet_episode_cluster': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_float,
                                        c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_episode_proj_loss_workspace_floats': (c_ll, [c_int, c_int, c_int]),
+    'effdet_episode_proj_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_ll, c_void_p, c_float, c_float,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_ll,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_episode_proj_loss_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_ll, c_void_p, c_float,
+                                                  c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+                                                  c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p]),
 }
 
 

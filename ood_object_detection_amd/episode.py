@@ -1,14 +1,16 @@
 """The few-shot episode stage between the MetaHead's outputs and `ood.novelty_score` (infer.py:362-447 projection phase,
-:566-654 meta phase) on the HIP kernels of csrc/episode.hip:
+:566-654 meta phase) on the HIP kernels of csrc/episode.hip and csrc/episode_loss.hip:
 
     sel = select_anchors(confs)                                   # the anchors above the 0.875 confidence quantile, per level and image
     feed, conf = projection_feed(activs, confs, sel, proj_net)    # [embedding | anchor enc | level enc | cell enc] rows
     out = cluster(proj_net(feed).reshape(-1, d), conf.reshape(-1), B, dot_mult, dot_add)
     t = target_from_selection(proj_embds, conf.reshape(-1), out, dot_mult, dot_add)     # the same target, with autograd history
+    loss = projection_losses(proj_embds, conf.reshape(-1), labs, cls_id, out, dot_mult, dot_add)   # infer.py:448-498, forward and backward
 
 float32 GPU tensors only, no CPU fallback.  Nothing here synchronises with the host and no allocation depends on a device value,
 so the whole chain can be captured in one `torch.cuda.graph`.  The n x n matrices of the script (`sim_mat`, `thresh_mat`,
-`weighted_sim`) are never formed: every use of them is rank-1 or n x m (see csrc/episode.hip)."""
+`weighted_sim`, `mask`, `sim_target`) are never formed: every use of them is rank-1 or n x m (see csrc/episode.hip and
+csrc/episode_loss.hip)."""
 import ctypes
 
 import torch
@@ -197,3 +199,111 @@ def target_from_selection(proj_embds, confs, out, dot_mult, dot_add, sim_target=
         sim = e @ protos.mean(0)
         target = soft_thresh * sim
     return {'soft_thresh': soft_thresh, 'target_clust': target_clust, 'sim': sim, 'target': target}
+
+
+LOSS_MODES = {'separate': 0, 'same': 1, 'no_conf': 2}       # infer.py FLAGS.loss_mode
+STAT_NAMES = ('task_obj_mean', 'task_obj_min', 'other_obj_mean', 'other_obj_max', 'no_obj_mean', 'no_obj_max')
+
+
+def _proj_loss_args(e, c, labs, cls, dots, idx, n, d, m, use_max, mode, margin, dm, da):
+    return (e.data_ptr(), c.data_ptr(), labs.data_ptr(), n, d, m, cls[0], cls[1].data_ptr() if cls[1] is not None else None, dm, da,
+            dots.data_ptr() if dots is not None else None, idx[0].data_ptr(), idx[1].data_ptr(), idx[2].data_ptr(),
+            idx[3].data_ptr() if idx[3] is not None else None, use_max, mode, margin)
+
+
+class _ProjectionLosses(torch.autograd.Function):
+    """effdet_episode_proj_loss / _backward: first order only (the projection phase calls final_loss.backward(), infer.py:787-789)"""
+
+    @staticmethod
+    def forward(ctx, proj_embds, confs, dot_mult, dot_add, labs, cls, idx, m, use_max, mode, margin):
+        lib = _lib.load()
+        e = proj_embds.detach().contiguous()
+        n, d = e.shape
+        dev = e.device
+        c = confs.detach().reshape(n).contiguous()
+        ws_floats = lib.effdet_episode_proj_loss_workspace_floats(n, d, m) if n > 0 and m > 0 else -1
+        if ws_floats < 0:
+            raise ValueError('need n >= num prototypes, at most 64 prototypes, d <= 512 and prototypes * d <= 16384')
+        dm, da, dots = _dots(dot_mult, dot_add, dev)
+        ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        inner = torch.empty(n, dtype=torch.float32, device=dev)
+        stats = torch.empty(6, dtype=torch.float32, device=dev)
+        counts = torch.empty(3, dtype=torch.int32, device=dev)
+        args = _proj_loss_args(e, c, labs, cls, dots, idx, n, d, m, use_max, mode, margin, dm, da)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.effdet_episode_proj_loss(st, *args, ws.data_ptr(), ws_floats, losses.data_ptr(), inner.data_ptr(), stats.data_ptr(),
+                                                counts.data_ptr()), 'effdet_episode_proj_loss')
+        ctx.keep = (e, c, labs, cls, dots, idx, ws)
+        ctx.scalars = (n, d, m, use_max, mode, margin, dm, da, ws_floats)
+        ctx.shapes = (proj_embds.shape, confs.shape, tuple(t.shape if torch.is_tensor(t) else None for t in (dot_mult, dot_add)))
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(inner, stats, counts)
+        return losses[0], losses[1], losses[2], inner, stats, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_clust, g_embds, g_obj, *_):
+        lib = _lib.load()
+        e, c, labs, cls, dots, idx, ws = ctx.keep
+        n, d, m, use_max, mode, margin, dm, da, ws_floats = ctx.scalars
+        dev = e.device
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        gup = torch.stack([zero if g is None else g.detach().to(dtype=torch.float32).reshape(()) for g in (g_clust, g_embds, g_obj)])
+        d_e = torch.empty(n, d, dtype=torch.float32, device=dev)
+        d_c = torch.empty(n, dtype=torch.float32, device=dev)
+        d_dots = torch.empty(2, dtype=torch.float32, device=dev)
+        args = _proj_loss_args(e, c, labs, cls, dots, idx, n, d, m, use_max, mode, margin, dm, da)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.effdet_episode_proj_loss_backward(st, *args, gup.data_ptr(), ws.data_ptr(), ws_floats, d_e.data_ptr(), d_c.data_ptr(),
+                                                         d_dots.data_ptr()), 'effdet_episode_proj_loss_backward')
+        e_shape, c_shape, dot_shapes = ctx.shapes
+        g_dots = [d_dots[i].reshape(s) if s is not None and ctx.needs_input_grad[2 + i] else None for i, s in enumerate(dot_shapes)]
+        return (d_e.reshape(e_shape), d_c.reshape(c_shape), g_dots[0], g_dots[1]) + (None,) * 7
+
+
+def projection_losses(proj_embds, confs, labs, cls_id, sel, dot_mult, dot_add, sim_target='max', loss_mode='separate', margin=0.):
+    """infer.py:448-498: the losses the projection phase trains on, from the decisions `cluster` took, on the HIP kernels of
+    csrc/episode_loss.hip - no n x n `mask` / `sim_target` / `sim_mat`, forward or backward.  proj_embds [n, d] un-normalised
+    ProjectionNet outputs, confs [n] logits, labs [n] int64 anchor labels (-2 / -1 / class ids) after the same selection, cls_id
+    the task class (a number, or a tensor, which is read on the device), dot_mult / dot_add numbers or tensors.  `sel` is the
+    dict `cluster` returns; only proto0, valid, proto, nearest are read, so a caller may supply its own decisions (indices outside
+    their range are clamped into it by the kernels).  loss_mode 'separate' / 'same' / 'no_conf' applies to sim_target 'max'.
+    `torch.gather(sim_target, 1, all_max_idxs.reshape(1, -1))` of the script reads row 0 and column nearest_i of the n x n
+    target, so a row's target is +1 iff labs[0] == cls_id and labs[nearest_i] == cls_id with nearest_i in [0, m): reproduced.
+    Returns dict(clust_loss, embds_loss, obj_loss: 0-d, with autograd history to proj_embds, confs and to dot_mult / dot_add
+    when they are tensors that require grad; inner_target [n] (detached); stats: task_obj_mean, task_obj_min, other_obj_mean,
+    other_obj_max, no_obj_mean, no_obj_max as device scalars, NaN for an empty group; counts [3] int32: the three group sizes).
+    The backward is once-differentiable: the projection phase is first order (infer.py:787-789).  The meta phase differentiates
+    its target twice; that path stays with `target_from_selection`.  With nothing requiring grad only the forward runs.  An empty
+    valid set gives NaN clust_loss (and NaN 'same' embds_loss / inner_target) as the reference does; obj_loss stays finite."""
+    if sim_target not in ('avg', 'max'):
+        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    if loss_mode not in LOSS_MODES:
+        raise ValueError("loss_mode must be 'separate', 'same' or 'no_conf' (infer.py FLAGS.loss_mode)")
+    _check(proj_embds, 2, 'projection_losses')
+    n = proj_embds.shape[0]
+    dev = proj_embds.device
+    if not torch.is_tensor(confs) or confs.device != dev or confs.dtype != torch.float32 or confs.numel() != n:
+        raise RuntimeError('projection_losses: confs must be a float32 GPU tensor of n elements (no CPU fallback)')
+    if not torch.is_tensor(labs) or labs.device != dev or labs.dtype != torch.int64 or labs.numel() != n:
+        raise RuntimeError('projection_losses: labs must be an int64 GPU tensor of n elements')
+    use_max = 1 if sim_target == 'max' else 0
+    m = int(sel['proto'].numel())
+    idx = []
+    for key, dtype, count in (('proto0', torch.int64, m), ('valid', torch.bool, m), ('proto', torch.int64, m), ('nearest', torch.int64, n)):
+        if key == 'nearest' and not use_max:
+            idx.append(None)
+            continue
+        t = sel[key]
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or t.numel() != count:
+            raise RuntimeError('projection_losses: sel[%r] must be a %s GPU tensor of %d elements' % (key, dtype, count))
+        idx.append(t.detach().reshape(count).contiguous())
+    if torch.is_tensor(cls_id):
+        cls = (0, cls_id.detach().to(device=dev, dtype=torch.int64).reshape(1))
+    else:
+        cls = (int(cls_id), None)
+    out = _ProjectionLosses.apply(proj_embds, confs, dot_mult, dot_add, labs.detach().reshape(n).contiguous(), cls, tuple(idx), m,
+                                  use_max, LOSS_MODES[loss_mode], float(margin))
+    return {'clust_loss': out[0], 'embds_loss': out[1], 'obj_loss': out[2], 'inner_target': out[3],
+            'stats': dict(zip(STAT_NAMES, out[4].unbind(0))), 'counts': out[5]}

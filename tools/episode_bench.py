@@ -7,7 +7,11 @@ ProjectionNet itself is common to both and left out: both sides cluster the same
     python3 tools/episode_bench.py --phase proj       projection-phase default (P3-P7: 12 276 anchors -> 1 692 rows per image, 42 300 rows)
 
 The two paths alternate, `--rounds` windows of `--iters` iterations each (HIP events around a window, host launch overhead
-included); the report is the median window and the min .. max spread per path.  Needs the GPU: there is no fallback."""
+included); the report is the median window and the min .. max spread per path.  Needs the GPU: there is no fallback.
+
+    python3 tools/episode_bench.py --losses           episode.projection_losses forward + backward (infer.py:448-498, 787-789) against
+                                                      the literal n x n composition with autograd (tests/_episode_loss_ref.py), at the
+                                                      meta-phase size (25 x 252 rows) and the projection-phase size (25 x 1 692), d 256"""
 import argparse
 import os
 import statistics
@@ -20,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import torch  # noqa: E402
 
+import _episode_loss_ref as lref  # noqa: E402
 import _episode_ref as ref  # noqa: E402
 from ood_object_detection_amd import episode  # noqa: E402
 from ood_object_detection_amd.effdet.aux_nets import ProjectionNet  # noqa: E402
@@ -37,8 +42,68 @@ def window(fn, iters):
     return t0.elapsed_time(t1) * 1e3 / iters
 
 
+def losses_section(a, dev):
+    """projection_losses forward + backward against the literal composition, same decisions, same upstream weights"""
+    B, d = a.images, a.width // 2
+    for rows in (252, 1692):
+        n = B * rows
+        x, _ = ref.clustered_rows(2, B, rows, d)
+        confs = torch.randn(n, generator=torch.Generator().manual_seed(2))
+        labs = lref.draw_labels(2, n, True).to(dev)
+        e, c = x.to(dev).requires_grad_(), confs.to(dev).requires_grad_()
+        dm, da = torch.tensor(1.5, device=dev, requires_grad=True), torch.tensor(0.25, device=dev, requires_grad=True)
+        with torch.no_grad():
+            sel = episode.cluster(e, c, B, dm, da)
+        leaves = [e, c, dm, da]
+
+        def step(fn):
+            o = fn(e, c, labs, lref.CLS_ID, sel, dm, da, 'max', 'separate', 0.)
+            return o, torch.autograd.grad(0.03 * (30. * (o['embds_loss'] + o['clust_loss']) + 1e-4 * o['obj_loss']), leaves)
+
+        new_path = lambda: step(episode.projection_losses)
+        literal_path = lambda: step(lref.losses_literal)
+        print('losses, %d images x %d rows, n = %d, d %d; one n x n float32 matrix is %.1f MB' % (B, rows, n, d, n * n * 4 / 1e6))
+        o_new, g_new = new_path()
+        literal, iters_lit = not a.no_literal, a.iters if n * n < 1e8 else max(1, a.iters // 20)
+        if literal:
+            try:
+                o_lit, g_lit = literal_path()
+                torch.cuda.synchronize()
+                print('same outputs: losses differ by %.2e (relative), gradients by %.2e of the largest entry'
+                      % (max(float((o_new[k] - o_lit[k]).abs() / o_lit[k].abs().clamp(min=1e-30)) for k in ('clust_loss', 'embds_loss', 'obj_loss')),
+                         max(float((p - q).abs().max() / q.abs().max()) for p, q in zip(g_new, g_lit))))
+                del o_lit, g_lit
+            except torch.OutOfMemoryError:
+                print('literal form: cannot run at this size (out of memory with %.0f GB free)' % (torch.cuda.mem_get_info()[0] / 1e9))
+                literal = False
+            torch.cuda.empty_cache()
+        for _ in range(3):
+            window(new_path, 5)
+            if literal:
+                window(literal_path, 2)
+        t_new, t_lit = [], []
+        for _ in range(a.rounds):
+            t_new.append(window(new_path, a.iters))
+            if literal:
+                t_lit.append(window(literal_path, iters_lit))
+        print('projection_losses forward + backward (6 HIP launches): median %.1f us, spread %.1f .. %.1f us  (%d windows of %d)'
+              % (statistics.median(t_new), min(t_new), max(t_new), a.rounds, a.iters))
+        if literal:
+            print('literal torch composition with autograd:               median %.1f us, spread %.1f .. %.1f us  (windows of %d)'
+                  % (statistics.median(t_lit), min(t_lit), max(t_lit), iters_lit))
+            print('ratio literal / new: %.2f' % (statistics.median(t_lit) / statistics.median(t_new)))
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        new_path()
+        torch.cuda.synchronize()
+        print('peak memory of one forward + backward: %.1f MB above the %.1f MB of inputs'
+              % ((torch.cuda.max_memory_allocated() - base) / 1e6, (e.numel() * 4 + c.numel() * 4 + labs.numel() * 8) / 1e6))
+        print()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--losses', action='store_true', help='time projection_losses forward + backward instead of the episode stage')
     ap.add_argument('--phase', choices=['meta', 'proj'], default='meta')
     ap.add_argument('--images', type=int, default=25)
     ap.add_argument('--fpn', type=int, default=160)
@@ -49,6 +114,8 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'episode_bench needs the GPU'
     dev = 'cuda:0'
+    if a.losses:
+        return losses_section(a, dev)
     sides, first = ([8, 4, 2], 2) if a.phase == 'meta' else ([32, 16, 8, 4, 2], 0)
     B, Fc, d = a.images, a.fpn, a.width // 2
     torch.manual_seed(0)
