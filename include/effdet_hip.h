@@ -651,6 +651,40 @@ int effdet_episode_proj_loss_backward(void* stream, const float* embds, const fl
                                       float margin, const float* grad_losses, float* workspace, long long workspace_floats,
                                       float* d_embds, float* d_confs, float* d_dots);
 
+/* The meta phase's support loss (infer.py:645-658), loss = mean_i BCE-with-logits(logits_i, t_i) with the target
+ * t_i = s_i target_clust[nearest_i] sim_i ('max', use_max != 0) or s_i sim_i ('avg') of the cluster call, on the decisions
+ * proto0 / valid / proto / nearest (clamped as for effdet_episode_proj_loss), differentiable twice.  float32; logits [n] may
+ * be the same memory as confs.  Forward: loss [1], target [n]; the first O(n + m d) floats of the workspace keep inv, s, sim,
+ * target_clust, cmean and the prototypes for the two later calls, which must be given the same arguments and workspace.
+ * Backward: grad_loss [1] a device float, the upstream gradient g; d_embds [n][d], d_confs [n], d_logits [n], d_dots [2] are
+ * overwritten.  thresh_grad == 0 holds s constant (FLAGS.inner_thresh_train off): d_confs and d_dots are then zero.
+ * Backward2: the backward of that backward.  v_embds [n][d], v_confs [n], v_logits [n], v_mult [1], v_add [1] are the
+ * cotangents on d_embds, d_confs, d_logits, d_dots[0], d_dots[1]; any of them may be NULL (zero).  d_grad [1] receives the
+ * gradient with respect to g, h_embds / h_confs / h_logits / h_dots the ones with respect to the forward's inputs (g times a
+ * Hessian-vector product).  Third order is not provided.  No atomics, every sum in a fixed order: two calls give the same
+ * bits.  The forward and the backward compute in float32, backward2 in float64 from the float32 inputs with one rounding on
+ * the way out; it uses the workspace's scratch as doubles, so the workspace must be 8-byte aligned (EINVAL otherwise).
+ * n >= m, m <= 64, d <= 512, m * d <= 16384; the workspace is at most 11.5 n + 75 m d + 4 d + 400 floats (3 n + m d kept, the
+ * rest scratch of a pass; -1 from the query: unsupported). */
+long long effdet_episode_supp_loss_workspace_floats(int n, int d, int m);
+int effdet_episode_supp_loss(void* stream, const float* embds, const float* confs, const float* logits, int n, int d, int m,
+                             float dot_mult, float dot_add, const float* dots, const long long* proto0,
+                             const unsigned char* valid, const long long* proto, const long long* nearest, int use_max,
+                             float* workspace, long long workspace_floats, float* loss, float* target);
+int effdet_episode_supp_loss_backward(void* stream, const float* embds, const float* confs, const float* logits, int n, int d,
+                                      int m, float dot_mult, float dot_add, const float* dots, const long long* proto0,
+                                      const unsigned char* valid, const long long* proto, const long long* nearest,
+                                      int use_max, int thresh_grad, const float* grad_loss, float* workspace,
+                                      long long workspace_floats, float* d_embds, float* d_confs, float* d_logits,
+                                      float* d_dots);
+int effdet_episode_supp_loss_backward2(void* stream, const float* embds, const float* confs, const float* logits, int n, int d,
+                                       int m, float dot_mult, float dot_add, const float* dots, const long long* proto0,
+                                       const unsigned char* valid, const long long* proto, const long long* nearest,
+                                       int use_max, int thresh_grad, const float* grad_loss, const float* v_embds,
+                                       const float* v_confs, const float* v_logits, const float* v_mult, const float* v_add,
+                                       float* workspace, long long workspace_floats, float* d_grad, float* h_embds,
+                                       float* h_confs, float* h_logits, float* h_dots);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,16 @@ SIGNATURES = {
     'effdet_episode_proj_loss_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_ll, c_void_p, c_float,
                                                   c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
                                                   c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p]),
+    'effdet_episode_supp_loss_workspace_floats': (c_ll, [c_int, c_int, c_int]),
+    'effdet_episode_supp_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_void_p]),
+    'effdet_episode_supp_loss_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                  c_ll, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_episode_supp_loss_backward2': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -6,11 +6,12 @@
     out = cluster(proj_net(feed).reshape(-1, d), conf.reshape(-1), B, dot_mult, dot_add)
     t = target_from_selection(proj_embds, conf.reshape(-1), out, dot_mult, dot_add)     # the same target, with autograd history
     loss = projection_losses(proj_embds, conf.reshape(-1), labs, cls_id, out, dot_mult, dot_add)   # infer.py:448-498, forward and backward
+    supp = support_loss(proj_embds, conf.reshape(-1), cls_logits, out, dot_mult, dot_add)          # infer.py:645-658, differentiable twice
 
 float32 GPU tensors only, no CPU fallback.  Nothing here synchronises with the host and no allocation depends on a device value,
 so the whole chain can be captured in one `torch.cuda.graph`.  The n x n matrices of the script (`sim_mat`, `thresh_mat`,
-`weighted_sim`, `mask`, `sim_target`) are never formed: every use of them is rank-1 or n x m (see csrc/episode.hip and
-csrc/episode_loss.hip)."""
+`weighted_sim`, `mask`, `sim_target`) are never formed: every use of them is rank-1 or n x m (see csrc/episode.hip,
+csrc/episode_loss.hip and csrc/episode_support.hip)."""
 import ctypes
 
 import torch
@@ -181,7 +182,8 @@ def target_from_selection(proj_embds, confs, out, dot_mult, dot_add, sim_target=
     """The differentiable remainder: `target_clust`, `sim` and `target` re-derived from the indices `cluster` returned, as plain
     torch row gathers and row dot products on [n, d] (no n x n), so training code gets them with autograd history, also under
     create_graph=True.  The discrete decisions (prototypes, valid set, nearest prototype) are constants here, as they are
-    non-differentiable in the reference.  Returns dict(soft_thresh, target_clust [m], sim [n], target [n])."""
+    non-differentiable in the reference.  Returns dict(soft_thresh, target_clust [m], sim [n], target [n]).  The meta phase's
+    binary cross-entropy on this target has its own HIP kernels at both orders: `support_loss`."""
     _check(proj_embds, 2, 'target_from_selection')
     if sim_target not in ('avg', 'max'):
         raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
@@ -275,7 +277,7 @@ def projection_losses(proj_embds, confs, labs, cls_id, sel, dot_mult, dot_add, s
     when they are tensors that require grad; inner_target [n] (detached); stats: task_obj_mean, task_obj_min, other_obj_mean,
     other_obj_max, no_obj_mean, no_obj_max as device scalars, NaN for an empty group; counts [3] int32: the three group sizes).
     The backward is once-differentiable: the projection phase is first order (infer.py:787-789).  The meta phase differentiates
-    its target twice; that path stays with `target_from_selection`.  With nothing requiring grad only the forward runs.  An empty
+    its loss twice; that is `support_loss`.  With nothing requiring grad only the forward runs.  An empty
     valid set gives NaN clust_loss (and NaN 'same' embds_loss / inner_target) as the reference does; obj_loss stays finite."""
     if sim_target not in ('avg', 'max'):
         raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
@@ -307,3 +309,146 @@ def projection_losses(proj_embds, confs, labs, cls_id, sel, dot_mult, dot_add, s
                                   use_max, LOSS_MODES[loss_mode], float(margin))
     return {'clust_loss': out[0], 'embds_loss': out[1], 'obj_loss': out[2], 'inner_target': out[3],
             'stats': dict(zip(STAT_NAMES, out[4].unbind(0))), 'counts': out[5]}
+
+
+def _sel_indices(sel, dev, n, use_max, what):
+    m = int(sel['proto'].numel())
+    idx = []
+    for key, dtype, count in (('proto0', torch.int64, m), ('valid', torch.bool, m), ('proto', torch.int64, m), ('nearest', torch.int64, n)):
+        if key == 'nearest' and not use_max:
+            idx.append(None)
+            continue
+        t = sel[key]
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or t.numel() != count:
+            raise RuntimeError('%s: sel[%r] must be a %s GPU tensor of %d elements' % (what, key, dtype, count))
+        idx.append(t.detach().reshape(count).contiguous())
+    return m, tuple(idx)
+
+
+class _SuppState:
+    """what the three passes of one support_loss call share: detached inputs, decisions, the workspace the forward filled"""
+
+    def args(self, thresh=None):
+        e, c, x, idx, dots = self.e, self.c, self.x, self.idx, self.dots
+        a = (e.data_ptr(), c.data_ptr(), x.data_ptr(), self.n, self.d, self.m, self.dm, self.da, dots.data_ptr() if dots is not None else None,
+             idx[0].data_ptr(), idx[1].data_ptr(), idx[2].data_ptr(), idx[3].data_ptr() if idx[3] is not None else None, self.use_max)
+        return a if thresh is None else a + (thresh,)
+
+
+def _opt(t, shape):
+    """a cotangent or None -> (float32 contiguous tensor of `shape` or None, its pointer or None)"""
+    if t is None:
+        return None, None
+    t = t.detach().to(dtype=torch.float32).expand(shape).contiguous()
+    return t, t.data_ptr()
+
+
+class _SupportLoss(torch.autograd.Function):
+    """effdet_episode_supp_loss; its backward is _SupportLossGrad, itself differentiable once"""
+
+    @staticmethod
+    def forward(ctx, proj_embds, confs, logits, dot_mult, dot_add, idx, m, use_max, thresh_grad):
+        lib = _lib.load()
+        st = _SuppState()
+        st.e = proj_embds.detach().contiguous()
+        st.n, st.d = st.e.shape
+        dev = st.e.device
+        st.c = confs.detach().reshape(st.n).contiguous()
+        st.x = logits.detach().reshape(st.n).contiguous()
+        st.idx, st.m, st.use_max, st.thresh_grad = idx, m, use_max, thresh_grad
+        st.ws_floats = lib.effdet_episode_supp_loss_workspace_floats(st.n, st.d, m) if st.n > 0 and m > 0 else -1
+        if st.ws_floats < 0:
+            raise ValueError('need n >= num prototypes, at most 64 prototypes, d <= 512 and prototypes * d <= 16384')
+        st.dm, st.da, st.dots = _dots(dot_mult, dot_add, dev)
+        st.ws = torch.empty(st.ws_floats, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        target = torch.empty(st.n, dtype=torch.float32, device=dev)
+        _lib.check(lib.effdet_episode_supp_loss(torch.cuda.current_stream(dev).cuda_stream, *st.args(), st.ws.data_ptr(), st.ws_floats,
+                                                loss.data_ptr(), target.data_ptr()), 'effdet_episode_supp_loss')
+        ctx.st = st
+        ctx.dot_tensors = tuple(torch.is_tensor(t) for t in (dot_mult, dot_add))
+        ctx.save_for_backward(proj_embds, confs, logits, *(t for t in (dot_mult, dot_add) if torch.is_tensor(t)))
+        ctx.mark_non_differentiable(target)
+        return loss, target
+
+    @staticmethod
+    def backward(ctx, g, _):
+        saved = list(ctx.saved_tensors)
+        proj_embds, confs, logits = saved[:3]
+        rest = saved[3:]
+        dot_mult, dot_add = (rest.pop(0) if is_t else None for is_t in ctx.dot_tensors)
+        d_e, d_c, d_x, d_m, d_a = _SupportLossGrad.apply(g, proj_embds, confs, logits, dot_mult, dot_add, ctx.st)
+        if not ctx.st.thresh_grad:
+            d_c = d_m = d_a = None                      # soft_thresh is a constant: nothing reaches confs or the dots through it
+        return (d_e, d_c, d_x, d_m if ctx.dot_tensors[0] else None, d_a if ctx.dot_tensors[1] else None, None, None, None, None)
+
+
+class _SupportLossGrad(torch.autograd.Function):
+    """effdet_episode_supp_loss_backward, with effdet_episode_supp_loss_backward2 as its (once-differentiable) backward"""
+
+    @staticmethod
+    def forward(ctx, g, proj_embds, confs, logits, dot_mult, dot_add, st):
+        lib = _lib.load()
+        dev = st.e.device
+        gup = g.detach().to(dtype=torch.float32).reshape(1).contiguous()
+        d_e = torch.empty(st.n, st.d, dtype=torch.float32, device=dev)
+        d_cx = torch.empty(2, st.n, dtype=torch.float32, device=dev)
+        d_dots = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.check(lib.effdet_episode_supp_loss_backward(torch.cuda.current_stream(dev).cuda_stream, *st.args(1 if st.thresh_grad else 0),
+                                                         gup.data_ptr(), st.ws.data_ptr(), st.ws_floats, d_e.data_ptr(), d_cx[0].data_ptr(),
+                                                         d_cx[1].data_ptr(), d_dots.data_ptr()), 'effdet_episode_supp_loss_backward')
+        ctx.st, ctx.gup = st, gup
+        ctx.save_for_backward(proj_embds, confs, logits)     # the kernels read st's aliases; saved so that an in-place change raises
+        ctx.shapes = (g.shape, proj_embds.shape, confs.shape, logits.shape) + tuple(t.shape if torch.is_tensor(t) else None for t in (dot_mult, dot_add))
+        ctx.set_materialize_grads(False)
+        return (d_e.reshape(proj_embds.shape), d_cx[0].reshape(confs.shape), d_cx[1].reshape(logits.shape),
+                d_dots[0].reshape(ctx.shapes[4] or ()), d_dots[1].reshape(ctx.shapes[5] or ()))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v_e, v_c, v_x, v_m, v_a):
+        lib = _lib.load()
+        st = ctx.st
+        ctx.saved_tensors                                    # autograd's version check of the inputs st aliases
+        dev = st.e.device
+        keep = [_opt(v_e, (st.n, st.d)), _opt(None if v_c is None else v_c.reshape(-1), (st.n,)),
+                _opt(None if v_x is None else v_x.reshape(-1), (st.n,)), _opt(None if v_m is None else v_m.reshape(()), ()), _opt(None if v_a is None else v_a.reshape(()), ())]
+        d_g = torch.empty(1, dtype=torch.float32, device=dev)
+        h_e = torch.empty(st.n, st.d, dtype=torch.float32, device=dev)
+        h_cx = torch.empty(2, st.n, dtype=torch.float32, device=dev)
+        h_dots = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.check(lib.effdet_episode_supp_loss_backward2(torch.cuda.current_stream(dev).cuda_stream, *st.args(1 if st.thresh_grad else 0),
+                                                          ctx.gup.data_ptr(), *(ptr for _, ptr in keep), st.ws.data_ptr(), st.ws_floats,
+                                                          d_g.data_ptr(), h_e.data_ptr(), h_cx[0].data_ptr(), h_cx[1].data_ptr(),
+                                                          h_dots.data_ptr()), 'effdet_episode_supp_loss_backward2')
+        g_shape, e_shape, c_shape, x_shape, m_shape, a_shape = ctx.shapes
+        need = ctx.needs_input_grad
+        return (d_g.reshape(g_shape) if need[0] else None, h_e.reshape(e_shape), h_cx[0].reshape(c_shape) if st.thresh_grad else None,
+                h_cx[1].reshape(x_shape), h_dots[0].reshape(m_shape) if m_shape is not None and need[4] and st.thresh_grad else None,
+                h_dots[1].reshape(a_shape) if a_shape is not None and need[5] and st.thresh_grad else None, None)
+
+
+def support_loss(proj_embds, confs, cls_logits, sel, dot_mult, dot_add, sim_target='max', thresh_grad=True):
+    """infer.py:645-658: the meta phase's inner loss, `F.binary_cross_entropy_with_logits(cls_logits, target)` on the target of
+    :648 / :652, from the decisions `cluster` took, on the HIP kernels of csrc/episode_support.hip at every order the meta phase
+    needs: the value, `torch.autograd.grad(loss, ..., create_graph=True)` and the backward through that gradient.  proj_embds [n, d]
+    un-normalised ProjectionNet outputs, confs [n] the confidence logits, cls_logits [n] the class logits (the same tensor as
+    confs without FLAGS.separate_head; autograd adds the two gradients), dot_mult / dot_add numbers or tensors.  `sel` is the dict
+    `cluster` returns; only proto0, valid, proto (and nearest for 'max') are read, and indices outside their range are clamped
+    into it by the kernels.  thresh_grad=False is FLAGS.inner_thresh_train off (infer.py:611): soft_thresh is a constant at
+    every order and confs / dot_mult / dot_add get no gradient through it.  The target is not confined to [0, 1]; the formula
+    max(x, 0) - x t + log1p(exp(-|x|)) holds as it is.  Returns dict(loss: 0-d, target: [n] detached, equal to cluster's).
+    An empty valid set gives NaN loss, target and gradients for 'max', as the reference does.  Third order is not built.  With
+    nothing requiring grad only the forward runs; without create_graph the gradient records nothing."""
+    if sim_target not in ('avg', 'max'):
+        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    _check(proj_embds, 2, 'support_loss')
+    n = proj_embds.shape[0]
+    dev = proj_embds.device
+    for name, t in (('confs', confs), ('cls_logits', cls_logits)):
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != torch.float32 or t.numel() != n:
+            raise RuntimeError('support_loss: %s must be a float32 GPU tensor of n elements (no CPU fallback)' % name)
+    use_max = 1 if sim_target == 'max' else 0
+    m, idx = _sel_indices(sel, dev, n, use_max, 'support_loss')
+    loss, target = _SupportLoss.apply(proj_embds, confs, cls_logits, dot_mult, dot_add, idx, m, use_max, bool(thresh_grad))
+    return {'loss': loss, 'target': target}

@@ -11,7 +11,11 @@ included); the report is the median window and the min .. max spread per path.  
 
     python3 tools/episode_bench.py --losses           episode.projection_losses forward + backward (infer.py:448-498, 787-789) against
                                                       the literal n x n composition with autograd (tests/_episode_loss_ref.py), at the
-                                                      meta-phase size (25 x 252 rows) and the projection-phase size (25 x 1 692), d 256"""
+                                                      meta-phase size (25 x 252 rows) and the projection-phase size (25 x 1 692), d 256
+    python3 tools/episode_bench.py --support          episode.support_loss (infer.py:645-658) against target_from_selection +
+                                                      F.binary_cross_entropy_with_logits on the same decisions, at the meta-phase default
+                                                      (25 x 252 rows, d 256): the loss, the create_graph=True gradient to the embeddings
+                                                      and logits, and the backward of a scalar of that gradient"""
 import argparse
 import os
 import statistics
@@ -23,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
 
 import _episode_loss_ref as lref  # noqa: E402
 import _episode_ref as ref  # noqa: E402
@@ -101,9 +106,64 @@ def losses_section(a, dev):
         print()
 
 
+def support_section(a, dev):
+    """support_loss against target_from_selection + BCE: the same decisions, one head (the class logits are the confidences)"""
+    B, d, rows = a.images, a.width // 2, 252
+    n = B * rows
+    x, _ = ref.clustered_rows(2, B, rows, d)
+    gen = torch.Generator().manual_seed(2)
+    e, c = x.to(dev).requires_grad_(), torch.randn(n, generator=gen).to(dev).requires_grad_()
+    dm, da = torch.tensor(1.5, device=dev, requires_grad=True), torch.tensor(0.25, device=dev, requires_grad=True)
+    w_e, w_c = torch.randn(n, d, generator=gen).to(dev), torch.randn(n, generator=gen).to(dev)
+    with torch.no_grad():
+        sel = episode.cluster(e, c, B, dm, da)
+
+    def hip_loss():
+        return episode.support_loss(e, c, c, sel, dm, da)['loss']
+
+    def torch_loss():
+        return F.binary_cross_entropy_with_logits(c, episode.target_from_selection(e, c, sel, dm, da)['target'])
+
+    def inner(loss_fn):
+        return torch.autograd.grad(loss_fn(), [e, c], create_graph=True)
+
+    def outer(loss_fn):
+        g = inner(loss_fn)
+        return torch.autograd.grad((g[0] * w_e).sum() + (g[1] * w_c).sum(), [e, c, dm, da])
+
+    print('support loss, %d images x %d rows, n = %d, d %d' % (B, rows, n, d))
+    with torch.no_grad():
+        l_new, l_old = hip_loss(), torch_loss()
+    g_new, g_old, h_new, h_old = inner(hip_loss), inner(torch_loss), outer(hip_loss), outer(torch_loss)
+    torch.cuda.synchronize()
+    print('same outputs: loss differs by %.2e (relative), gradients by %.2e, second-order results by %.2e of the largest entry'
+          % (float((l_new - l_old).abs() / l_old.abs()), max(float((p - q).abs().max() / q.abs().max()) for p, q in zip(g_new, g_old)),
+             max(float((p - q).abs().max() / q.abs().max()) for p, q in zip(h_new, h_old))))
+    del g_new, g_old, h_new, h_old
+    stages = [('loss', lambda f: f(), 3), ('loss + create_graph gradient', inner, 6), ('loss + gradient + backward through it', outer, 10)]
+    for name, stage, launches in stages:
+        paths = [lambda: stage(hip_loss), lambda: stage(torch_loss)]
+        if name == 'loss':
+            paths = [torch.no_grad()(p) for p in paths]
+        for _ in range(3):
+            for p in paths:
+                window(p, 5)
+        t_new, t_old = [], []
+        for _ in range(a.rounds):
+            t_new.append(window(paths[0], a.iters))
+            t_old.append(window(paths[1], a.iters))
+        print('%s' % name)
+        print('  support_loss (%2d HIP launches):          median %.1f us, spread %.1f .. %.1f us  (%d windows of %d)'
+              % (launches, statistics.median(t_new), min(t_new), max(t_new), a.rounds, a.iters))
+        print('  target_from_selection + BCE (torch):     median %.1f us, spread %.1f .. %.1f us'
+              % (statistics.median(t_old), min(t_old), max(t_old)))
+        print('  ratio torch / support_loss: %.2f' % (statistics.median(t_old) / statistics.median(t_new)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--losses', action='store_true', help='time projection_losses forward + backward instead of the episode stage')
+    ap.add_argument('--support', action='store_true', help='time support_loss at its three orders instead of the episode stage')
     ap.add_argument('--phase', choices=['meta', 'proj'], default='meta')
     ap.add_argument('--images', type=int, default=25)
     ap.add_argument('--fpn', type=int, default=160)
@@ -116,6 +176,8 @@ def main():
     dev = 'cuda:0'
     if a.losses:
         return losses_section(a, dev)
+    if a.support:
+        return support_section(a, dev)
     sides, first = ([8, 4, 2], 2) if a.phase == 'meta' else ([32, 16, 8, 4, 2], 0)
     B, Fc, d = a.images, a.fpn, a.width // 2
     torch.manual_seed(0)

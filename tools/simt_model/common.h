@@ -1,0 +1,66 @@
+// A CPU model of the SIMT execution, enough to run csrc/episode_support.hip as host C++ (tools/simt_model/run.py copies the kernel
+// source beside this file, where `#include "common.h"` finds it instead of csrc/common.h): one std::thread per thread of a
+// workgroup, the workgroups one after another, a barrier for __syncthreads and one per wave for the shuffles and the ballot.
+// __shared__ is a function-local static, shared by the threads of the one workgroup that is running.  It checks the arithmetic and
+// the indexing of a kernel, not its timing or its memory model.
+#pragma once
+#include <cmath>
+#include <cstring>
+#include <thread>
+#include <vector>
+#include <barrier>
+#include <memory>
+#include <algorithm>
+#define DEV static inline
+#define __global__
+#define __shared__ static
+#define __launch_bounds__(x)
+#define EFFDET_ENTER() (void)0
+#define EFFDET_OK 0
+#define EFFDET_EINVAL 1
+#define EFFDET_ELAUNCH 2
+static inline int effdet_check_launch() { return 0; }
+typedef void* hipStream_t;
+struct dim3 { int x, y, z; dim3(int a = 1, int b = 1, int c = 1) : x(a), y(b), z(c) {} };
+struct SimCtx { std::barrier<>* block; std::barrier<>* wave; double* xf; int* xi; };
+static thread_local dim3 threadIdx, blockIdx, gridDim;
+static thread_local SimCtx simctx;
+static inline void __syncthreads() { simctx.block->arrive_and_wait(); }
+static inline int __builtin_amdgcn_readfirstlane(int v) { return v; }
+template <class T> static inline T __shfl_xor(T v, int o, int) {
+    const int lane = threadIdx.x & 63;
+    simctx.xf[lane] = v; simctx.wave->arrive_and_wait();
+    const T r = (T)simctx.xf[lane ^ o]; simctx.wave->arrive_and_wait();
+    return r;
+}
+static inline unsigned long long __ballot(bool p) {
+    const int lane = threadIdx.x & 63;
+    simctx.xi[lane] = p ? 1 : 0; simctx.wave->arrive_and_wait();
+    unsigned long long r = 0;
+    for (int i = 0; i < 64; ++i) if (simctx.xi[i]) r |= 1ull << i;
+    simctx.wave->arrive_and_wait();
+    return r;
+}
+DEV float wave_reduce_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
+template <class K, class... A>
+void sim_launch(K kernel, dim3 grid, dim3 block, A... args) {
+    const int nt = block.x, nw = (nt + 63) / 64;
+    for (int by = 0; by < grid.y; ++by)
+        for (int bx = 0; bx < grid.x; ++bx) {
+            std::barrier<> bb(nt);
+            std::vector<std::unique_ptr<std::barrier<>>> wb;
+            std::vector<std::vector<double>> xf(nw, std::vector<double>(64));
+            std::vector<std::vector<int>> xi(nw, std::vector<int>(64));
+            for (int w = 0; w < nw; ++w) wb.emplace_back(new std::barrier<>(std::min(64, nt - 64 * w)));
+            std::vector<std::thread> th;
+            for (int t = 0; t < nt; ++t)
+                th.emplace_back([&, t] {
+                    threadIdx = dim3(t); blockIdx = dim3(bx, by); gridDim = grid;
+                    simctx = SimCtx{&bb, wb[t / 64].get(), xf[t / 64].data(), xi[t / 64].data()};
+                    kernel(args...);
+                });
+            for (auto& x : th) x.join();
+        }
+}
+#define hipLaunchKernelGGL(k, g, b, sh, st, ...) sim_launch(k, g, b, __VA_ARGS__)
+using std::fmax; using std::sqrt; using std::exp;
