@@ -222,11 +222,15 @@ int effdet_sepconv_fused(void* stream, int dtype, int B, int nlevels, const int*
  * levels, each followed by F.batch_norm(training=True) (statistics of the current batch, per level) and Swish.
  * effdet_sepconv_meta runs one layer for all levels: the previous layer's batch-norm arrives folded into
  * in_scale / in_shift [rows][F] (row in_affine_row[level]; NULL for the first layer) applied before the SiLU (pre_act),
- * the conv output + bias is written raw and its per-channel sums / sums of squares go to stat_partial
- * [B][effdet_sepconv_tiles][2][N] (NULL: not needed).  dw_out (optional, per level [B, H*W, F]) receives the
- * depthwise output (`x_pred`, what ret_activs returns).  effdet_bn_batch_stats turns the partial sums into the next
+ * the conv output q + bias is written raw and, per tile and channel, three floats go to stat_partial
+ * [B][effdet_sepconv_tiles][3][N] (NULL: not needed): a pivot (the tile's first pixel), the sum of q - pivot and the sum of
+ * (q - pivot)^2 over the tile's pixels inside the map.  dw_out (optional, per level [B, H*W, F]) receives the
+ * depthwise output (`x_pred`, what ret_activs returns).  effdet_bn_batch_stats (same dtype and level_hw as the launch that
+ * wrote the table: the tile counts follow from them) merges the tiles by Chan's update in double and turns them into the next
  * layer's scale / shift [nlevels][N]: scale = w / sqrt(var_biased + eps), shift = b - mean * scale with
- * weight / bias [rows][N] (row param_row[level]). */
+ * weight / bias [rows][N] (row param_row[level]).
+ * Widths: F a multiple of 8 whose tile fits 160 KiB of LDS - up to 288 (float32 needs 162 432 bytes there); F >= 384 returns
+ * the invalid-argument code from effdet_sepconv_meta in both dtypes, before anything is launched. */
 int effdet_sepconv_meta(void* stream, int dtype, int B, int nlevels, const int* level_hw,
                         const void* const* in_ptr, const long long* in_image_stride,
                         const float* in_scale, const float* in_shift, const int* in_affine_row, int pre_act,

@@ -53,7 +53,7 @@ struct SepArgs {
     // META (MetaHead, effdet/efficientdet.py:569-695): batch-statistics BN of the previous layer arrives as a per-level
     // affine applied to the input before the activation, and this layer's outputs are summed for the next one's statistics
     const float* in_scale; const float* in_shift;   // [rows][F] or null
-    float* stat_partial;                            // [B][tiles][2][N] per-workgroup sums / sums of squares, or null
+    float* stat_partial;                            // [B][tiles][3][N] per workgroup: pivot | sum (q - pivot) | sum (q - pivot)^2, or null
     int tiles_total;
 };
 
@@ -650,12 +650,14 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? (FT == 64 && !OOD && !META && !Is
             continue;
         }
         // Epilogue in registers: per 32-channel group J this lane holds channels [32J + 8fp, +8) of its pixel
-        float st1[META ? NP : 1][8], st2[META ? NP : 1][8];
+        float stq[META ? WPT : 1][META ? NP : 1][8];       // META: the values the statistics are taken of
         if constexpr (META) {
 #pragma unroll
-            for (int J = 0; J < NP; ++J)
+            for (int i = 0; i < WPT; ++i)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { st1[J][e] = 0.f; st2[J][e] = 0.f; }
+                for (int J = 0; J < NP; ++J)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) stq[i][J][e] = 0.f;
         }
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
@@ -703,12 +705,12 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? (FT == 64 && !OOD && !META && !Is
                             store_piece<T>(out + pix_off[i] + n_begin + cb, vals[J], nvalid, p.vec_ok != 0);
                     }
                     if constexpr (META) {
-                        if (p.stat_partial != nullptr && pix_in[i]) {
+                        if (p.stat_partial != nullptr) {
 #pragma unroll
                             for (int e = 0; e < 8; ++e) {
                                 float q = vals[J][e];
                                 if constexpr (!IsPair<T>::value) q = to_f<T>(from_f<T>(vals[J][e]));   // statistics of what the next layer reads
-                                st1[J][e] += q; st2[J][e] += q * q;
+                                stq[i][J][e] = q;
                             }
                         }
                     }
@@ -767,14 +769,33 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? (FT == 64 && !OOD && !META && !Is
         }
         if constexpr (META) {
             if (p.stat_partial != nullptr) {
-                // per-channel sums over this workgroup's pixels: 16 lanes (pixels) by shuffles, the waves through LDS in a
-                // fixed order, one row of the partial table per workgroup
+                // Per-channel sums over this workgroup's pixels, SHIFTED by a pivot: the value of the tile's first pixel (always inside
+                // the map), so that the sums hold q - pivot (of the order of the channel's spread, not of its mean) and their
+                // squares.  sum q*q / n - mean^2 on plain float32 sums loses the variance of a channel whose mean is many
+                // standard deviations from zero (and most of it at 2 - 4 samples per channel); the shifted sums keep float32's
+                // relative accuracy on the deviations themselves.  The pivot travels through the scale half of `cs` - a META
+                // launch has no scale (checked on the host), nothing reads that half after this chunk's load.
+                // 16 lanes (pixels) by shuffles, the waves through LDS in a fixed order, one row of the partial table per workgroup.
+                float* piv = cs;                               // [BN]
                 float* sst = cs + 2 * BN;                      // [NWAVE][2][BN]
+                if (wave == 0 && frow == 0) {                  // pixel 0 of the tile: wave 0, tile 0, row 0
+#pragma unroll
+                    for (int J = 0; J < NP; ++J)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) piv[32 * J + 8 * fpiece + e] = stq[0][J][e];
+                }
+                __syncthreads();
 #pragma unroll
                 for (int J = 0; J < NP; ++J)
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        float a = st1[J][e], q = st2[J][e];
+                        const float pv = piv[32 * J + 8 * fpiece + e];
+                        float a = 0.f, q = 0.f;
+#pragma unroll
+                        for (int i = 0; i < WPT; ++i) {
+                            const float d = pix_in[i] ? stq[i][J][e] - pv : 0.f;
+                            a += d; q += d * d;
+                        }
 #pragma unroll
                         for (int o = 1; o < 16; o <<= 1) { a += __shfl_xor(a, o, 64); q += __shfl_xor(q, o, 64); }
                         if (frow == 0) { sst[(wave * 2 + 0) * BN + 32 * J + 8 * fpiece + e] = a; sst[(wave * 2 + 1) * BN + 32 * J + 8 * fpiece + e] = q; }
@@ -784,8 +805,11 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? (FT == 64 && !OOD && !META && !Is
                     const int which = tid / BN, n = tid % BN;
                     float tot = 0.f;
                     for (int w = 0; w < NWAVE; ++w) tot += sst[(w * 2 + which) * BN + n];
-                    if (n < n_count)
-                        p.stat_partial[(((long long)b * p.tiles_total + blockIdx.x) * 2 + which) * N + n_begin + n] = tot;
+                    if (n < n_count) {
+                        float* row = p.stat_partial + (((long long)b * p.tiles_total + blockIdx.x) * 3) * N + n_begin + n;
+                        row[(1 + which) * (long long)N] = tot;
+                        if (which == 0) row[0] = piv[n];
+                    }
                 }
             }
         }
@@ -971,7 +995,7 @@ static int sepconv_common(
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (meta) {                                  // MetaHead layers: generic-width kernels with the extra inputs / outputs
-        if (ood_classes > 0 || fuse_mode != 0 || out_f32) return EFFDET_EINVAL;
+        if (ood_classes > 0 || fuse_mode != 0 || out_f32 || scale != nullptr) return EFFDET_EINVAL;   // (no scale: its LDS row carries the statistics pivot)
         return dtype == 0 ? launch_sep<float, 8, 8, 64, false, 256, 0, true>(st, a, B)
                           : launch_sep<bf16_t, 8, 16, 64, false, 512, 0, true>(st, a, B);
     }
@@ -1008,8 +1032,9 @@ extern "C" int effdet_sepconv_fused(
 
 // One MetaHead layer for all levels (effdet/efficientdet.py:655-676): the previous layer's batch-statistics BN arrives as
 // in_scale / in_shift [rows][F] (row in_affine_row[level]; null for the first layer) applied before the SiLU, the conv
-// output (+ bias) is written raw, and its per-channel sums / sums of squares go to stat_partial
-// [B][effdet_sepconv_tiles][2][N] for effdet_bn_batch_stats.  dw_out (optional, per level [B, H*W, F]) receives the
+// output (+ bias) is written raw, and per workgroup (tile) and channel a pivot (the tile's first pixel), the sum of q - pivot
+// and the sum of (q - pivot)^2 over the tile's pixels inside the map go to stat_partial [B][effdet_sepconv_tiles][3][N] for
+// effdet_bn_batch_stats.  dw_out (optional, per level [B, H*W, F]) receives the
 // depthwise output (`x_pred`, what ret_activs returns).
 extern "C" int effdet_sepconv_meta(
     void* stream, int dtype, int B, int nlevels, const int* level_hw,
@@ -1043,28 +1068,41 @@ extern "C" int effdet_sepconv_tiles(int dtype, int nlevels, const int* level_hw,
 namespace {
 struct BnStatArgs {
     const float* partial; int B, tiles_total, N;
-    int nlevels; int tile_begin[6]; int count[5];       // pixels per level (B*H*W)
+    int nlevels; int tile_begin[6];
+    int H[5], W[5], TH, TW;                              // level sizes and the tile of the launch that wrote `partial`
     const float* weight; const float* bias; int param_row[5];
     float eps; float* out_scale; float* out_shift;       // [nlevels][N]
 };
 
-// F.batch_norm(training=True) of one (level, layer): mean / biased variance over B*H*W from the per-workgroup sums
-// (fixed order, double accumulation), folded with the affine parameters into scale / shift for the next layer's load
+// F.batch_norm(training=True) of one (level, layer): mean / biased variance over B*H*W from the per-workgroup shifted sums.
+// Each tile gives (count, mean = pivot + s / count, M2 = q - s^2 / count) - the count follows from the level size and the
+// tile's position - and the tiles are merged in a fixed order by Chan's update in double: no difference of large numbers
+// anywhere.  Folded with the affine parameters into scale / shift for the next layer's load.
 __global__ __launch_bounds__(256) void bn_batch_stats_kernel(BnStatArgs p) {
     const int l = blockIdx.x;
+    const int tiles_x = (p.W[l] + p.TW - 1) / p.TW;
     for (int n = threadIdx.x; n < p.N; n += 256) {
-        double s = 0.0, q = 0.0;
+        double mean = 0.0, m2 = 0.0, cnt = 0.0;
         for (int b = 0; b < p.B; ++b)
             for (int t = p.tile_begin[l]; t < p.tile_begin[l + 1]; ++t) {
-                const float* row = p.partial + (((long long)b * p.tiles_total + t) * 2) * p.N;
-                s += (double)row[n]; q += (double)row[p.N + n];
+                const int ty = (t - p.tile_begin[l]) / tiles_x, tx = (t - p.tile_begin[l]) % tiles_x;
+                const int th = p.H[l] - ty * p.TH < p.TH ? p.H[l] - ty * p.TH : p.TH;
+                const int tw = p.W[l] - tx * p.TW < p.TW ? p.W[l] - tx * p.TW : p.TW;
+                const double c = (double)(th * tw);
+                const float* row = p.partial + (((long long)b * p.tiles_total + t) * 3) * p.N;
+                const double s = (double)row[p.N + n], q = (double)row[2 * (long long)p.N + n];
+                const double tm = (double)row[n] + s / c;
+                double tq = q - s * s / c; if (tq < 0.0) tq = 0.0;
+                const double tot = cnt + c, d = tm - mean;
+                mean += d * (c / tot);
+                m2 += tq + d * d * (cnt * c / tot);
+                cnt = tot;
             }
-        const double mean = s / p.count[l];
-        double var = q / p.count[l] - mean * mean; if (var < 0.0) var = 0.0;
+        const double var = m2 / cnt;
         const float w = p.weight[(long long)p.param_row[l] * p.N + n], bb = p.bias[(long long)p.param_row[l] * p.N + n];
-        const float sc = w / sqrtf((float)var + p.eps);
-        p.out_scale[(long long)l * p.N + n] = sc;
-        p.out_shift[(long long)l * p.N + n] = bb - (float)mean * sc;
+        const double sc = (double)w / sqrt(var + (double)p.eps);
+        p.out_scale[(long long)l * p.N + n] = (float)sc;
+        p.out_shift[(long long)l * p.N + n] = (float)((double)bb - mean * sc);
     }
 }
 }  // namespace
@@ -1074,13 +1112,16 @@ extern "C" int effdet_bn_batch_stats(void* stream, int dtype, const float* parti
                                      float* out_scale, float* out_shift) {
     EFFDET_ENTER();
     if (!partial || !level_hw || !weight || !bias || !param_row || !out_scale || !out_shift || B <= 0 || N <= 0 || nlevels < 1 || nlevels > 5) return EFFDET_EINVAL;
+    for (int l = 0; l < nlevels; ++l) if (level_hw[2 * l] <= 0 || level_hw[2 * l + 1] <= 0) return EFFDET_EINVAL;
     BnStatArgs a; a.partial = partial; a.B = B; a.N = N; a.nlevels = nlevels; a.weight = weight; a.bias = bias; a.eps = eps;
     a.out_scale = out_scale; a.out_shift = out_shift;
     int tb[5];
     const int tiles = effdet_sepconv_tiles(dtype, nlevels, level_hw, tb);
     if (tiles <= 0) return EFFDET_EINVAL;
     a.tiles_total = tiles;
-    for (int l = 0; l < nlevels; ++l) { a.tile_begin[l] = tb[l]; a.count[l] = B * level_hw[2 * l] * level_hw[2 * l + 1]; a.param_row[l] = param_row[l]; }
+    a.TH = 8; a.TW = dtype == 0 ? 8 : 16;                // the tile of effdet_sepconv_tiles / of the META launch
+    for (int l = 0; l < nlevels; ++l) { a.tile_begin[l] = tb[l]; a.H[l] = level_hw[2 * l]; a.W[l] = level_hw[2 * l + 1]; a.param_row[l] = param_row[l]; }
+    for (int l = nlevels; l < 5; ++l) { a.H[l] = a.W[l] = 1; a.param_row[l] = 0; }
     a.tile_begin[nlevels] = tiles;
     hipLaunchKernelGGL(bn_batch_stats_kernel, dim3(nlevels), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return effdet_check_launch();

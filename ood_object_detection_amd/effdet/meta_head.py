@@ -6,7 +6,10 @@ predict conv to one logit per anchor.  `fast_weights` (the MAML inner-loop copie
 module's own parameters in the reference's list order; `ret_activs` returns the predict layer's depthwise output.
 
 HIP path: one `effdet_sepconv_meta` launch per layer for all levels, `effdet_bn_batch_stats` in between (the batch
-statistics are folded into a per-level scale / shift that the next layer applies while loading its halo tile).
+statistics are folded into a per-level scale / shift that the next layer applies while loading its halo tile).  The variance
+comes from per-tile sums shifted by a pivot sample and merged by Chan's update in double ("MetaHead widths and
+batch statistics").  Widths: every `fpn_channels` that is a multiple of 8 up to 288 (d0 - d5); 384 and more are refused
+with a RuntimeError by the first layer's call.
 With grad mode on and trainable weights / inputs the forward is the differentiable float32 path (effdet/meta_ops.py: autograd
 primitives on the training kernels, differentiable twice - the `create_graph=True` inner gradient of infer.py:658 and the outer
 backward through it; `first_order = True` selects the single-node backward of effdet/meta_grad.py instead)."""
@@ -122,7 +125,7 @@ class MetaHead(nn.Module):
         ybuf = [torch.empty(B, P, F, dtype=dtype, device=dev) for _ in range(2)]
         out = torch.empty(B, P, A, dtype=dtype, device=dev)
         tiles = lib.effdet_sepconv_tiles(dt, nl, c_hw, None)
-        partial = torch.empty(B, tiles, 2, F, dtype=torch.float32, device=dev)
+        partial = torch.empty(B, tiles, 3, F, dtype=torch.float32, device=dev)      # per tile: pivot | sum (q - pivot) | sum (q - pivot)^2
         sc = torch.empty(nl, F, dtype=torch.float32, device=dev)
         sh = torch.empty(nl, F, dtype=torch.float32, device=dev)
         rows = (ctypes.c_int * nl)(*range(nl))

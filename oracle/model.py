@@ -335,30 +335,31 @@ def ood_scores(cls_outs, num_classes):
 
 
 def meta_head_forward(conv_dw_rep, conv_pw_rep, conv_pb_rep, bn_rep_w, bn_rep_b, predict, x, level_offset=0,
-                      predict_class=None, eps=1e-5):
+                      predict_class=None, eps=1e-5, dtype=torch.float32):
     """MetaHead.forward (effdet/efficientdet.py:636-695) with explicit weight lists in the reference's order
     (bn lists are level-major: index level * num_layers + rep).  Returns (outputs, x_pred activations[, class_outputs]).
     Pinned: tools/make_golden.py instantiates the reference class on the CPU (its `.to('cuda')` calls neutralised in that
     script only) and tests/golden/meta_nets.npz holds its outputs; tests/test_oracle_golden.py checks this restatement
-    against them."""
+    against them.  `dtype=torch.float64` runs the same expressions in double: the yardstick the kernels are measured against
+    where float32's own rounding would be part of the error (tests/test_meta_head_widths_*.py)."""
     num_layers = len(conv_dw_rep)
     outputs, activs, class_outputs = [], [], []
     for level in range(level_offset, len(x)):
-        x_level = x[level].float()
+        x_level = x[level].to(dtype)
         bn_w_lev = bn_rep_w[level * num_layers:(level + 1) * num_layers]
         bn_b_lev = bn_rep_b[level * num_layers:(level + 1) * num_layers]
         for conv_dw, conv_pw, conv_pb, bn_w, bn_b in zip(conv_dw_rep, conv_pw_rep, conv_pb_rep, bn_w_lev, bn_b_lev):
             x_level = F.pad(x_level, (1, 1, 1, 1))
-            x_level = F.conv2d(x_level, conv_dw.float(), groups=conv_dw.shape[0], padding=(0, 0))
-            x_level = F.conv2d(x_level, conv_pw.float(), bias=conv_pb.float())
-            x_level = F.batch_norm(x_level, None, None, bn_w.float(), bn_b.float(), training=True, eps=eps)
+            x_level = F.conv2d(x_level, conv_dw.to(dtype), groups=conv_dw.shape[0], padding=(0, 0))
+            x_level = F.conv2d(x_level, conv_pw.to(dtype), bias=conv_pb.to(dtype))
+            x_level = F.batch_norm(x_level, None, None, bn_w.to(dtype), bn_b.to(dtype), training=True, eps=eps)
             x_level = x_level * torch.sigmoid(x_level)
         x_pred = F.pad(x_level, (1, 1, 1, 1))
-        x_pred = F.conv2d(x_pred, predict[0].float(), groups=predict[0].shape[0])
+        x_pred = F.conv2d(x_pred, predict[0].to(dtype), groups=predict[0].shape[0])
         activs.append(x_pred)
-        outputs.append(F.conv2d(x_pred, predict[1].float(), bias=predict[2].float()))
+        outputs.append(F.conv2d(x_pred, predict[1].to(dtype), bias=predict[2].to(dtype)))
         if predict_class is not None:
-            class_outputs.append(F.conv2d(x_pred, predict_class[0].float(), bias=predict_class[1].float()))
+            class_outputs.append(F.conv2d(x_pred, predict_class[0].to(dtype), bias=predict_class[1].to(dtype)))
     return (outputs, activs, class_outputs) if predict_class is not None else (outputs, activs)
 
 

@@ -67,3 +67,30 @@ def sepconv(dtype, B, level_hw, level_inputs, fuse_mode, fw, den, pre_act, taps,
                                   den, pre_act, ptr(taps), ptr(wq), ptr(scale), ptr(shift), c_aff, post_act, F, N,
                                   c_out, c_ostr, *oa)
     assert rc == 0, rc
+
+
+def meta_layer_with_stats(x, taps, pw, bias, bn_w, bn_b, eps=1e-5):
+    """One MetaHead layer as effdet/meta_head.py drives it: effdet_sepconv_meta (no input affine, no activation) with
+    stat_partial set, then effdet_bn_batch_stats.  x: list of NHWC tensors [B, H, W, F]; taps [9][F] float32; pw [N][F] in x's
+    dtype; bias [N], bn_w / bn_b [levels][N] float32.  Returns the raw outputs [B, H, W, N] and scale / shift [levels][N]."""
+    lib = _lib.load()
+    arr = lambda ct, v: (ct * len(v))(*v)
+    dev, dtype = x[0].device, x[0].dtype
+    B, F, N, nl = x[0].shape[0], x[0].shape[3], pw.shape[0], len(x)
+    hw = [(t.shape[1], t.shape[2]) for t in x]
+    c_hw = arr(ctypes.c_int, [v for p in hw for v in p])
+    tiles = lib.effdet_sepconv_tiles(DT[dtype], nl, c_hw, None)
+    assert tiles > 0
+    partial = torch.zeros(B, tiles, 3, N, dtype=torch.float32, device=dev)
+    y = [torch.empty(B, h, w, N, dtype=dtype, device=dev) for h, w in hw]
+    scale = torch.empty(nl, N, dtype=torch.float32, device=dev)
+    shift = torch.empty(nl, N, dtype=torch.float32, device=dev)
+    rows = arr(ctypes.c_int, list(range(nl)))
+    rc = lib.effdet_sepconv_meta(stream(dev), DT[dtype], B, nl, c_hw, arr(ctypes.c_void_p, [t.data_ptr() for t in x]),
+                                 arr(ctypes.c_longlong, [t.stride(0) for t in x]), None, None, rows, 0, ptr(taps), ptr(pw), ptr(bias), F, N,
+                                 arr(ctypes.c_void_p, [t.data_ptr() for t in y]), arr(ctypes.c_longlong, [t.stride(0) for t in y]),
+                                 ptr(partial), None, None)
+    assert rc == 0, rc
+    rc = lib.effdet_bn_batch_stats(stream(dev), DT[dtype], ptr(partial), B, nl, c_hw, N, ptr(bn_w), ptr(bn_b), rows, eps, ptr(scale), ptr(shift))
+    assert rc == 0, rc
+    return y, scale, shift
