@@ -557,6 +557,35 @@ int effdet_adam_clip_step(void* stream, float* p, const float* g, float* m, floa
 int effdet_adam_clip_step_dev(void* stream, float* p, const float* g, float* m, float* v, long long n,
                               float lr, float beta1, float beta2, float eps, const float* bc_dev, float max_norm, const float* sqnorm);
 
+/* ---- grouped optimizer (group_optim.hip): clip_grad_norm_ per clip domain + torch.optim.Adam / SGD with parameter groups ------
+ * Flat float32 buffers of n_floats values (a multiple of 16) for parameters, gradients and state (Adam: state1 = exp_avg,
+ * state2 = exp_avg_sq; SGD: state1 = momentum buffer, state2 ignored).  A parameter tensor is a segment: start and padded length
+ * multiples of 16 floats, padding zero.  Device tables (int32), built by optim.plan_layout:
+ *   pieces     [n_pieces][4]      {offset, length (both in 16-byte units, length <= effdet_group_piece_floats() / 4), segment, 0};
+ *                                 a piece lies inside one segment; the first n_norm_pieces pieces are those of the clip domains,
+ *                                 domain after domain
+ *   seg_group  [n_segments]       group of the segment, -1: in no group (it only contributes to its domain's norm)
+ *   dom_ranges [n_domains + 1][4] {first piece, end piece, first segment, end segment} per domain; last row: segments in no domain
+ *   dyn        what may change between steps: n_groups rows of 16 words {double lr, beta1, beta2; float weight_decay, eps,
+ *              float(1 - beta1), float(beta2), float(1 - beta2), momentum; int nesterov; 3 unused}, then float max_norm[n_domains],
+ *              then int present[n_segments]
+ * and device state: step [n_segments] int32 (Adam: updates so far; SGD: 1 once the momentum buffer exists), advanced by the
+ * kernels; seg_const [n_segments][4] 32-bit words (workspace: three floats and an integer flag word per segment, 16-byte aligned),
+ * partial [max(1, n_norm_pieces)], norms [max(1, n_domains)] floats (workspace / output).
+ * Per domain: norms[d] = sqrt(sum g^2) over its present segments, coef = min(1, max_norm / (norm + 1e-6)), applied to the gradient
+ * value inside the update (the gradient buffer is not modified).  A segment that is not present, or in no group, keeps every byte
+ * of its parameters, state and step count.  kind 0: Adam, 1: SGD (momentum, optional Nesterov, dampening 0); both with coupled
+ * weight decay, in the operation order of torch's single-tensor paths.  Three launches, fixed-order sums, no atomics, nothing
+ * read back: capturable.  effdet_group_norms: the norms alone (needs n_domains > 0). */
+long long effdet_group_piece_floats(void);
+int effdet_group_norms(void* stream, const float* grad, long long n_floats, const int* pieces, int n_pieces, int n_norm_pieces,
+                       const int* seg_group, int n_segments, const int* dom_ranges, int n_domains, const int* dyn, int n_groups,
+                       float* partial, float* norms);
+int effdet_group_step(void* stream, int kind, float* param, const float* grad, float* state1, float* state2, long long n_floats,
+                      const int* pieces, int n_pieces, int n_norm_pieces, const int* seg_group, int n_segments,
+                      const int* dom_ranges, int n_domains, const int* dyn, int n_groups, int* step, float* seg_const,
+                      float* partial, float* norms);
+
 /* ---- detection evaluation (the effdet/evaluation package, driven by pretrain.py:246-252) ----------------------- */
 
 /* Per-image greedy matching (per_image_evaluation.py:377-405) + CorLoc (:143-176).  det [B,max_det,6] rows

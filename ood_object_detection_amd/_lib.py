@@ -63,6 +63,11 @@ SIGNATURES = {
                                       c_int, c_float, c_void_p]),
     'effdet_adam_clip_step_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_float, c_float, c_float, c_float,
                                           c_void_p, c_float, c_void_p]),
+    'effdet_group_piece_floats': (c_ll, []),
+    'effdet_group_norms': (c_int, [c_void_p, c_void_p, c_ll, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p]),
+    'effdet_group_step': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_int, c_int, c_void_p, c_int,
+                                  c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_novelty_score': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int,
                                      c_void_p, c_void_p, c_void_p]),
     'effdet_ood_image_score': (c_int, [c_void_p, c_void_p, c_int, c_ll, c_void_p]),

@@ -28,10 +28,13 @@ def set_bn_eval(module):
 
 class PretrainStep(object):
     def __init__(self, model, lr=1e-3, max_grad_norm=10.0, alpha=0.15, box_loss_weight=50.0, freeze_bn=False,
-                 labeler=True, graph=False, graph_warmup=2):
+                 labeler=True, graph=False, graph_warmup=2, optimizer=None):
         """graph=True: after `graph_warmup` eager iterations the whole iteration (zero_grad, forward, loss, backward and -
         single GPU - clip + Adam) is captured into one hipGraph and replayed; the ~5 000 launches of a step then cost one
-        submission.  Shapes must stay fixed; labels are assigned eagerly and copied into the graph's static buffers."""
+        submission.  Shapes must stay fixed; labels are assigned eagerly and copied into the graph's static buffers.
+        optimizer: an `optim.GroupedOptimizer` over (some of) the model's parameters, used in place of the FlatAdam that is
+        otherwise built from `lr` / `max_grad_norm` (parameter groups, clip domains, Nesterov SGD: optim.script_param_groups);
+        'grad_norm' is then its 1-d tensor of per-domain norms."""
         from .effdet.anchors import Anchors, AnchorLabeler
         from .effdet.config import set_config_writeable
         from .effdet.loss import DetectionLoss
@@ -45,7 +48,8 @@ class PretrainStep(object):
         set_config_writeable(cfg)
         cfg.alpha, cfg.box_loss_weight = alpha, box_loss_weight
         self.loss_fn = DetectionLoss(cfg)
-        self.opt = FlatAdam(model.parameters(), lr=lr, max_grad_norm=max_grad_norm)
+        self._grouped = optimizer is not None
+        self.opt = optimizer if self._grouped else FlatAdam(model.parameters(), lr=lr, max_grad_norm=max_grad_norm)
         self.anchors = Anchors.from_config(cfg).to(model.backbone.conv_stem.weight.device)
         self.labeler = AnchorLabeler(self.anchors, cfg.num_classes, match_threshold=0.5) if labeler else None
         self.num_levels = cfg.num_levels
@@ -125,13 +129,15 @@ class PretrainStep(object):
             class_out, box_out = model(feats, mode='fpn_and_head')
             loss, class_loss, box_loss = self.loss_fn(class_out, box_out, s_cls, s_box, s_np)
             loss.backward()
-            norm = opt.step_captured() if self.world == 1 else None
+            # a GroupedOptimizer's step() records only its launches under capture: its step counts live on the device
+            step_captured = opt.step if self._grouped else opt.step_captured
+            norm = step_captured() if self.world == 1 else None
             outs = [loss.detach(), class_loss, box_loss, norm]
         g2 = None
         if self.world > 1:
             g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g2, pool=g1.pool()):
-                outs[3] = opt.step_captured()
+                outs[3] = step_captured()
         del feats, class_out, box_out, loss
         self._cap = (g1, g2, (sx, s_cls, s_box, s_np), outs)
 
@@ -156,7 +162,10 @@ class PretrainStep(object):
             for d, t in zip(s_box, box_t):
                 d.copy_(t)
         s_np.copy_(npos)
-        self.opt.advance()
+        if self._grouped:
+            self.opt.refresh()                  # learning rates edited since the last replay reach the device tables
+        else:
+            self.opt.advance()
         g1.replay()
         if g2 is not None:
             self._allreduce(time_allreduce)
