@@ -183,6 +183,29 @@ int effdet_mbconv_expand_dw_gated(void* stream, int dtype, const void* X, const 
                                   const float* s2, const float* t2, float* pool_partial,
                                   int B, int H, int W, int Cin, int mid, int k, int stride);
 int effdet_mbconv_gated_tiles_per_image(int dtype, int H, int W, int Cin, int mid, int k, int stride);
+/* Host-only plan query (launches nothing): which fused form and which geometry effdet_mbconv_expand_dw (gated == 0) or
+ * effdet_mbconv_expand_dw_gated (gated != 0) runs for this block - answered by the launcher's own planning function.
+ * EFFDET_PAD_SYMMETRIC in dtype is ignored (no geometry depends on the padding convention).  Fills min(n,
+ * EFFDET_MBCONV_PLAN_INTS) ints of `out` and returns that count, or EFFDET_EINVAL (out == NULL, n <= 0, or Cin / mid not a
+ * positive multiple of 8, which the launch refuses before it plans; the two tiles_per_image queries do not make that check and
+ * answer for the geometry alone).  Slots, unused ones 0:
+ *    0  form: 0 none (the caller runs expand GEMM + depthwise), 1 rolling window, 2 shared-X rolling window ("wide"),
+ *             3 band x channel slice ("deep"), 4 spatial tiles ("front")
+ *    1  parts: pool-partial rows per image (= effdet_mbconv[_gated]_tiles_per_image; 0 for form 0)
+ *    2  nkc: 32-channel K chunks of Cin                         (roll, wide)
+ *    3  MT: 16-pixel input tiles per strip row                  (roll, wide)
+ *    4  NO: 16-pixel output tiles per strip row                 (roll, wide)
+ *    5  NJ: channel tiles per wave (roll) / NPL: 16-byte X pieces a lane stages per row (wide)
+ *    6  TWo: strip width in output pixels                       (roll, wide)
+ *    7  nstrips                                                 (roll, wide)
+ *    8  band_rows: output rows per band                         (roll, wide, deep)
+ *    9  nbands                                                  (roll, wide, deep)
+ *   10  waves per workgroup                                     (roll, wide)
+ *   11  dynamic LDS bytes of a workgroup                        (every form)
+ *   12  nchunks: 64-channel slices of mid                       (deep)
+ *   13  TH, 14 TW: output tile; 15 tiles_x, 16 tiles_y          (front) */
+#define EFFDET_MBCONV_PLAN_INTS 17
+int effdet_mbconv_plan_describe(int dtype, int H, int W, int Cin, int mid, int k, int stride, int gated, int* out, int n);
 
 /* SqueezeExcite gate: mean -> fc(C->R)+SiLU -> fc(R->C) -> sigmoid.  W1: [R][C] (conv_reduce weight),
  * W2t: [R][C] (conv_expand weight TRANSPOSED, so that consecutive threads read consecutive channels). */

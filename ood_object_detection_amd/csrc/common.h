@@ -279,10 +279,16 @@ template <typename T> DEV void row_store4(void* row, int ch, const f32x4 v) {
     }
 }
 
+// What the plan query (effdet_mbconv_plan_describe, mbconv.hip) reports of a rolling-window geometry: K-chunks, input / output tiles
+// (16 px) per strip row, channel tiles per wave (roll: NJ) or 16-byte X pieces a lane stages per row (wide: NPL), strip width in
+// output pixels, strips, rows per band, bands, waves per workgroup, dynamic LDS bytes
+struct MbRollWideInfo { int nkc, mt, no, nj_npl, two, nstrips, band_rows, nbands, waves, lds; };
+
 // mbconv_roll.hip (internal, hidden from the C ABI): rolling-window form of the fused MBConv front half, bf16 only.
 // parts = SE pool partial rows per image when the form applies to the geometry, 0 otherwise.
 // pair != 0: dtype 2 (two-term bf16) instead of bfloat16
 __attribute__((visibility("hidden"))) int effdet_mbconv_roll_parts(int H, int W, int Cin, int mid, int k, int stride, int pair = 0);
+__attribute__((visibility("hidden"))) int effdet_mbconv_roll_geometry(int H, int W, int Cin, int mid, int k, int stride, int pair, MbRollWideInfo* o);
 __attribute__((visibility("hidden"))) int effdet_mbconv_roll_launch(hipStream_t st, const void* X, const float* in_gate, void* Y, const void* W1, const float* s1, const float* t1,
                               const float* taps, const float* s2, const float* t2, float* pool_partial,
                               int B, int H, int W, int Cin, int mid, int k, int stride, int pair = 0, int sym = 0);
@@ -290,6 +296,7 @@ __attribute__((visibility("hidden"))) int effdet_mbconv_roll_launch(hipStream_t 
 // mbconv_wide.hip (internal): rolling-window form for inputs wider than 64 channels (X rows shared by a workgroup through an
 // LDS ring), bf16 only; parts = SE pool partial rows per image when the form applies to the geometry, 0 otherwise
 __attribute__((visibility("hidden"))) int effdet_mbconv_wide_parts(int H, int W, int Cin, int mid, int k, int stride, int pair = 0);
+__attribute__((visibility("hidden"))) int effdet_mbconv_wide_geometry(int H, int W, int Cin, int mid, int k, int stride, int pair, MbRollWideInfo* o);
 __attribute__((visibility("hidden"))) int effdet_mbconv_wide_launch(hipStream_t st, const void* X, void* Y, const void* W1, const float* s1, const float* t1,
                               const float* taps, const float* s2, const float* t2, float* pool_partial,
                               int B, int H, int W, int Cin, int mid, int k, int stride, int pair = 0, int sym = 0);

@@ -823,7 +823,7 @@ int launch_front(hipStream_t st, MbArgs& a, const Geometry& g) {
 enum MbForm { MB_NONE, MB_ROLL, MB_WIDE, MB_DEEP, MB_FRONT };
 
 // parts: SE pool-partial rows per image the launch writes (what the caller sizes `partial` by and hands the SE gate as nblk)
-struct MbPlan { MbForm form; int parts; DeepGeometry deep; Geometry tile; };
+struct MbPlan { MbForm form; int parts; DeepGeometry deep; Geometry tile; MbRollWideInfo rw; };
 
 // The one place that decides which fused form runs a block.  Forms, in order of preference:
 //   rolling window (mbconv_roll.hip; bf16 and two-term bf16)  ->  rolling window with X shared through LDS (mbconv_wide.hip;
@@ -834,8 +834,8 @@ MbPlan mbconv_plan(int dtype, int H, int W, int Cin, int mid, int k, int stride,
     if (H <= 0 || W <= 0 || Cin <= 0 || mid <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2) || dtype < 0 || dtype > 2) return p;
     if (dtype >= 1) {
         const int pair = dtype == 2;
-        if ((p.parts = effdet_mbconv_roll_parts(H, W, Cin, mid, k, stride, pair)) > 0) { p.form = MB_ROLL; return p; }
-        if (!gated && (p.parts = effdet_mbconv_wide_parts(H, W, Cin, mid, k, stride, pair)) > 0) { p.form = MB_WIDE; return p; }
+        if ((p.parts = effdet_mbconv_roll_geometry(H, W, Cin, mid, k, stride, pair, &p.rw)) > 0) { p.form = MB_ROLL; return p; }
+        if (!gated && (p.parts = effdet_mbconv_wide_geometry(H, W, Cin, mid, k, stride, pair, &p.rw)) > 0) { p.form = MB_WIDE; return p; }
         p.parts = 0;
         if (pair) return p;
     }
@@ -863,6 +863,34 @@ extern "C" int effdet_mbconv_gated_tiles_per_image(int dtype, int H, int W, int 
     (void)take_pad_flag(dtype);
     const MbPlan p = mbconv_plan(dtype, H, W, Cin, mid, k, stride, true);
     return p.form != MB_NONE ? p.parts : EFFDET_EINVAL;
+}
+
+// Host-only: what mbconv_plan() - the launcher's own decision - chose for a geometry; nothing is launched.  Slots (unused ones 0):
+//   0 form (0 none, 1 roll, 2 wide, 3 deep, 4 front)   1 parts (pool-partial rows per image)
+//   roll / wide:  2 nkc   3 MT   4 NO   5 NJ (roll) or NPL (wide)   6 TWo   7 nstrips   10 waves per workgroup
+//   roll / wide / deep:  8 band_rows   9 nbands          every form:  11 dynamic LDS bytes
+//   deep:  12 nchunks          front:  13 TH   14 TW   15 tiles_x   16 tiles_y
+extern "C" int effdet_mbconv_plan_describe(int dtype, int H, int W, int Cin, int mid, int k, int stride, int gated, int* out, int n) {
+    if (!out || n <= 0) return EFFDET_EINVAL;
+    (void)take_pad_flag(dtype);                          // (no geometry depends on the padding convention)
+    if (Cin <= 0 || Cin % 8 || mid <= 0 || mid % 8) return EFFDET_EINVAL;      // what the launcher refuses before it plans
+    const MbPlan p = mbconv_plan(dtype, H, W, Cin, mid, k, stride, gated != 0);
+    int v[EFFDET_MBCONV_PLAN_INTS] = {0};
+    v[0] = (int)p.form; v[1] = p.form != MB_NONE ? p.parts : 0;
+    if (p.form == MB_ROLL || p.form == MB_WIDE) {
+        const MbRollWideInfo& g = p.rw;
+        v[2] = g.nkc; v[3] = g.mt; v[4] = g.no; v[5] = g.nj_npl; v[6] = g.two; v[7] = g.nstrips;
+        v[8] = g.band_rows; v[9] = g.nbands; v[10] = g.waves; v[11] = g.lds;
+    } else if (p.form == MB_DEEP) {
+        v[8] = p.deep.band_rows; v[9] = p.deep.nbands; v[11] = (int)p.deep.lds; v[12] = p.deep.nchunks;
+    } else if (p.form == MB_FRONT) {
+        const int Ho = same_out(H, stride), Wo = same_out(W, stride);
+        v[11] = (int)p.tile.lds; v[13] = p.tile.TH; v[14] = p.tile.TW;
+        v[15] = (Wo + p.tile.TW - 1) / p.tile.TW; v[16] = (Ho + p.tile.TH - 1) / p.tile.TH;
+    }
+    const int m = n < EFFDET_MBCONV_PLAN_INTS ? n : EFFDET_MBCONV_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = v[i];
+    return m;
 }
 
 static int mbconv_common(void* stream, int dtype, const void* X, const float* in_gate, void* Y, const void* W1,

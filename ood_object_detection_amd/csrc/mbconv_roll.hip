@@ -607,6 +607,14 @@ int effdet_mbconv_roll_parts(int H, int W, int Cin, int mid, int k, int stride, 
     return g.kern ? g.nstrips * g.nbands : 0;
 }
 
+// internal: the geometry pick_roll chose, for mbconv.hip's plan query (nothing is launched).  Returns parts like the function above
+int effdet_mbconv_roll_geometry(int H, int W, int Cin, int mid, int k, int stride, int pair, MbRollWideInfo* o) {
+    const RollGeometry g = pick_roll(H, W, Cin, mid, k, stride, pair != 0);
+    if (!g.kern) return 0;
+    *o = MbRollWideInfo{g.nkc, g.IWa / 16, (g.TWo + 15) / 16, g.nj, g.TWo, g.nstrips, g.band_rows, g.nbands, g.wpg, (int)g.lds};
+    return g.nstrips * g.nbands;
+}
+
 int effdet_mbconv_roll_launch(hipStream_t st, const void* X, const float* in_gate, void* Y, const void* W1, const float* s1, const float* t1,
                               const float* taps, const float* s2, const float* t2, float* pool_partial,
                               int B, int H, int W, int Cin, int mid, int k, int stride, int pair, int sym) {

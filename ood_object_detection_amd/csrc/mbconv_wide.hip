@@ -585,6 +585,14 @@ int effdet_mbconv_wide_parts(int H, int W, int Cin, int mid, int k, int stride, 
     return g.kern ? g.nstrips * g.nbands : 0;
 }
 
+// internal: the geometry pick_wide chose, for mbconv.hip's plan query (nothing is launched).  Returns parts like the function above
+int effdet_mbconv_wide_geometry(int H, int W, int Cin, int mid, int k, int stride, int pair, MbRollWideInfo* o) {
+    const WideGeometry g = pick_wide(H, W, Cin, mid, k, stride, pair != 0);
+    if (!g.kern) return 0;
+    *o = MbRollWideInfo{g.nkc, g.IWa / 16, (g.TWo + 15) / 16, g.npl, g.TWo, g.nstrips, g.band_rows, g.nbands, g.nw, (int)g.lds};
+    return g.nstrips * g.nbands;
+}
+
 int effdet_mbconv_wide_launch(hipStream_t st, const void* X, void* Y, const void* W1, const float* s1, const float* t1,
                               const float* taps, const float* s2, const float* t2, float* pool_partial,
                               int B, int H, int W, int Cin, int mid, int k, int stride, int pair, int sym) {
