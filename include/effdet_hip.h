@@ -741,6 +741,38 @@ int effdet_episode_supp_loss_backward2(void* stream, const float* embds, const f
                                        float* workspace, long long workspace_floats, float* d_grad, float* h_embds,
                                        float* h_confs, float* h_logits, float* h_dots);
 
+/* The meta phase's inner update (infer.py:660-678) for a list of n_tensors float32 tensors in one launch:
+ *     out[t][i] = p[t][i] - (lr[lr_index[t]] * g[t][i]),   i < count[t],
+ * the product and the difference rounded separately, as torch's `par - par_lr * inner_grad`.  p, g, out, count, lr_index are
+ * HOST arrays of n_tensors entries (device pointers to contiguous memory in the first three); lr_ptr / lr_val are host arrays
+ * of n_lr entries: step size k is read on the device from lr_ptr[k] at the time the kernel runs, or is lr_val[k] when
+ * lr_ptr[k] is NULL.  Everything travels by value in the kernel arguments, so the launch captures into a graph and a step
+ * size changed in place is seen by the next replay.  Any 4-byte aligned pointers; 16-byte accesses are used for a tensor
+ * only when its three pointers allow them.  The output tensors must not overlap the inputs or each other.
+ * Limits: 1 <= n_tensors <= effdet_inner_update_max_tensors() (32), 1 <= n_lr <= effdet_inner_update_max_step_sizes() (16),
+ * 1 <= count[t] <= 2^30, 0 <= lr_index[t] < n_lr; EINVAL otherwise or for a NULL pointer (lr_ptr[k] excepted).  Longer lists
+ * are split by the caller.
+ * Backward, for the cotangents grad_out[t] of out[t]:
+ *     dg[t][i] = -(lr[lr_index[t]] * grad_out[t][i])            (dg[t] == NULL: not wanted),
+ *     dlr[k]   = -sum_{t: lr_index[t] == k} sum_i grad_out[t][i] * g[t][i]     (dlr == NULL: not wanted, no reduction runs);
+ * the gradient with respect to p[t] is grad_out[t] itself.  dlr [n_lr] floats are overwritten; a step size no tensor uses
+ * gets 0.  The sum is taken in float64 from the float32 inputs: per workgroup, then per step size in one ordered pass, and is
+ * rounded to float32 once; no atomics, two calls give the same bits.  At most two launches.  The workspace (8-byte aligned,
+ * size from the query below, -1: arguments outside the limits) holds the float64 totals [max_step_sizes] followed by the
+ * per-workgroup partials.  accumulate != 0 starts from the totals an earlier call left in the same workspace instead of from
+ * zero and writes dlr for both together - how a caller chains the pieces of a list longer than max_tensors with the same
+ * lr_ptr / lr_val table and still rounds once. */
+int effdet_inner_update_max_tensors(void);
+int effdet_inner_update_max_step_sizes(void);
+long long effdet_inner_update_workspace_doubles(int n_tensors, const long long* count);
+int effdet_inner_update(void* stream, int n_tensors, const void* const* p, const void* const* g, void* const* out,
+                        const long long* count, const int* lr_index, int n_lr, const void* const* lr_ptr,
+                        const float* lr_val);
+int effdet_inner_update_backward(void* stream, int n_tensors, const void* const* grad_out, const void* const* g,
+                                 void* const* dg, const long long* count, const int* lr_index, int n_lr,
+                                 const void* const* lr_ptr, const float* lr_val, double* workspace,
+                                 long long workspace_doubles, int accumulate, float* dlr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,6 +201,13 @@ SIGNATURES = {
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
                                                    c_void_p, c_void_p, c_void_p]),
+    'effdet_inner_update_max_tensors': (c_int, []),
+    'effdet_inner_update_max_step_sizes': (c_int, []),
+    'effdet_inner_update_workspace_doubles': (c_ll, [c_int, P(c_ll)]),
+    'effdet_inner_update': (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_void_p), P(c_ll), P(c_int), c_int, P(c_void_p),
+                                    P(c_float)]),
+    'effdet_inner_update_backward': (c_int, [c_void_p, c_int, P(c_void_p), P(c_void_p), P(c_void_p), P(c_ll), P(c_int), c_int,
+                                             P(c_void_p), P(c_float), c_void_p, c_ll, c_int, c_void_p]),
 }
 
 

@@ -7,11 +7,12 @@
     t = target_from_selection(proj_embds, conf.reshape(-1), out, dot_mult, dot_add)     # the same target, with autograd history
     loss = projection_losses(proj_embds, conf.reshape(-1), labs, cls_id, out, dot_mult, dot_add)   # infer.py:448-498, forward and backward
     supp = support_loss(proj_embds, conf.reshape(-1), cls_logits, out, dot_mult, dot_add)          # infer.py:645-658, differentiable twice
+    fast = inner_update(class_net.named_parameters(), inner_grad, learnable_lr)                    # infer.py:660-678, learnable step sizes
 
 float32 GPU tensors only, no CPU fallback.  Nothing here synchronises with the host and no allocation depends on a device value,
 so the whole chain can be captured in one `torch.cuda.graph`.  The n x n matrices of the script (`sim_mat`, `thresh_mat`,
 `weighted_sim`, `mask`, `sim_target`) are never formed: every use of them is rank-1 or n x m (see csrc/episode.hip,
-csrc/episode_loss.hip and csrc/episode_support.hip)."""
+csrc/episode_loss.hip and csrc/episode_support.hip; the inner update is csrc/inner_update.hip)."""
 import ctypes
 
 import torch
@@ -452,3 +453,178 @@ def support_loss(proj_embds, confs, cls_logits, sel, dot_mult, dot_add, sim_targ
     m, idx = _sel_indices(sel, dev, n, use_max, 'support_loss')
     loss, target = _SupportLoss.apply(proj_embds, confs, cls_logits, dot_mult, dot_add, idx, m, use_max, bool(thresh_grad))
     return {'loss': loss, 'target': target}
+
+
+def plan_inner_update(names, n_lr, only_final=False, separate_head=False):
+    """Which step size updates which `class_net` parameter, by the rule of infer.py:663-671 on the parameter's name: for every
+    name the index into `learnable_lr` (0 <= index < n_lr), or None for a parameter that passes through unchanged.  Pure host
+    code.  Pass through: 'bn_' in the name; only_final and 'predict_p' not in it; separate_head and 'predict_p' in it without
+    'sep'.  Otherwise 'predict_dw' takes learnable_lr[-2], 'predict_p' takes learnable_lr[-1] and everything else
+    learnable_lr[int(name[7])] (the layer digit of 'conv_dw0', 'conv_pw1', ...).  Python's negative indexing is part of the
+    rule - with only_final the script builds ONE step size and [-1] finds it - so the result is the index the script's
+    expression selects, normalised to [0, n_lr).  ValueError (naming the parameter) where the script's expression would raise
+    IndexError or ValueError: a list too short for the name, or a name without a digit at position 7."""
+    n_lr = int(n_lr)
+    if n_lr < 1:
+        raise ValueError('plan_inner_update: at least one step size is needed')
+    plan = []
+    for n in names:
+        if 'bn_' in n or (only_final and 'predict_p' not in n) or (separate_head and 'predict_p' in n and 'sep' not in n):
+            plan.append(None)
+            continue
+        if 'predict_dw' in n:
+            k = -2
+        elif 'predict_p' in n:
+            k = -1
+        else:
+            try:
+                k = int(n[7])
+            except (IndexError, ValueError):
+                raise ValueError('plan_inner_update: parameter %r has no layer digit at position 7 (infer.py:671)' % (n,)) from None
+        if not -n_lr <= k < n_lr:
+            raise ValueError('plan_inner_update: parameter %r selects learnable_lr[%d], but there are only %d step sizes' % (n, k, n_lr))
+        plan.append(k % n_lr)
+    return plan
+
+
+def _inner_update_launches(index, max_tensors):
+    """the positions 0 .. len(index) - 1 in runs of at most max_tensors: one launch each"""
+    return [range(s, min(s + max_tensors, len(index))) for s in range(0, len(index), max_tensors)]
+
+
+def _lr_table(lr_spec, lrs):
+    """lr_spec[k]: position of step size k among the tensors `lrs`, or its Python value -> the two host arrays of the C ABI"""
+    ptr = [lrs[v].data_ptr() if isinstance(v, int) else None for v in lr_spec]
+    val = [0.0 if isinstance(v, int) else v[0] for v in lr_spec]
+    return _ptrs(ptr), (ctypes.c_float * len(val))(*val)
+
+
+class _InnerUpdate(torch.autograd.Function):
+    """effdet_inner_update over the whole list; effdet_inner_update_backward is its (once-differentiable) backward.  The outer
+    loop calls plain .backward() and p - lr g is bilinear, so nothing of higher order is needed: the second-order terms of MAML
+    enter through g's own graph, which the cotangent dg reaches."""
+
+    @staticmethod
+    def forward(ctx, lr_spec, index, *tensors):
+        lib = _lib.load()
+        n_l, n = sum(isinstance(v, int) for v in lr_spec), len(index)
+        lrs, ps, gs = tensors[:n_l], tensors[n_l:n_l + n], tensors[n_l + n:]
+        dev = ps[0].device
+        pc = [p.detach().contiguous() for p in ps]
+        gc = [g.detach().contiguous() for g in gs]
+        outs = [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in pc]
+        lr_ptr, lr_val = _lr_table(lr_spec, lrs)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for run in _inner_update_launches(index, lib.effdet_inner_update_max_tensors()):
+            _lib.check(lib.effdet_inner_update(st, len(run), _ptrs([pc[t].data_ptr() for t in run]), _ptrs([gc[t].data_ptr() for t in run]),
+                                               _ptrs([outs[t].data_ptr() for t in run]), _lls([pc[t].numel() for t in run]),
+                                               _ints([index[t] for t in run]), len(lr_spec), lr_ptr, lr_val), 'effdet_inner_update')
+        ctx.lr_spec, ctx.index = lr_spec, index
+        ctx.lr_shapes = [t.shape for t in lrs]
+        ctx.save_for_backward(*lrs, *gc)             # detached aliases share the version counters: an in-place change raises
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grad_outs):
+        lib = _lib.load()
+        lr_spec, index = ctx.lr_spec, ctx.index
+        n_l, n = len(ctx.lr_shapes), len(index)
+        saved = ctx.saved_tensors
+        lrs, gc = saved[:n_l], saved[n_l:]
+        need = ctx.needs_input_grad[2:]
+        need_lr, need_p, need_g = need[:n_l], need[n_l:n_l + n], need[n_l + n:]
+        live = [t for t in range(n) if grad_outs[t] is not None]
+        d_lr, d_g = [None] * n_l, [None] * n
+        want_lr = any(need_lr)
+        if live and (want_lr or any(need_g[t] for t in live)):
+            dev = gc[0].device
+            G = {t: grad_outs[t].detach().to(dtype=torch.float32).contiguous() for t in live}
+            for t in live:
+                if need_g[t]:
+                    d_g[t] = torch.empty(gc[t].shape, dtype=torch.float32, device=dev)
+            lr_ptr, lr_val = _lr_table(lr_spec, lrs)
+            runs = [[live[i] for i in r] for r in _inner_update_launches(live, lib.effdet_inner_update_max_tensors())]
+            ws = ws_doubles = dlr = None
+            if want_lr:
+                ws_doubles = max(lib.effdet_inner_update_workspace_doubles(len(r), _lls([gc[t].numel() for t in r])) for r in runs)
+                ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev)
+                dlr = torch.empty(len(lr_spec), dtype=torch.float32, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            for i, r in enumerate(runs):            # one stream: a later run reuses the partials' space after the earlier one has added them up
+                _lib.check(lib.effdet_inner_update_backward(
+                    st, len(r), _ptrs([G[t].data_ptr() for t in r]), _ptrs([gc[t].data_ptr() for t in r]),
+                    _ptrs([d_g[t].data_ptr() if d_g[t] is not None else None for t in r]), _lls([gc[t].numel() for t in r]),
+                    _ints([index[t] for t in r]), len(lr_spec), lr_ptr, lr_val, ws.data_ptr() if want_lr else None,
+                    ws_doubles if want_lr else 0, 1 if i > 0 else 0, dlr.data_ptr() if want_lr else None), 'effdet_inner_update_backward')
+            if want_lr:
+                used = {index[t] for t in live}
+                for k, v in enumerate(lr_spec):
+                    if isinstance(v, int) and need_lr[v] and k in used:
+                        d_lr[v] = dlr[k].reshape(ctx.lr_shapes[v])
+        d_p = [grad_outs[t] if need_p[t] else None for t in range(n)]
+        return (None, None, *d_lr, *d_p, *d_g)
+
+
+def inner_update(named_params, inner_grad, learnable_lr, only_final=False, separate_head=False):
+    """infer.py:660-678, the MAML inner update, on the HIP kernels of csrc/inner_update.hip: one launch forward and at most two
+    backward for the whole list.  named_params: `class_net.named_parameters()` or any iterable of (name, tensor) - leaves or
+    earlier fast weights (the FLAGS.steps > 1 loop); inner_grad: the tuple `torch.autograd.grad(supp_class_loss, params,
+    allow_unused=True, create_graph=True)` returned, in the same order; learnable_lr: the step sizes, each a 0-d or 1-element
+    float32 GPU tensor (Parameter or not; read on the device when the kernel runs, so nothing synchronises and a captured graph
+    sees a value changed in place) or a Python number (travels by value, gets no gradient).  `plan_inner_update` chooses the
+    step size of every parameter from its name.  Returns the fast-weight list in the order `MetaHead.forward(fast_weights=...)`
+    slices it: par - par_lr * inner_grad with torch's two roundings for an updated parameter, and the SAME object for one that
+    passes through.  Deviation from the script: a parameter whose gradient is None (allow_unused) is passed through as the
+    same object as well, where `par_lr * None` would raise a TypeError after printing the name.
+    Gradients of a later .backward(): to the parameter the cotangent itself, to inner_grad (the entry to the second-order graph)
+    -(lr * cotangent), to a step size -sum cotangent * inner_grad over every tensor it updates, accumulated in float64 in a fixed
+    order and rounded once (no atomics: two calls give the same bits).  A step size that updates no tensor, or does not require
+    grad, gets None, and then no reduction runs.  The backward is once-differentiable.
+    Raises for everything unsupported - there is no fallback: CPU or non-float32 tensors, a gradient whose shape differs from
+    its parameter's, empty tensors, and a step size tensor on the CPU (infer.py:244-250 creates them there: create them on the
+    GPU, `nn.Parameter(torch.tensor(inner_lr, device='cuda'))`).  Non-contiguous tensors are made contiguous."""
+    named = list(named_params)
+    grads = list(inner_grad)
+    lrs_in = list(learnable_lr)
+    if len(grads) != len(named):
+        raise ValueError('inner_update: %d parameters but %d gradients' % (len(named), len(grads)))
+    plan = plan_inner_update([n for n, _ in named], len(lrs_in), only_final, separate_head)
+    lib = _lib.load()
+    if len(lrs_in) > lib.effdet_inner_update_max_step_sizes():
+        raise ValueError('inner_update: at most %d step sizes' % lib.effdet_inner_update_max_step_sizes())
+    active = [i for i, k in enumerate(plan) if k is not None and grads[i] is not None]
+    dev = None
+    for i in active:
+        n, p = named[i]
+        g = grads[i]
+        for what, t in (('parameter', p), ('gradient of', g)):
+            if not torch.is_tensor(t) or t.device.type != 'cuda' or t.dtype != torch.float32:
+                raise RuntimeError('inner_update: %s %r must be a float32 GPU tensor (no CPU fallback)' % (what, n))
+        dev = dev or p.device
+        if p.device != dev or g.device != dev:
+            raise RuntimeError('inner_update: %r is on another device than the first parameter' % (n,))
+        if g.shape != p.shape:
+            raise ValueError('inner_update: the gradient of %r has shape %s, the parameter %s' % (n, tuple(g.shape), tuple(p.shape)))
+        if p.numel() == 0:
+            raise ValueError('inner_update: %r is empty' % (n,))
+    lr_spec, lr_tensors = [], []
+    for k, v in enumerate(lrs_in):
+        if torch.is_tensor(v):
+            if v.device.type != 'cuda':
+                raise RuntimeError('inner_update: learnable_lr[%d] is on the CPU; create the step sizes on the GPU, '
+                                   "e.g. nn.Parameter(torch.tensor(inner_lr, device='cuda')) (no CPU fallback)" % k)
+            if v.dtype != torch.float32 or v.numel() != 1 or (dev is not None and v.device != dev):
+                raise RuntimeError('inner_update: learnable_lr[%d] must be a 0-d or 1-element float32 tensor on the parameters\' GPU' % k)
+            lr_spec.append(len(lr_tensors))
+            lr_tensors.append(v)
+        else:
+            lr_spec.append((float(v),))
+    fast = [p for _, p in named]
+    if active:
+        outs = _InnerUpdate.apply(tuple(lr_spec), tuple(plan[i] for i in active), *lr_tensors, *(named[i][1] for i in active),
+                                  *(grads[i] for i in active))
+        for i, o in zip(active, outs):
+            fast[i] = o
+    return fast

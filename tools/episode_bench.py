@@ -15,7 +15,10 @@ included); the report is the median window and the min .. max spread per path.  
     python3 tools/episode_bench.py --support          episode.support_loss (infer.py:645-658) against target_from_selection +
                                                       F.binary_cross_entropy_with_logits on the same decisions, at the meta-phase default
                                                       (25 x 252 rows, d 256): the loss, the create_graph=True gradient to the embeddings
-                                                      and logits, and the backward of a scalar of that gradient"""
+                                                      and logits, and the backward of a scalar of that gradient
+    python3 tools/episode_bench.py --inner            episode.inner_update (infer.py:660-678) forward + backward against the literal
+                                                      loop `par - par_lr * inner_grad` with GPU step sizes and autograd, on the d0 head's
+                                                      parameter list (F 64, 3 layers, 9 anchors) and the d3 default's (F 160, 4 layers)"""
 import argparse
 import os
 import statistics
@@ -31,6 +34,7 @@ import torch.nn.functional as F  # noqa: E402
 
 import _episode_loss_ref as lref  # noqa: E402
 import _episode_ref as ref  # noqa: E402
+import _inner_update_ref as iref  # noqa: E402
 from ood_object_detection_amd import episode  # noqa: E402
 from ood_object_detection_amd.effdet.aux_nets import ProjectionNet  # noqa: E402
 
@@ -160,10 +164,59 @@ def support_section(a, dev):
         print('  ratio torch / support_loss: %.2f' % (statistics.median(t_old) / statistics.median(t_new)))
 
 
+def inner_section(a, dev):
+    """inner_update forward + backward against the literal loop: the same tensors, step sizes and cotangents; the gradients go to
+    the parameters, to inner_grad (leaves here, standing for the create_graph=True gradient) and to the step sizes"""
+    for label, Fc, layers in (('d0 head', 64, 3), ('d3 default', 160, 4)):
+        named_shapes = iref.meta_head_shapes(Fc, layers, 5, A)
+        names = [n for n, _ in named_shapes]
+        cpu = iref.seeded_list(layers, named_shapes)
+        ps, gs = ([t.to(dev).requires_grad_() for t in lst] for lst in cpu[:2])
+        Ws = [t.to(dev) for t in cpu[2]]
+        lrs = [torch.nn.Parameter(torch.tensor(0.05 + 0.02 * k, device=dev)) for k in range(layers + 2)]
+        plan = episode.plan_inner_update(names, len(lrs))
+        act = [i for i, k in enumerate(plan) if k is not None]
+        leaves = [ps[i] for i in act] + [gs[i] for i in act] + lrs
+        shared = len(act) - len(set(plan[i] for i in act))
+
+        def step(update):
+            fast = update(list(zip(names, ps)), gs, lrs)
+            return fast, torch.autograd.grad([fast[i] for i in act], leaves, grad_outputs=[Ws[i] for i in act])
+
+        new_path = lambda: step(episode.inner_update)
+        literal_path = lambda: step(iref.literal_update)
+        f_new, g_new = new_path()
+        f_lit, g_lit = literal_path()
+        torch.cuda.synchronize()
+        n_t = len(act)
+        print('inner update, %s: F %d, %d layers, %d anchors; %d of %d tensors updated, %d elements, %d step sizes'
+              % (label, Fc, layers, A, n_t, len(names), sum(ps[i].numel() for i in act), len(lrs)))
+        print('same outputs: fast weights bit-equal %s, d inner_grad bit-equal %s, d lr differs by %.2e of the largest entry'
+              % (all(torch.equal(p, q) for p, q in zip(f_new, f_lit)), all(torch.equal(p, q) for p, q in zip(g_new[n_t:2 * n_t], g_lit[n_t:2 * n_t])),
+                 float((torch.stack(g_new[2 * n_t:]) - torch.stack(g_lit[2 * n_t:])).abs().max() / torch.stack(g_lit[2 * n_t:]).abs().max())))
+        del f_new, g_new, f_lit, g_lit
+        for _ in range(3):
+            window(new_path, 5)
+            window(literal_path, 5)
+        t_new, t_lit = [], []
+        for _ in range(a.rounds):
+            t_new.append(window(new_path, a.iters))
+            t_lit.append(window(literal_path, a.iters))
+        # launches counted from the expressions: mul + sub per tensor forward; neg, grad * lr, grad * g and its sum per tensor
+        # backward, plus one add per tensor that shares its step size with an earlier one
+        print('inner_update forward + backward (1 + 2 = 3 HIP launches):   median %.1f us, spread %.1f .. %.1f us  (%d windows of %d)'
+              % (statistics.median(t_new), min(t_new), max(t_new), a.rounds, a.iters))
+        print('literal torch loop with autograd (%d + %d = %d launches):  median %.1f us, spread %.1f .. %.1f us'
+              % (2 * n_t, 4 * n_t + shared, 6 * n_t + shared, statistics.median(t_lit), min(t_lit), max(t_lit)))
+        print('ratio literal / new: %.2f' % (statistics.median(t_lit) / statistics.median(t_new)))
+        print()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--losses', action='store_true', help='time projection_losses forward + backward instead of the episode stage')
     ap.add_argument('--support', action='store_true', help='time support_loss at its three orders instead of the episode stage')
+    ap.add_argument('--inner', action='store_true', help='time inner_update forward + backward against the literal torch loop')
     ap.add_argument('--phase', choices=['meta', 'proj'], default='meta')
     ap.add_argument('--images', type=int, default=25)
     ap.add_argument('--fpn', type=int, default=160)
@@ -178,6 +231,8 @@ def main():
         return losses_section(a, dev)
     if a.support:
         return support_section(a, dev)
+    if a.inner:
+        return inner_section(a, dev)
     sides, first = ([8, 4, 2], 2) if a.phase == 'meta' else ([32, 16, 8, 4, 2], 0)
     B, Fc, d = a.images, a.fpn, a.width // 2
     torch.manual_seed(0)
