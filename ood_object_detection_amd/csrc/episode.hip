@@ -20,15 +20,12 @@
 //                            prototype stage; (e) E P^T with max / argmax / mean epilogue, prototypes in LDS, E read once.
 //                            Every reduction runs in a fixed order (per-wave partials, then a sequential second stage): results
 //                            are bitwise reproducible.  argmax ties go to the lower index.
-#include "common.h"
+#include "episode_rows.h"
 
 namespace {
 
 constexpr int EP_MAX_LEVELS = 8;
-constexpr int EP_MAX_DL = 8;              // d <= 64 * EP_MAX_DL
-constexpr int EP_MAX_M = 64;
-constexpr int EP_MAX_PARTS = 32;
-constexpr int EP_MAX_G = 256;
+constexpr int EP_MAX_G = 256;             // the cluster stage's cap on rows_split
 
 // order-preserving key of a float; -0 counts as +0, as torch's comparison does
 DEV unsigned int ep_key(float f) {
@@ -166,31 +163,24 @@ __global__ __launch_bounds__(256) void episode_feed_kernel(FeedArgs a, const flo
 __global__ __launch_bounds__(256) void episode_prep_kernel(const float* X, const float* confs, int n, int d, int rows_per_block,
                                                            float dot_mult, float dot_add, const float* dots,
                                                            float* inv, float* s, float* gpart) {
-    __shared__ float red[4][64 * EP_MAX_DL];
+    __shared__ float red[4][64 * PL_MAX_DL];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float dm = dots ? dots[0] : dot_mult, da = dots ? dots[1] : dot_add;
-    const int r0 = blockIdx.x * rows_per_block;
-    int r1 = r0 + rows_per_block; if (r1 > n) r1 = n;
-    float acc[EP_MAX_DL];
+    const PlDots dt = pl_dots(dots, dot_mult, dot_add);
+    int r1;
+    const int r0 = pl_row_range(rows_per_block, n, r1);
+    float acc[PL_MAX_DL];
 #pragma unroll
-    for (int k = 0; k < EP_MAX_DL; ++k) acc[k] = 0.f;
+    for (int k = 0; k < PL_MAX_DL; ++k) acc[k] = 0.f;
     for (int i = r0 + wave; i < r1; i += 4) {
-        const float* row = X + (long long)i * d;
-        float v[EP_MAX_DL];
-        float ss = 0.f;
+        float v[PL_MAX_DL];
+        const float iv = pl_load_row(X + (long long)i * d, d, lane, v);
+        const float si = pl_sigmoid(dt.m * (confs[i] + dt.a));
 #pragma unroll
-        for (int k = 0; k < EP_MAX_DL; ++k) { const int c = lane + 64 * k; v[k] = c < d ? row[c] : 0.f; }
-#pragma unroll
-        for (int k = 0; k < EP_MAX_DL; ++k) ss += v[k] * v[k];       // columns past d add +0: the sum novelty_score_kernel forms
-        ss = wave_reduce_sum(ss);
-        const float iv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-        const float si = 1.0f / (1.0f + expf(-(dm * (confs[i] + da))));
-#pragma unroll
-        for (int k = 0; k < EP_MAX_DL; ++k) acc[k] += si * (v[k] * iv);
+        for (int k = 0; k < PL_MAX_DL; ++k) acc[k] += si * (v[k] * iv);
         if (lane == 0) { inv[i] = iv; s[i] = si; }
     }
 #pragma unroll
-    for (int k = 0; k < EP_MAX_DL; ++k) red[wave][lane + 64 * k] = acc[k];
+    for (int k = 0; k < PL_MAX_DL; ++k) red[wave][lane + 64 * k] = acc[k];
     __syncthreads();
     for (int c = threadIdx.x; c < d; c += 256) gpart[(long long)blockIdx.x * d + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
 }
@@ -217,11 +207,11 @@ __global__ __launch_bounds__(256) void episode_gsum_kernel(const float* gpart, i
 // (b) / (d): score_i = s_i (e_i . v); best row of the part (blockIdx.x) of image blockIdx.y, ties to the lower row
 __global__ __launch_bounds__(256) void episode_score_kernel(const float* X, const float* inv, const float* s, const float* v, int p, int d,
                                                             int per, float* best_s, int* best_i) {
-    __shared__ float vl[64 * EP_MAX_DL];
+    __shared__ float vl[64 * PL_MAX_DL];
     __shared__ float bs[4];
     __shared__ int bi[4];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int c = threadIdx.x; c < 64 * EP_MAX_DL; c += 256) vl[c] = c < d ? v[c] : 0.f;
+    for (int c = threadIdx.x; c < 64 * PL_MAX_DL; c += 256) vl[c] = c < d ? v[c] : 0.f;
     __syncthreads();
     const int img = blockIdx.y;
     const int j0 = blockIdx.x * per;
@@ -254,10 +244,10 @@ __global__ __launch_bounds__(1024) void episode_proto_kernel(const float* X, con
                                                              int use_thresh, float thresh, float* cmean, float* vsum,
                                                              long long* proto_out, float* avg_out, unsigned char* valid_out,
                                                              int* n_valid_out, float* tclust_out) {
-    __shared__ long long pidx[EP_MAX_M];
-    __shared__ float vec[64 * EP_MAX_DL];
-    __shared__ float avg[EP_MAX_M];
-    __shared__ int val[EP_MAX_M];
+    __shared__ long long pidx[PL_MAX_M];
+    __shared__ float vec[64 * PL_MAX_DL];
+    __shared__ float avg[PL_MAX_M];
+    __shared__ int val[PL_MAX_M];
     __shared__ int nv_;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (tid < m) {
@@ -342,15 +332,15 @@ __global__ __launch_bounds__(64 * EP_ASSIGN_WAVES) void episode_assign_kernel(co
     for (long long i = (long long)blockIdx.x * EP_ASSIGN_WAVES + wave; i < n; i += (long long)gridDim.x * EP_ASSIGN_WAVES) {
         const float* row = X + i * d;
         const float iv = inv[i];
-        float xv[EP_MAX_DL];                                        // the normalised row, read once
+        float xv[PL_MAX_DL];                                        // the normalised row, read once
 #pragma unroll
-        for (int k = 0; k < EP_MAX_DL; ++k) { const int c = lane + 64 * k; xv[k] = (c < d ? row[c] : 0.f) * iv; }
+        for (int k = 0; k < PL_MAX_DL; ++k) { const int c = lane + 64 * k; xv[k] = (c < d ? row[c] : 0.f) * iv; }
         float acc_sum = 0.f, acc_max = -INFINITY;
         int arg = 0;
         for (int j = 0; j < m; ++j) {
             float dot = 0.f;
 #pragma unroll
-            for (int k = 0; k < EP_MAX_DL; ++k) { const int c = lane + 64 * k; if (c < d) dot += xv[k] * pl_[j * d + c]; }
+            for (int k = 0; k < PL_MAX_DL; ++k) { const int c = lane + 64 * k; if (c < d) dot += xv[k] * pl_[j * d + c]; }
             dot = wave_reduce_sum(dot);
             acc_sum += dot;
             if (dot > acc_max) { acc_max = dot; arg = j; }
@@ -366,10 +356,9 @@ struct ClusterPlan { int G, rows_per_block, parts, per, p; long long o_inv, o_gp
 ClusterPlan cluster_plan(int n, int d, int m) {
     ClusterPlan c;
     c.p = n / m;
-    c.G = (n + 15) / 16; if (c.G > EP_MAX_G) c.G = EP_MAX_G;
-    c.rows_per_block = (n + c.G - 1) / c.G;
-    c.G = (n + c.rows_per_block - 1) / c.rows_per_block;
-    c.parts = (c.p + 63) / 64; if (c.parts > EP_MAX_PARTS) c.parts = EP_MAX_PARTS; if (c.parts < 1) c.parts = 1;
+    const RowsSplit r = rows_split(n, EP_MAX_G);
+    c.G = r.G; c.rows_per_block = r.rows_per_block;
+    c.parts = (c.p + 63) / 64; if (c.parts > PL_MAX_PARTS) c.parts = PL_MAX_PARTS; if (c.parts < 1) c.parts = 1;
     c.per = (c.p + c.parts - 1) / c.parts;
     long long o = 0;
     c.o_inv = o; o += n;
@@ -383,7 +372,7 @@ ClusterPlan cluster_plan(int n, int d, int m) {
     return c;
 }
 bool cluster_shape_ok(int n, int d, int m) {
-    return n > 0 && d > 0 && m > 0 && m <= EP_MAX_M && d <= 64 * EP_MAX_DL && (long long)m * d <= 16384 && n % m == 0;
+    return pl_shape_ok(n, d, m) && n % m == 0;
 }
 
 }  // namespace

@@ -18,8 +18,9 @@
 // of the rows: inv, s, sim (kept for the backward), inner_target, per-block partials of the two sums and the nine group
 // statistics; (3) one wave adds the partials in order.
 // Backward, three launches: (1) a wave per row: dsim_i, dl_i, dconf_i, dE_i = (dsim_i P[nearest_i] - e_i dsim_i sim_i) inv_i and
-// per-block partials of d dot_mult / d dot_add; (2) grid (part, prototype): a workgroup walks its part of the rows and adds dsim_i e_i
-// of the rows whose nearest prototype is its own, in ascending row order, into registers - [parts][m][d] partials, no atomics;
+// per-block partials of d dot_mult / d dot_add; (2) grid (part, prototype), pl_part_kernel of episode_rows.h: a workgroup walks its
+// part of the rows and adds dsim_i e_i of the rows whose nearest prototype is its own, in ascending row order, into registers -
+// [parts][m][d] partials, no atomics;
 // (3) one workgroup: dP_k = sum over the parts + dtarget_clust_k cmean, dcmean = sum_k dtarget_clust_k P_k, both taken through the
 // normalisation into the rows proto_k / proto0_k one after the other (a row can be both, and an ordinary row too), and the two
 // dot sums.  Every reduction has a fixed order: two calls give the same bits.
@@ -44,33 +45,21 @@ DEV float pl_x(int use_max, int mode, float s, float sim, float tcn) {
 DEV float pl_hinge_arg(bool t, float x, float margin) { return t ? 1.0f - x : x - margin; }
 
 struct PlPlan {
-    int G, rows_per_block, parts, per;
-    long long o_inv, o_s, o_sim, o_tc, o_cmean, o_pmean, o_P, o_nv;                      // kept from the forward for the backward
-    long long o_fpart, o_dsim, o_dtcrow, o_dotpart, o_dPpart, o_dtcpart, o_dP, total;    // scratch
+    RowsSplit rows;
+    PartsSplit parts;
+    PlKept kept;                                                                          // from the forward for the backward
+    long long o_fpart, o_rowc, o_dotpart, o_dPpart, o_bTpart, o_dP, total;                // scratch
 };
 PlPlan pl_plan(int n, int d, int m) {
     PlPlan p;
-    p.G = (n + 15) / 16; if (p.G > PL_MAX_G) p.G = PL_MAX_G;
-    p.rows_per_block = (n + p.G - 1) / p.G;
-    p.G = (n + p.rows_per_block - 1) / p.rows_per_block;
-    p.parts = (n + 255) / 256; if (p.parts > PL_MAX_PARTS) p.parts = PL_MAX_PARTS;
-    p.per = (n + p.parts - 1) / p.parts;
-    p.parts = (n + p.per - 1) / p.per;
-    long long o = 0;
-    p.o_inv = o; o += n;
-    p.o_s = o; o += n;
-    p.o_sim = o; o += n;
-    p.o_tc = o; o += PL_MAX_M;
-    p.o_cmean = o; o += d;
-    p.o_pmean = o; o += d;
-    p.o_P = o; o += (long long)m * d;
-    p.o_nv = o; o += 1;
-    p.o_fpart = o; o += (long long)p.G * PL_NPART;
-    p.o_dsim = o; o += n;
-    p.o_dtcrow = o; o += n;
-    p.o_dotpart = o; o += (long long)p.G * 2;
-    p.o_dPpart = o; o += (long long)p.parts * m * d;
-    p.o_dtcpart = o; o += (long long)p.parts * m;
+    p.rows = rows_split(n, PL_MAX_G);
+    p.parts = parts_split(n, PL_MAX_PARTS);
+    long long o = pl_kept(n, d, m, p.kept);
+    p.o_fpart = o; o += (long long)p.rows.G * PL_NPART;
+    p.o_rowc = o; o += 4LL * n;
+    p.o_dotpart = o; o += (long long)p.rows.G * 2;
+    p.o_dPpart = o; o += (long long)p.parts.parts * m * d;
+    p.o_bTpart = o; o += 2LL * p.parts.parts * m;
     p.o_dP = o; o += (long long)m * d;
     p.total = o;
     return p;
@@ -80,57 +69,21 @@ PlPlan pl_plan(int n, int d, int m) {
 // forward
 // ---------------------------------------------------------------------------------------------------------------------------
 
-// (1) one workgroup: P [m][d], cmean [d], pmean [d] = mean_k P_k, tc [m], nv, losses[0] = clust_loss
+// (1) one workgroup: the prototype stage (P, cmean, pmean, tc, nv), then losses[0] = clust_loss
 __global__ __launch_bounds__(1024) void pl_proto_kernel(const float* X, const long long* labs, int n, int d, int m, long long cls_id,
                                                         const long long* cls_dev, const long long* proto0, const unsigned char* valid,
                                                         const long long* proto, int use_max, int mode, float margin, float* P,
                                                         float* cmean, float* pmean, float* tc, float* nv_out, float* losses) {
-    __shared__ float vec[64 * PL_MAX_DL];
-    __shared__ float tcs[PL_MAX_M];
-    __shared__ float iv0[PL_MAX_M];
-    __shared__ long long r0[PL_MAX_M];
-    __shared__ int val[PL_MAX_M];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int k = wave; k < m; k += 16) {
-        float v[PL_MAX_DL];
-        const long long r = pl_clamp(proto[k], n);
-        const float iv = pl_load_row(X + r * d, d, lane, v);
-#pragma unroll
-        for (int q = 0; q < PL_MAX_DL; ++q) { const int c = lane + 64 * q; if (c < d) P[(long long)k * d + c] = v[q] * iv; }
-        const long long rr = pl_clamp(proto0[k], n);
-        const float iv2 = pl_load_row(X + rr * d, d, lane, v);
-        if (lane == 0) { iv0[k] = iv2; r0[k] = rr; val[k] = valid[k] ? 1 : 0; }
-    }
+    __shared__ PlProtoLds L;
+    pl_proto_stage(L, X, n, d, m, proto0, valid, proto, P, cmean, pmean, tc, nv_out);
     __syncthreads();
-    int nv = 0;
-    for (int k = 0; k < m; ++k) nv += val[k];
-    const float nvf = (float)nv;
-    for (int c = tid; c < d; c += 1024) {
-        float t = 0.f, u = 0.f;
-        for (int k = 0; k < m; ++k) {
-            if (val[k]) t += X[r0[k] * d + c] * iv0[k];
-            u += P[(long long)k * d + c];
-        }
-        const float cm = t / nvf;                                   // an empty valid set gives NaN, as the reference's mean does
-        cmean[c] = cm; vec[c] = cm;
-        pmean[c] = u / (float)m;
-    }
-    __syncthreads();
-    for (int k = wave; k < m; k += 16) {
-        float dot = 0.f;
-        for (int c = lane; c < d; c += 64) dot += P[(long long)k * d + c] * vec[c];
-        dot = wave_reduce_sum(dot);
-        if (lane == 0) { tc[k] = dot; tcs[k] = dot; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        nv_out[0] = nvf;
+    if (threadIdx.x == 0) {
         float sum = 0.f;
         if (use_max && mode != PL_SAME) {
             const long long cls = cls_dev ? cls_dev[0] : cls_id;
             for (int k = 0; k < m; ++k) {
                 const bool y = labs[pl_clamp(proto[k], n)] == cls;
-                const float arg = pl_hinge_arg(y, tcs[k], margin);
+                const float arg = pl_hinge_arg(y, L.tc[k], margin);
                 sum += arg < 0.f ? 0.f : arg;                       // NaN stays NaN, as torch's clamp keeps it
             }
             sum /= (float)m;
@@ -138,8 +91,6 @@ __global__ __launch_bounds__(1024) void pl_proto_kernel(const float* X, const lo
         losses[0] = sum;
     }
 }
-
-struct PlRow { float l, s, sim, tcn, x, arg; bool t, tobj; long long lab; };
 
 // (2) a wave per row
 __global__ __launch_bounds__(256) void pl_rows_kernel(const float* X, const float* confs, const long long* labs, int n, int d, int m,
@@ -149,31 +100,24 @@ __global__ __launch_bounds__(256) void pl_rows_kernel(const float* X, const floa
                                                       float* s, float* sim, float* inner_target, float* fpart) {
     __shared__ float red[4][PL_NPART];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float dm = dots ? dots[0] : dot_mult, da = dots ? dots[1] : dot_add;
+    const PlDots dt = pl_dots(dots, dot_mult, dot_add);
     const long long cls = cls_dev ? cls_dev[0] : cls_id;
     const bool lab0 = labs[0] == cls;
-    const int r0 = blockIdx.x * rows_per_block;
-    int r1 = r0 + rows_per_block; if (r1 > n) r1 = n;
+    int r1;
+    const int r0 = pl_row_range(rows_per_block, n, r1);
     float hs = 0.f, os = 0.f, g_sum[3] = {0.f, 0.f, 0.f}, t_min = INFINITY, o_max = -INFINITY, n_max = -INFINITY;
     int g_cnt[3] = {0, 0, 0};
     for (int i = r0 + wave; i < r1; i += 4) {
         float v[PL_MAX_DL];
         const float iv = pl_load_row(X + (long long)i * d, d, lane, v);
-        const float l = dm * (confs[i] + da);
-        const float si = 1.0f / (1.0f + expf(-l));
-        const float* prow = pmean;
+        const float l = dt.m * (confs[i] + dt.a);
+        const float si = pl_sigmoid(l);
+        const int k = pl_nearest(nearest, i, m, use_max);
         float tcn = 0.f;
+        const float* prow = pl_proto_row(k, d, P, pmean, tc, tcn);
         const long long lab = labs[i];
-        bool t = lab == cls;
-        if (use_max) {
-            const int k = (int)pl_clamp(nearest[i], m);
-            prow = P + (long long)k * d; tcn = tc[k];
-            t = lab0 && labs[k] == cls;
-        }
-        float dot = 0.f;
-#pragma unroll
-        for (int q = 0; q < PL_MAX_DL; ++q) { const int c = lane + 64 * q; if (c < d) dot += (v[q] * iv) * prow[c]; }
-        dot = wave_reduce_sum(dot);
+        const bool t = use_max ? lab0 && labs[k] == cls : lab == cls;
+        const float dot = pl_row_dot(v, iv, prow, d, lane);
         const float arg = pl_hinge_arg(t, pl_x(use_max, mode, si, dot, tcn), margin);
         hs += arg < 0.f ? 0.f : arg;
         const float tobj = lab > -1 ? 1.f : 0.f;
@@ -238,22 +182,22 @@ __global__ __launch_bounds__(64) void pl_final_kernel(const float* fpart, int G,
 // backward
 // ---------------------------------------------------------------------------------------------------------------------------
 
-// (1) a wave per row: dconf, the row's own part of dE, dsim / dtarget_clust contributions for the prototype stage
+// (1) a wave per row: dconf, the row's own part of dE, and for the part kernel rowc[4 i] = dsim_i inv_i, rowc[4 i + 2] = the row's
+// dtarget_clust contribution
 __global__ __launch_bounds__(256) void pl_bwd_rows_kernel(const float* X, const float* confs, const long long* labs, int n, int d, int m,
                                                           int rows_per_block, long long cls_id, const long long* cls_dev,
                                                           float dot_mult, float dot_add, const float* dots, const long long* nearest,
                                                           int use_max, int mode, float margin, const float* gup, const float* P,
                                                           const float* pmean, const float* tc, const float* inv, const float* s,
-                                                          const float* sim, float* dE, float* dconf, float* dsim_out, float* dtcrow,
-                                                          float* dotpart) {
+                                                          const float* sim, float* dE, float* dconf, float* rowc, float* dotpart) {
     __shared__ float red[4][2];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float dm = dots ? dots[0] : dot_mult, da = dots ? dots[1] : dot_add;
+    const PlDots dt = pl_dots(dots, dot_mult, dot_add);
     const long long cls = cls_dev ? cls_dev[0] : cls_id;
     const bool lab0 = labs[0] == cls;
     const float ge = gup[1], go = gup[2];
-    const int r0 = blockIdx.x * rows_per_block;
-    int r1 = r0 + rows_per_block; if (r1 > n) r1 = n;
+    int r1;
+    const int r0 = pl_row_range(rows_per_block, n, r1);
     float pm = 0.f, pa = 0.f;
     for (int i = r0 + wave; i < r1; i += 4) {
         const float* row = X + (long long)i * d;
@@ -261,15 +205,11 @@ __global__ __launch_bounds__(256) void pl_bwd_rows_kernel(const float* X, const 
 #pragma unroll
         for (int q = 0; q < PL_MAX_DL; ++q) { const int c = lane + 64 * q; v[q] = c < d ? row[c] : 0.f; }
         const float iv = inv[i], si = s[i], simi = sim[i], cf = confs[i];
-        const float* prow = pmean;
+        const int k = pl_nearest(nearest, i, m, use_max);
         float tcn = 0.f;
+        const float* prow = pl_proto_row(k, d, P, pmean, tc, tcn);
         const long long lab = labs[i];
-        bool t = lab == cls;
-        if (use_max) {
-            const int k = (int)pl_clamp(nearest[i], m);
-            prow = P + (long long)k * d; tcn = tc[k];
-            t = lab0 && labs[k] == cls;
-        }
+        const bool t = use_max ? lab0 && labs[k] == cls : lab == cls;
         const float arg = pl_hinge_arg(t, pl_x(use_max, mode, si, simi, tcn), margin);
         const float dx = arg >= 0.f ? (t ? -ge : ge) / (float)n : 0.f;
         float dsim, ds, dtcr = 0.f;
@@ -278,59 +218,20 @@ __global__ __launch_bounds__(256) void pl_bwd_rows_kernel(const float* X, const 
         else { dsim = dx; ds = 0.f; }
         const float tobj = lab > -1 ? 1.f : 0.f;
         const float dl = ds * (si * (1.0f - si)) + go * (si - tobj);
-        pm += dl * (cf + da);
-        pa += dl * dm;
+        pm += dl * (cf + dt.a);
+        pa += dl * dt.m;
         const float edot = dsim * simi;                              // e_i . de_i
         float* out = dE + (long long)i * d;
 #pragma unroll
         for (int q = 0; q < PL_MAX_DL; ++q) { const int c = lane + 64 * q; if (c < d) out[c] = (dsim * prow[c] - (v[q] * iv) * edot) * iv; }
-        if (lane == 0) { dconf[i] = dl * dm; dsim_out[i] = dsim; dtcrow[i] = dtcr; }
+        if (lane == 0) { dconf[i] = dl * dt.m; rowc[4LL * i] = dsim * iv; rowc[4LL * i + 2] = dtcr; }   // pl_part_kernel<false>'s two slots
     }
     if (lane == 0) { red[wave][0] = pm; red[wave][1] = pa; }
     __syncthreads();
     if (threadIdx.x < 2) dotpart[(long long)blockIdx.x * 2 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-// (2) grid (part, prototype): dPpart[part][k][:] = sum over the part's rows with nearest == k of dsim_i e_i, ascending rows per wave
-// ('avg': one "prototype", every row), dtcpart[part][k] = the same sum of dtcrow
-__global__ __launch_bounds__(256) void pl_bwd_part_kernel(const float* X, const long long* nearest, int n, int d, int m, int per, int use_max,
-                                                          const float* inv, const float* dsim, const float* dtcrow, float* dPpart,
-                                                          float* dtcpart) {
-    __shared__ float red[4][64 * PL_MAX_DL];
-    __shared__ float tcr[4];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k = blockIdx.y, q = blockIdx.x, mm = gridDim.y;
-    const int r0 = q * per;
-    int r1 = r0 + per; if (r1 > n) r1 = n;
-    float acc[PL_MAX_DL];
-#pragma unroll
-    for (int u = 0; u < PL_MAX_DL; ++u) acc[u] = 0.f;
-    float tca = 0.f;
-    for (int base = r0 + wave * 64; base < r1; base += 256) {
-        const int i = base + lane;
-        bool match = i < r1;
-        if (match && use_max) match = (int)pl_clamp(nearest[i], m) == k;
-        if (match) tca += dtcrow[i];
-        unsigned long long mask = __ballot(match);
-        while (mask) {
-            const int b = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const long long ii = base + b;
-            const float coef = dsim[ii] * inv[ii];
-            const float* row = X + ii * d;
-#pragma unroll
-            for (int u = 0; u < PL_MAX_DL; ++u) { const int c = lane + 64 * u; if (c < d) acc[u] += coef * row[c]; }
-        }
-    }
-    tca = wave_reduce_sum(tca);
-#pragma unroll
-    for (int u = 0; u < PL_MAX_DL; ++u) red[wave][lane + 64 * u] = acc[u];
-    if (lane == 0) tcr[wave] = tca;
-    __syncthreads();
-    const long long o = (long long)q * mm + k;
-    for (int c = threadIdx.x; c < d; c += 256) dPpart[o * d + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-    if (threadIdx.x == 0) dtcpart[o] = ((tcr[0] + tcr[1]) + tcr[2]) + tcr[3];
-}
+// (2) is pl_part_kernel<false, float> of episode_rows.h: dPpart [parts][m][d], bTpart [parts][m][2] with the dtarget_clust sums in slot 0
 
 // (3) one workgroup: the prototype gradients, through the normalisation into dE's rows; d dot_mult, d dot_add
 __global__ __launch_bounds__(1024) void pl_bwd_proto_kernel(const float* X, const long long* labs, int n, int d, int m, int parts, int G,
@@ -338,7 +239,7 @@ __global__ __launch_bounds__(1024) void pl_bwd_proto_kernel(const float* X, cons
                                                             const unsigned char* valid, const long long* proto, int use_max, int mode,
                                                             float margin, const float* gup, const float* P, const float* cmean,
                                                             const float* tc, const float* nv_in, const float* inv, const float* dPpart,
-                                                            const float* dtcpart, const float* dotpart, float* dP, float* dE, float* ddots) {
+                                                            const float* bTpart, const float* dotpart, float* dP, float* dE, float* ddots) {
     __shared__ float dcmv[64 * PL_MAX_DL];
     __shared__ float dtc[PL_MAX_M], dotP[PL_MAX_M], dot0[PL_MAX_M];
     __shared__ long long rr[PL_MAX_M], rr0[PL_MAX_M];
@@ -354,7 +255,7 @@ __global__ __launch_bounds__(1024) void pl_bwd_proto_kernel(const float* X, cons
             const float arg = pl_hinge_arg(y, tc[k], margin);
             g = arg >= 0.f ? (y ? -gup[0] : gup[0]) / (float)m : 0.f;
         } else if (use_max) {
-            for (int q = 0; q < parts; ++q) g += dtcpart[(long long)q * m + k];
+            for (int q = 0; q < parts; ++q) g += bTpart[2 * ((long long)q * m + k)];
         }
         dtc[k] = g; rr[k] = r; rr0[k] = pl_clamp(proto0[k], n); val[k] = valid[k] ? 1 : 0;
     }
@@ -435,14 +336,15 @@ extern "C" int effdet_episode_proj_loss(void* stream, const float* embds, const 
         !pl_args_ok(embds, confs, labs, n, d, m, proto0, valid, proto, nearest, use_max, loss_mode, workspace, workspace_floats))
         return EFFDET_EINVAL;
     const PlPlan p = pl_plan(n, d, m);
+    const PlKept& k = p.kept;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* w = workspace;
     hipLaunchKernelGGL(pl_proto_kernel, dim3(1), dim3(1024), 0, st, embds, labs, n, d, m, cls_id, cls_id_dev, proto0, valid, proto, use_max,
-                       loss_mode, margin, w + p.o_P, w + p.o_cmean, w + p.o_pmean, w + p.o_tc, w + p.o_nv, losses);
-    hipLaunchKernelGGL(pl_rows_kernel, dim3(p.G), dim3(256), 0, st, embds, confs, labs, n, d, m, p.rows_per_block, cls_id, cls_id_dev,
-                       dot_mult, dot_add, dots, nearest, use_max, loss_mode, margin, w + p.o_P, w + p.o_pmean, w + p.o_tc, w + p.o_inv,
-                       w + p.o_s, w + p.o_sim, inner_target, w + p.o_fpart);
-    hipLaunchKernelGGL(pl_final_kernel, dim3(1), dim3(64), 0, st, w + p.o_fpart, p.G, n, losses, stats, counts);
+                       loss_mode, margin, w + k.o_P, w + k.o_cmean, w + k.o_pmean, w + k.o_tc, w + k.o_nv, losses);
+    hipLaunchKernelGGL(pl_rows_kernel, dim3(p.rows.G), dim3(256), 0, st, embds, confs, labs, n, d, m, p.rows.rows_per_block, cls_id, cls_id_dev,
+                       dot_mult, dot_add, dots, nearest, use_max, loss_mode, margin, w + k.o_P, w + k.o_pmean, w + k.o_tc, w + k.o_inv,
+                       w + k.o_s, w + k.o_sim, inner_target, w + p.o_fpart);
+    hipLaunchKernelGGL(pl_final_kernel, dim3(1), dim3(64), 0, st, w + p.o_fpart, p.rows.G, n, losses, stats, counts);
     return effdet_check_launch();
 }
 
@@ -457,15 +359,16 @@ extern "C" int effdet_episode_proj_loss_backward(void* stream, const float* embd
         !pl_args_ok(embds, confs, labs, n, d, m, proto0, valid, proto, nearest, use_max, loss_mode, workspace, workspace_floats))
         return EFFDET_EINVAL;
     const PlPlan p = pl_plan(n, d, m);
+    const PlKept& k = p.kept;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* w = workspace;
-    hipLaunchKernelGGL(pl_bwd_rows_kernel, dim3(p.G), dim3(256), 0, st, embds, confs, labs, n, d, m, p.rows_per_block, cls_id, cls_id_dev,
-                       dot_mult, dot_add, dots, nearest, use_max, loss_mode, margin, grad_losses, w + p.o_P, w + p.o_pmean, w + p.o_tc,
-                       w + p.o_inv, w + p.o_s, w + p.o_sim, d_embds, d_confs, w + p.o_dsim, w + p.o_dtcrow, w + p.o_dotpart);
-    hipLaunchKernelGGL(pl_bwd_part_kernel, dim3(p.parts, use_max ? m : 1), dim3(256), 0, st, embds, nearest, n, d, m, p.per, use_max,
-                       w + p.o_inv, w + p.o_dsim, w + p.o_dtcrow, w + p.o_dPpart, w + p.o_dtcpart);
-    hipLaunchKernelGGL(pl_bwd_proto_kernel, dim3(1), dim3(1024), 0, st, embds, labs, n, d, m, p.parts, p.G, cls_id, cls_id_dev, proto0, valid,
-                       proto, use_max, loss_mode, margin, grad_losses, w + p.o_P, w + p.o_cmean, w + p.o_tc, w + p.o_nv, w + p.o_inv,
-                       w + p.o_dPpart, w + p.o_dtcpart, w + p.o_dotpart, w + p.o_dP, d_embds, d_dots);
+    hipLaunchKernelGGL(pl_bwd_rows_kernel, dim3(p.rows.G), dim3(256), 0, st, embds, confs, labs, n, d, m, p.rows.rows_per_block, cls_id,
+                       cls_id_dev, dot_mult, dot_add, dots, nearest, use_max, loss_mode, margin, grad_losses, w + k.o_P, w + k.o_pmean,
+                       w + k.o_tc, w + k.o_inv, w + k.o_s, w + k.o_sim, d_embds, d_confs, w + p.o_rowc, w + p.o_dotpart);
+    hipLaunchKernelGGL((pl_part_kernel<false, float>), dim3(p.parts.parts, use_max ? m : 1), dim3(256), 0, st, embds, (const float*)nullptr,
+                       nearest, n, d, m, p.parts.per, use_max, w + p.o_rowc, w + p.o_dPpart, (float*)nullptr, w + p.o_bTpart);
+    hipLaunchKernelGGL(pl_bwd_proto_kernel, dim3(1), dim3(1024), 0, st, embds, labs, n, d, m, p.parts.parts, p.rows.G, cls_id, cls_id_dev,
+                       proto0, valid, proto, use_max, loss_mode, margin, grad_losses, w + k.o_P, w + k.o_cmean, w + k.o_tc, w + k.o_nv,
+                       w + k.o_inv, w + p.o_dPpart, w + p.o_bTpart, w + p.o_dotpart, w + p.o_dP, d_embds, d_dots);
     return effdet_check_launch();
 }

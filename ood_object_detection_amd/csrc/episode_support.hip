@@ -24,7 +24,7 @@
 //     b = bar e - inv (u V_e + a bar edot),   bar r = inv (b - e (e . b)) - inv^2 (w - a u) e
 // Three launches, as the projection-loss backward: (1) a wave per row: the row's own bar r, d conf, d x, per-block partials of
 // d dot_mult / d dot_add / Ldot, and four per-row coefficients; (2) grid (part, prototype): [parts][m][d] partials of bar P and bar Pdot
-// over the rows whose nearest prototype it is, ascending rows, no atomics; (3) one workgroup: bar P_k / bar Pdot_k complete, bar cmean /
+// over the rows whose nearest prototype it is, ascending rows, no atomics (pl_part_kernel of episode_rows.h); (3) one workgroup: bar P_k / bar Pdot_k complete, bar cmean /
 // bar cmeandot, through the normalisation into the rows proto_k / proto0_k one after the other, and the scalar sums.  The second pass
 // runs one more launch first: one workgroup forms Pdot, cmeandot, mean_k Pdot_k and tcdot.  A null cotangent is zero.
 // Forward and backward compute in float32.  The second pass computes in float64 from the float32 inputs (its own P, cmean, tc, inv,
@@ -44,8 +44,10 @@ struct SlScratch {                        // a pass's scratch, in units of its o
     long long o_fpart, o_rowc, o_BPpart, o_BPdpart, o_bTpart, o_BP, o_BPd, o_P, o_cmean, o_pmean, o_tc, o_nv, o_Pdot, o_cmd, o_pmd, o_tcd, total;
 };
 struct SlPlan {
-    int G, rows_per_block, parts, per, parts2, per2;
-    long long o_inv, o_s, o_sim, o_tc, o_cmean, o_pmean, o_P, o_nv, o_scratch, total;       // kept from the forward; scratch, in floats
+    RowsSplit rows;
+    PartsSplit parts, parts2;                         // of the first and the second pass
+    PlKept kept;                                      // from the forward
+    long long o_scratch, total;                       // in floats
     SlScratch s1, s2;
 };
 SlScratch sl_scratch(int n, int d, int m, int G, int parts, bool second) {
@@ -71,89 +73,31 @@ SlScratch sl_scratch(int n, int d, int m, int G, int parts, bool second) {
     s.total = o;
     return s;
 }
-void sl_split(int n, int max_parts, int& parts, int& per) {
-    parts = (n + 255) / 256; if (parts > max_parts) parts = max_parts;
-    per = (n + parts - 1) / parts;
-    parts = (n + per - 1) / per;
-}
 SlPlan sl_plan(int n, int d, int m) {
     SlPlan p;
-    p.G = (n + 15) / 16; if (p.G > PL_MAX_G) p.G = PL_MAX_G;
-    p.rows_per_block = (n + p.G - 1) / p.G;
-    p.G = (n + p.rows_per_block - 1) / p.rows_per_block;
-    sl_split(n, PL_MAX_PARTS, p.parts, p.per);
-    sl_split(n, SL_MAX_PARTS2, p.parts2, p.per2);
-    long long o = 0;
-    p.o_inv = o; o += n;
-    p.o_s = o; o += n;
-    p.o_sim = o; o += n;
-    p.o_tc = o; o += PL_MAX_M;
-    p.o_cmean = o; o += d;
-    p.o_pmean = o; o += d;
-    p.o_P = o; o += (long long)m * d;
-    p.o_nv = o; o += 1;
+    p.rows = rows_split(n, PL_MAX_G);
+    p.parts = parts_split(n, PL_MAX_PARTS);
+    p.parts2 = parts_split(n, SL_MAX_PARTS2);
+    long long o = pl_kept(n, d, m, p.kept);
     o += o & 1;                                       // float64 alignment of the scratch
     p.o_scratch = o;
-    p.s1 = sl_scratch(n, d, m, p.G, p.parts, false);
-    p.s2 = sl_scratch(n, d, m, p.G, p.parts2, true);
+    p.s1 = sl_scratch(n, d, m, p.rows.G, p.parts.parts, false);
+    p.s2 = sl_scratch(n, d, m, p.rows.G, p.parts2.parts, true);
     const long long a = p.s1.total, b = 2 * p.s2.total;
     p.total = o + (a > b ? a : b);
     return p;
-}
-
-DEV float sl_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-DEV double sl_sigmoid(double v) { return 1.0 / (1.0 + exp(-v)); }
-template <class R> DEV R sl_wave_sum(R v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------------------------------------
 
-// one workgroup: P [m][d], cmean [d], pmean [d] = mean_k P_k, tc [m], nv
+// one workgroup: the prototype stage (P, cmean, pmean, tc, nv)
 __global__ __launch_bounds__(1024) void sl_proto_kernel(const float* X, int n, int d, int m, const long long* proto0, const unsigned char* valid,
                                                         const long long* proto, float* P, float* cmean, float* pmean, float* tc,
                                                         float* nv_out) {
-    __shared__ float vec[64 * PL_MAX_DL];
-    __shared__ float iv0[PL_MAX_M];
-    __shared__ long long r0[PL_MAX_M];
-    __shared__ int val[PL_MAX_M];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int k = wave; k < m; k += 16) {
-        float v[PL_MAX_DL];
-        const long long r = pl_clamp(proto[k], n);
-        const float iv = pl_load_row(X + r * d, d, lane, v);
-#pragma unroll
-        for (int q = 0; q < PL_MAX_DL; ++q) { const int c = lane + 64 * q; if (c < d) P[(long long)k * d + c] = v[q] * iv; }
-        const long long rr = pl_clamp(proto0[k], n);
-        const float iv2 = pl_load_row(X + rr * d, d, lane, v);
-        if (lane == 0) { iv0[k] = iv2; r0[k] = rr; val[k] = valid[k] ? 1 : 0; }
-    }
-    __syncthreads();
-    int nv = 0;
-    for (int k = 0; k < m; ++k) nv += val[k];
-    const float nvf = (float)nv;
-    for (int c = tid; c < d; c += 1024) {
-        float t = 0.f, u = 0.f;
-        for (int k = 0; k < m; ++k) {
-            if (val[k]) t += X[r0[k] * d + c] * iv0[k];
-            u += P[(long long)k * d + c];
-        }
-        const float cm = t / nvf;                                   // an empty valid set gives NaN, as the reference's mean does
-        cmean[c] = cm; vec[c] = cm;
-        pmean[c] = u / (float)m;
-    }
-    __syncthreads();
-    for (int k = wave; k < m; k += 16) {
-        float dot = 0.f;
-        for (int c = lane; c < d; c += 64) dot += P[(long long)k * d + c] * vec[c];
-        dot = wave_reduce_sum(dot);
-        if (lane == 0) tc[k] = dot;
-    }
-    if (tid == 0) nv_out[0] = nvf;
+    __shared__ PlProtoLds L;
+    pl_proto_stage(L, X, n, d, m, proto0, valid, proto, P, cmean, pmean, tc, nv_out);
 }
 
 // a wave per row
@@ -163,24 +107,17 @@ __global__ __launch_bounds__(256) void sl_fwd_rows_kernel(const float* X, const 
                                                           const float* tc, float* inv, float* s, float* sim, float* target, float* fpart) {
     __shared__ float red[4];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float dm = dots ? dots[0] : dot_mult, da = dots ? dots[1] : dot_add;
-    const int r0 = blockIdx.x * rows_per_block;
-    int r1 = r0 + rows_per_block; if (r1 > n) r1 = n;
+    const PlDots dt = pl_dots(dots, dot_mult, dot_add);
+    int r1;
+    const int r0 = pl_row_range(rows_per_block, n, r1);
     float sum = 0.f;
     for (int i = r0 + wave; i < r1; i += 4) {
         float v[PL_MAX_DL];
         const float iv = pl_load_row(X + (long long)i * d, d, lane, v);
-        const float si = sl_sigmoid(dm * (confs[i] + da));
-        const float* prow = pmean;
+        const float si = pl_sigmoid(dt.m * (confs[i] + dt.a));
         float T = 1.f;
-        if (use_max) {
-            const int k = (int)pl_clamp(nearest[i], m);
-            prow = P + (long long)k * d; T = tc[k];
-        }
-        float dot = 0.f;
-#pragma unroll
-        for (int q = 0; q < PL_MAX_DL; ++q) { const int c = lane + 64 * q; if (c < d) dot += (v[q] * iv) * prow[c]; }
-        dot = wave_reduce_sum(dot);
+        const float* prow = pl_proto_row(pl_nearest(nearest, i, m, use_max), d, P, pmean, tc, T);
+        const float dot = pl_row_dot(v, iv, prow, d, lane);
         const float t = (si * T) * dot, x = logits[i];
         sum += (fmaxf(x, 0.f) - x * t) + log1pf(expf(-fabsf(x)));
         if (lane == 0) { inv[i] = iv; s[i] = si; sim[i] = dot; target[i] = t; }
@@ -223,10 +160,10 @@ __global__ __launch_bounds__(1024) void sl_tangent_kernel(const float* X, const 
                 w[q] = (Ve && c < d) ? (double)Ve[r * d + c] : 0.;
                 ss += e[q] * e[q];
             }
-            const double iv = 1.0 / fmax(sqrt(sl_wave_sum(ss)), 1e-12);
+            const double iv = 1.0 / fmax(sqrt(pl_wave_sum(ss)), 1e-12);
 #pragma unroll
             for (int q = 0; q < PL_MAX_DL; ++q) { e[q] *= iv; a += e[q] * w[q]; }
-            a = sl_wave_sum(a);
+            a = pl_wave_sum(a);
             if (pass == 0) {
 #pragma unroll
                 for (int q = 0; q < PL_MAX_DL; ++q) {
@@ -265,7 +202,7 @@ __global__ __launch_bounds__(1024) void sl_tangent_kernel(const float* X, const 
             dot += p * vec[c];
             dotd += Pdot[(long long)k * d + c] * vec[c] + p * vecd[c];
         }
-        dot = sl_wave_sum(dot); dotd = sl_wave_sum(dotd);
+        dot = pl_wave_sum(dot); dotd = pl_wave_sum(dotd);
         if (lane == 0) { tc[k] = dot; tcd[k] = dotd; }
     }
     if (tid == 0) nv_out[0] = nvf;
@@ -283,25 +220,22 @@ __global__ __launch_bounds__(256) void sl_rows_kernel(const float* X, const floa
                                                       float* dconf, float* dlogit, R* rowc, R* fpart) {
     __shared__ R red[4][3];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const R dm = dots ? dots[0] : dot_mult, da = dots ? dots[1] : dot_add;
+    const PlDots dt = pl_dots(dots, dot_mult, dot_add);
+    const R dm = dt.m, da = dt.a;
     const R g = gup[0], nf = (R)n;
     R Vm = 0, Va = 0;
     if (SECOND) { Vm = V.mult ? V.mult[0] : 0.f; Va = V.add ? V.add[0] : 0.f; }
-    const int r0 = blockIdx.x * rows_per_block;
-    int r1 = r0 + rows_per_block; if (r1 > n) r1 = n;
+    int r1;
+    const int r0 = pl_row_range(rows_per_block, n, r1);
     R pm = 0, pa = 0, pl = 0;
     for (int i = r0 + wave; i < r1; i += 4) {
         const float* row = X + (long long)i * d;
         const R cf = confs[i], x = logits[i], l = dm * (cf + da);
         const float* vrow = (SECOND && V.e) ? V.e + (long long)i * d : nullptr;
-        const R* prow = pmean;
-        const R* pdrow = pmd;
+        const int k = pl_nearest(nearest, i, m, use_max);
         R T = 1, Td = 0;
-        if (use_max) {
-            const int k = (int)pl_clamp(nearest[i], m);
-            prow = P + (long long)k * d; T = tc[k];
-            if (SECOND) { pdrow = Pdot + (long long)k * d; Td = tcd[k]; }
-        }
+        const R* prow = pl_proto_row(k, d, P, pmean, tc, T);
+        const R* pdrow = SECOND ? pl_proto_row(k, d, Pdot, pmd, tcd, Td) : pmd;
         R e[PL_MAX_DL], w[PL_MAX_DL];
         R iv, si, simi, a = 0, prw = 0, epd = 0;
         if (SECOND) {
@@ -313,7 +247,7 @@ __global__ __launch_bounds__(256) void sl_rows_kernel(const float* X, const floa
                 w[q] = (vrow && c < d) ? (R)vrow[c] : (R)0;
                 ss += e[q] * e[q];
             }
-            iv = (R)1 / fmax(sqrt(sl_wave_sum(ss)), (R)1e-12);
+            iv = (R)1 / fmax(sqrt(pl_wave_sum(ss)), (R)1e-12);
             simi = 0;
 #pragma unroll
             for (int q = 0; q < PL_MAX_DL; ++q) {
@@ -322,15 +256,15 @@ __global__ __launch_bounds__(256) void sl_rows_kernel(const float* X, const floa
                 a += e[q] * w[q];
                 if (c < d) { simi += e[q] * prow[c]; prw += prow[c] * w[q]; epd += e[q] * pdrow[c]; }
             }
-            simi = sl_wave_sum(simi); a = sl_wave_sum(a); prw = sl_wave_sum(prw); epd = sl_wave_sum(epd);
-            si = sl_sigmoid(l);
+            simi = pl_wave_sum(simi); a = pl_wave_sum(a); prw = pl_wave_sum(prw); epd = pl_wave_sum(epd);
+            si = pl_sigmoid(l);
         } else {
             iv = inv[i]; si = s[i]; simi = sim[i];
 #pragma unroll
             for (int q = 0; q < PL_MAX_DL; ++q) { const int c = lane + 64 * q; e[q] = c < d ? row[c] * iv : (R)0; }
         }
         // s (1 - s) as sigmoid(l) sigmoid(-l): 1 - s is 0 in float32 from l = 17 on, the product is not
-        const R t = (si * T) * simi, sx = sl_sigmoid(x), sp = si * sl_sigmoid(-l);
+        const R t = (si * T) * simi, sx = pl_sigmoid(x), sp = si * pl_sigmoid(-l);
         R bt, btd = 0, dx, simdot = 0, ldot = 0, sdot = 0, vc = 0;
         if (SECOND) {
             simdot = (prw - simi * a) * iv + epd;                    // edot_i . P + e_i . Pdot
@@ -339,7 +273,7 @@ __global__ __launch_bounds__(256) void sl_rows_kernel(const float* X, const floa
             const R tdot = (sdot * T) * simi + (si * Td) * simi + (si * T) * simdot;
             const R vx = V.x ? V.x[i] : 0.f;
             pl += (sx - t) * vx - x * tdot;
-            dx = g * ((sx * sl_sigmoid(-x)) * vx - tdot) / nf;
+            dx = g * ((sx * pl_sigmoid(-x)) * vx - tdot) / nf;
             bt = -(g * vx) / nf; btd = -(g * x) / nf;
         } else {
             dx = g * (sx - t) / nf;
@@ -382,59 +316,6 @@ __global__ __launch_bounds__(256) void sl_rows_kernel(const float* X, const floa
     if (lane == 0) { red[wave][0] = pm; red[wave][1] = pa; red[wave][2] = pl; }
     __syncthreads();
     if (threadIdx.x < 3) fpart[(long long)blockIdx.x * 4 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
-
-// (2) grid (part, prototype): over the part's rows with nearest == k, ascending rows per wave ('avg': one "prototype", every row),
-// BPpart = sum c1_i r_i + c2_i V_e,i;  BPdpart = sum c2_i r_i;  bTpart = sums of bar T, bar Tdot
-template <bool SECOND, class R>
-__global__ __launch_bounds__(256) void sl_part_kernel(const float* X, const float* Ve, const long long* nearest, int n, int d, int m, int per,
-                                                      int use_max, const R* rowc, R* BPpart, R* BPdpart, R* bTpart) {
-    __shared__ R red[4][64 * PL_MAX_DL];
-    __shared__ R redd[SECOND ? 4 : 1][64 * PL_MAX_DL];
-    __shared__ R tcr[4][2];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k = blockIdx.y, q = blockIdx.x, mm = gridDim.y;
-    const int r0 = q * per;
-    int r1 = r0 + per; if (r1 > n) r1 = n;
-    R acc[PL_MAX_DL], accd[PL_MAX_DL];
-#pragma unroll
-    for (int u = 0; u < PL_MAX_DL; ++u) { acc[u] = 0; accd[u] = 0; }
-    R ta = 0, tb = 0;
-    for (int base = r0 + wave * 64; base < r1; base += 256) {
-        const int i = base + lane;
-        bool match = i < r1;
-        if (match && use_max) match = (int)pl_clamp(nearest[i], m) == k;
-        if (match) { ta += rowc[4LL * i + 2]; if (SECOND) tb += rowc[4LL * i + 3]; }
-        unsigned long long mask = __ballot(match);
-        while (mask) {
-            const int b = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const long long ii = base + b;
-            const R c1 = rowc[4 * ii], c2 = SECOND ? rowc[4 * ii + 1] : (R)0;
-            const float* row = X + ii * d;
-            const float* vrow = (SECOND && Ve) ? Ve + ii * d : nullptr;
-#pragma unroll
-            for (int u = 0; u < PL_MAX_DL; ++u) {
-                const int c = lane + 64 * u;
-                if (c < d) {
-                    const R r = row[c];
-                    acc[u] += c1 * r;
-                    if (SECOND) { if (vrow) acc[u] += c2 * (R)vrow[c]; accd[u] += c2 * r; }
-                }
-            }
-        }
-    }
-    ta = sl_wave_sum(ta); tb = sl_wave_sum(tb);
-#pragma unroll
-    for (int u = 0; u < PL_MAX_DL; ++u) { red[wave][lane + 64 * u] = acc[u]; if (SECOND) redd[wave][lane + 64 * u] = accd[u]; }
-    if (lane == 0) { tcr[wave][0] = ta; tcr[wave][1] = tb; }
-    __syncthreads();
-    const long long o = (long long)q * mm + k;
-    for (int c = threadIdx.x; c < d; c += 256) {
-        BPpart[o * d + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-        if (SECOND) BPdpart[o * d + c] = ((redd[0][c] + redd[1][c]) + redd[2][c]) + redd[3][c];
-    }
-    if (threadIdx.x < 2) bTpart[2 * o + threadIdx.x] = ((tcr[0][threadIdx.x] + tcr[1][threadIdx.x]) + tcr[2][threadIdx.x]) + tcr[3][threadIdx.x];
 }
 
 // (3) one workgroup: the prototype gradients, through the normalisation into dE's rows; d dot_mult, d dot_add, Ldot
@@ -504,7 +385,7 @@ __global__ __launch_bounds__(1024) void sl_bwd_proto_kernel(const float* X, cons
         if (SECOND) {
             R ss = 0;
             for (int c = lane; c < d; c += 64) { const R v = X[r * d + c]; ss += v * v; }
-            iv = (R)1 / fmax(sqrt(sl_wave_sum(ss)), (R)1e-12);
+            iv = (R)1 / fmax(sqrt(pl_wave_sum(ss)), (R)1e-12);
         } else {
             iv = inv[r];
         }
@@ -518,7 +399,7 @@ __global__ __launch_bounds__(1024) void sl_bwd_proto_kernel(const float* X, cons
                 a += e * v; u += bed * e; w += bed * v;
             }
         }
-        a = sl_wave_sum(a); u = sl_wave_sum(u); w = sl_wave_sum(w); eb = sl_wave_sum(eb);
+        a = pl_wave_sum(a); u = pl_wave_sum(u); w = pl_wave_sum(w); eb = pl_wave_sum(eb);
         if (lane == 0) { riv[which][k] = iv; ra[which][k] = a; ru[which][k] = u; rw[which][k] = w; reb[which][k] = eb - iv * ((R)2 * u * a); }
     }
     __syncthreads();
@@ -541,7 +422,7 @@ __global__ __launch_bounds__(1024) void sl_bwd_proto_kernel(const float* X, cons
     if (wave == 15) {
         R a = 0, b = 0, l = 0;
         for (int g = lane; g < G; g += 64) { a += fpart[4 * g]; b += fpart[4 * g + 1]; if (SECOND) l += fpart[4 * g + 2]; }
-        a = sl_wave_sum(a); b = sl_wave_sum(b); l = sl_wave_sum(l);
+        a = pl_wave_sum(a); b = pl_wave_sum(b); l = pl_wave_sum(l);
         if (lane == 0) { ddots[0] = (float)a; ddots[1] = (float)b; if (SECOND) dgrad[0] = (float)(l / (R)n); }
     }
 }
@@ -560,7 +441,8 @@ int sl_backward(hipStream_t st, const float* embds, const float* confs, const fl
                 float* d_confs, float* d_logits, float* d_dots) {
     const SlPlan p = sl_plan(n, d, m);
     const SlScratch& s = SECOND ? p.s2 : p.s1;
-    const int parts = SECOND ? p.parts2 : p.parts, per = SECOND ? p.per2 : p.per;
+    const PlKept& k = p.kept;
+    const PartsSplit& ps = SECOND ? p.parts2 : p.parts;
     R* x = reinterpret_cast<R*>(w + p.o_scratch);
     const R *P, *cmean, *pmean, *tc, *nv;
     if constexpr (SECOND) {
@@ -568,15 +450,15 @@ int sl_backward(hipStream_t st, const float* embds, const float* confs, const fl
                            x + s.o_pmean, x + s.o_tc, x + s.o_nv, x + s.o_Pdot, x + s.o_cmd, x + s.o_pmd, x + s.o_tcd);
         P = x + s.o_P; cmean = x + s.o_cmean; pmean = x + s.o_pmean; tc = x + s.o_tc; nv = x + s.o_nv;
     } else {
-        P = w + p.o_P; cmean = w + p.o_cmean; pmean = w + p.o_pmean; tc = w + p.o_tc; nv = w + p.o_nv;
+        P = w + k.o_P; cmean = w + k.o_cmean; pmean = w + k.o_pmean; tc = w + k.o_tc; nv = w + k.o_nv;
     }
-    hipLaunchKernelGGL((sl_rows_kernel<SECOND, R>), dim3(p.G), dim3(256), 0, st, embds, confs, logits, n, d, m, p.rows_per_block, dot_mult,
-                       dot_add, dots, nearest, use_max, thresh_grad, gup, V, P, pmean, tc, w + p.o_inv, w + p.o_s, w + p.o_sim,
+    hipLaunchKernelGGL((sl_rows_kernel<SECOND, R>), dim3(p.rows.G), dim3(256), 0, st, embds, confs, logits, n, d, m, p.rows.rows_per_block,
+                       dot_mult, dot_add, dots, nearest, use_max, thresh_grad, gup, V, P, pmean, tc, w + k.o_inv, w + k.o_s, w + k.o_sim,
                        x + s.o_Pdot, x + s.o_pmd, x + s.o_tcd, d_embds, d_confs, d_logits, x + s.o_rowc, x + s.o_fpart);
-    hipLaunchKernelGGL((sl_part_kernel<SECOND, R>), dim3(parts, use_max ? m : 1), dim3(256), 0, st, embds, V.e, nearest, n, d, m, per, use_max,
+    hipLaunchKernelGGL((pl_part_kernel<SECOND, R>), dim3(ps.parts, use_max ? m : 1), dim3(256), 0, st, embds, V.e, nearest, n, d, m, ps.per, use_max,
                        x + s.o_rowc, x + s.o_BPpart, x + s.o_BPdpart, x + s.o_bTpart);
-    hipLaunchKernelGGL((sl_bwd_proto_kernel<SECOND, R>), dim3(1), dim3(1024), 0, st, embds, V.e, n, d, m, parts, p.G, proto0, valid, proto,
-                       use_max, P, cmean, nv, w + p.o_inv, x + s.o_Pdot, x + s.o_cmd, x + s.o_BPpart, x + s.o_BPdpart, x + s.o_bTpart,
+    hipLaunchKernelGGL((sl_bwd_proto_kernel<SECOND, R>), dim3(1), dim3(1024), 0, st, embds, V.e, n, d, m, ps.parts, p.rows.G, proto0, valid, proto,
+                       use_max, P, cmean, nv, w + k.o_inv, x + s.o_Pdot, x + s.o_cmd, x + s.o_BPpart, x + s.o_BPdpart, x + s.o_bTpart,
                        x + s.o_fpart, x + s.o_BP, x + s.o_BPd, d_embds, d_dots, d_grad);
     return effdet_check_launch();
 }
@@ -596,13 +478,15 @@ extern "C" int effdet_episode_supp_loss(void* stream, const float* embds, const 
     if (!loss || !target || !sl_args_ok(embds, confs, logits, n, d, m, proto0, valid, proto, nearest, use_max, workspace, workspace_floats))
         return EFFDET_EINVAL;
     const SlPlan p = sl_plan(n, d, m);
+    const PlKept& k = p.kept;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* w = workspace;
-    hipLaunchKernelGGL(sl_proto_kernel, dim3(1), dim3(1024), 0, st, embds, n, d, m, proto0, valid, proto, w + p.o_P, w + p.o_cmean, w + p.o_pmean,
-                       w + p.o_tc, w + p.o_nv);
-    hipLaunchKernelGGL(sl_fwd_rows_kernel, dim3(p.G), dim3(256), 0, st, embds, confs, logits, n, d, m, p.rows_per_block, dot_mult, dot_add, dots,
-                       nearest, use_max, w + p.o_P, w + p.o_pmean, w + p.o_tc, w + p.o_inv, w + p.o_s, w + p.o_sim, target, w + p.o_scratch + p.s1.o_fpart);
-    hipLaunchKernelGGL(sl_final_kernel, dim3(1), dim3(64), 0, st, w + p.o_scratch + p.s1.o_fpart, p.G, n, loss);
+    float* fpart = w + p.o_scratch + p.s1.o_fpart;
+    hipLaunchKernelGGL(sl_proto_kernel, dim3(1), dim3(1024), 0, st, embds, n, d, m, proto0, valid, proto, w + k.o_P, w + k.o_cmean, w + k.o_pmean,
+                       w + k.o_tc, w + k.o_nv);
+    hipLaunchKernelGGL(sl_fwd_rows_kernel, dim3(p.rows.G), dim3(256), 0, st, embds, confs, logits, n, d, m, p.rows.rows_per_block, dot_mult, dot_add,
+                       dots, nearest, use_max, w + k.o_P, w + k.o_pmean, w + k.o_tc, w + k.o_inv, w + k.o_s, w + k.o_sim, target, fpart);
+    hipLaunchKernelGGL(sl_final_kernel, dim3(1), dim3(64), 0, st, fpart, p.rows.G, n, loss);
     return effdet_check_launch();
 }
 

@@ -37,6 +37,36 @@ def _check(t, dim, what):
         raise RuntimeError('%s: expected a float32 %d-d GPU tensor (no CPU fallback)' % (what, dim))
 
 
+def _use_max(sim_target):
+    if sim_target not in ('avg', 'max'):
+        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    return 1 if sim_target == 'max' else 0
+
+
+def _check_vector(t, dev, dtype, n, what, name):
+    if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or t.numel() != n:
+        raise RuntimeError('%s: %s must be a %s GPU tensor of %d elements (no CPU fallback)' % (what, name, dtype, n))
+
+
+def _flat(t, n):
+    return t.detach().reshape(n).contiguous()
+
+
+def _workspace(query, n, d, m, dev, limits):
+    """the float32 workspace the kernels of an (n, d, m) problem ask for; ValueError(limits) when they do not take the shape"""
+    ws_floats = query(n, d, m) if n > 0 and m > 0 else -1
+    if ws_floats < 0:
+        raise ValueError(limits)
+    return torch.empty(ws_floats, dtype=torch.float32, device=dev), ws_floats
+
+
+LOSS_LIMITS = 'need n >= num prototypes, at most 64 prototypes, d <= 512 and prototypes * d <= 16384'
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
 def _nhwc(t):
     """[B, C, H, W] -> (tensor that owns [B, H, W, C] memory, image stride); the MetaHead's permuted views are taken as they are"""
     B, C, H, W = t.shape
@@ -78,7 +108,7 @@ def select_anchors(confs):
         keepalive.append(v)
         ptr.append(v.data_ptr()); stride.append(s); count.append(A * H * W); keep.append(kept_per_level(H, W, A))
         outs.append(torch.empty(B, keep[-1], dtype=torch.int32, device=c.device))
-    st = torch.cuda.current_stream(confs[0].device).cuda_stream
+    st = _stream(confs[0].device)
     _lib.check(lib.effdet_episode_select(st, B, len(confs), _ptrs(ptr), _lls(stride), _ints(count), _ints(keep),
                                          _ptrs([o.data_ptr() for o in outs])), 'effdet_episode_select')
     return outs
@@ -121,7 +151,7 @@ def projection_feed(activs, confs, sel, proj_net, first_level=0):
     Kp = (K + 7) // 8 * 8
     feed = torch.empty(B, R, Kp, dtype=torch.float32, device=dev)
     conf = torch.empty(B, R, dtype=torch.float32, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = _stream(dev)
     _lib.check(lib.effdet_episode_feed(st, B, nl, _ptrs(aptr), _lls(astr), _ptrs(cptr), _lls(cstr), _ptrs(sptr), _ints(keeps),
                                        _ints(widths), anch.data_ptr(), lev.data_ptr(), lev.shape[0], cell.data_ptr(), cell.shape[0],
                                        int(first_level), A, Fc, Kp, feed.data_ptr(), conf.data_ptr()), 'effdet_episode_feed')
@@ -147,31 +177,27 @@ def cluster(proj_embds, confs, num_images, dot_mult, dot_add, valid_threshold=No
     An empty valid set gives NaN target_clust / target as in the reference; n_valid says so.  argmax ties go to the lower index.
     num_images <= 64, d <= 512, num_images * d <= 16384."""
     _check(proj_embds, 2, 'cluster')
-    if sim_target not in ('avg', 'max'):
-        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    use_max = _use_max(sim_target)
     lib = _lib.load()
     e = proj_embds.detach().contiguous()
     n, d = e.shape
     m = int(num_images)
     dev = e.device
-    if not torch.is_tensor(confs) or confs.device != dev or confs.dtype != torch.float32 or confs.numel() != n:
-        raise RuntimeError('cluster: confs must be a float32 GPU tensor of n elements (no CPU fallback)')
-    c = confs.detach().reshape(n).contiguous()
-    ws_floats = lib.effdet_episode_cluster_workspace_floats(n, d, m) if m > 0 and n > 0 else -1
-    if ws_floats < 0:
-        raise ValueError('need n %% num_images == 0, num_images <= 64, d <= 512 and num_images * d <= 16384')
+    _check_vector(confs, dev, torch.float32, n, 'cluster', 'confs')
+    c = _flat(confs, n)
+    ws, ws_floats = _workspace(lib.effdet_episode_cluster_workspace_floats, n, d, m, dev,
+                               'need n % num_images == 0, num_images <= 64, d <= 512 and num_images * d <= 16384')
     dm, da, dots = _dots(dot_mult, dot_add, dev)
-    ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
     fn = torch.empty(4, n, dtype=torch.float32, device=dev)              # soft_thresh, sim, target, (spare)
     fm = torch.empty(3, m, dtype=torch.float32, device=dev)              # avg_init0, avg_init, target_clust
     im = torch.empty(2, m, dtype=torch.int64, device=dev)
     nearest = torch.empty(n, dtype=torch.int64, device=dev)
     valid = torch.empty(m, dtype=torch.bool, device=dev)
     n_valid = torch.empty(1, dtype=torch.int32, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = _stream(dev)
     _lib.check(lib.effdet_episode_cluster(st, e.data_ptr(), c.data_ptr(), n, d, m, dm, da, dots.data_ptr() if dots is not None else None,
                                           0 if valid_threshold is None else 1, 0.0 if valid_threshold is None else float(valid_threshold),
-                                          1 if sim_target == 'max' else 0, ws.data_ptr(), ws_floats, fn[0].data_ptr(), im[0].data_ptr(),
+                                          use_max, ws.data_ptr(), ws_floats, fn[0].data_ptr(), im[0].data_ptr(),
                                           fm[0].data_ptr(), valid.data_ptr(), n_valid.data_ptr(), im[1].data_ptr(), fm[1].data_ptr(),
                                           fm[2].data_ptr(), fn[1].data_ptr(), nearest.data_ptr(), fn[2].data_ptr()),
                'effdet_episode_cluster')
@@ -186,15 +212,14 @@ def target_from_selection(proj_embds, confs, out, dot_mult, dot_add, sim_target=
     non-differentiable in the reference.  Returns dict(soft_thresh, target_clust [m], sim [n], target [n]).  The meta phase's
     binary cross-entropy on this target has its own HIP kernels at both orders: `support_loss`."""
     _check(proj_embds, 2, 'target_from_selection')
-    if sim_target not in ('avg', 'max'):
-        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    use_max = _use_max(sim_target)
     e = F.normalize(proj_embds, p=2)
     soft_thresh = (dot_mult * (confs.reshape(-1) + dot_add)).sigmoid()
     valid = out['valid'].to(e.dtype)
     cmean = (e[out['proto0']] * valid[:, None]).sum(0) / valid.sum()      # mean of the valid first prototypes (NaN when none is)
     protos = e[out['proto']]
     target_clust = protos @ cmean
-    if sim_target == 'max':
+    if use_max:
         nearest = out['nearest']
         sim = (e * protos[nearest]).sum(1)
         target = soft_thresh * target_clust[nearest] * sim
@@ -223,19 +248,15 @@ class _ProjectionLosses(torch.autograd.Function):
         e = proj_embds.detach().contiguous()
         n, d = e.shape
         dev = e.device
-        c = confs.detach().reshape(n).contiguous()
-        ws_floats = lib.effdet_episode_proj_loss_workspace_floats(n, d, m) if n > 0 and m > 0 else -1
-        if ws_floats < 0:
-            raise ValueError('need n >= num prototypes, at most 64 prototypes, d <= 512 and prototypes * d <= 16384')
+        c = _flat(confs, n)
+        ws, ws_floats = _workspace(lib.effdet_episode_proj_loss_workspace_floats, n, d, m, dev, LOSS_LIMITS)
         dm, da, dots = _dots(dot_mult, dot_add, dev)
-        ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
         inner = torch.empty(n, dtype=torch.float32, device=dev)
         stats = torch.empty(6, dtype=torch.float32, device=dev)
         counts = torch.empty(3, dtype=torch.int32, device=dev)
         args = _proj_loss_args(e, c, labs, cls, dots, idx, n, d, m, use_max, mode, margin, dm, da)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.effdet_episode_proj_loss(st, *args, ws.data_ptr(), ws_floats, losses.data_ptr(), inner.data_ptr(), stats.data_ptr(),
+        _lib.check(lib.effdet_episode_proj_loss(_stream(dev), *args, ws.data_ptr(), ws_floats, losses.data_ptr(), inner.data_ptr(), stats.data_ptr(),
                                                 counts.data_ptr()), 'effdet_episode_proj_loss')
         ctx.keep = (e, c, labs, cls, dots, idx, ws)
         ctx.scalars = (n, d, m, use_max, mode, margin, dm, da, ws_floats)
@@ -257,8 +278,7 @@ class _ProjectionLosses(torch.autograd.Function):
         d_c = torch.empty(n, dtype=torch.float32, device=dev)
         d_dots = torch.empty(2, dtype=torch.float32, device=dev)
         args = _proj_loss_args(e, c, labs, cls, dots, idx, n, d, m, use_max, mode, margin, dm, da)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.effdet_episode_proj_loss_backward(st, *args, gup.data_ptr(), ws.data_ptr(), ws_floats, d_e.data_ptr(), d_c.data_ptr(),
+        _lib.check(lib.effdet_episode_proj_loss_backward(_stream(dev), *args, gup.data_ptr(), ws.data_ptr(), ws_floats, d_e.data_ptr(), d_c.data_ptr(),
                                                          d_dots.data_ptr()), 'effdet_episode_proj_loss_backward')
         e_shape, c_shape, dot_shapes = ctx.shapes
         g_dots = [d_dots[i].reshape(s) if s is not None and ctx.needs_input_grad[2 + i] else None for i, s in enumerate(dot_shapes)]
@@ -280,34 +300,20 @@ def projection_losses(proj_embds, confs, labs, cls_id, sel, dot_mult, dot_add, s
     The backward is once-differentiable: the projection phase is first order (infer.py:787-789).  The meta phase differentiates
     its loss twice; that is `support_loss`.  With nothing requiring grad only the forward runs.  An empty
     valid set gives NaN clust_loss (and NaN 'same' embds_loss / inner_target) as the reference does; obj_loss stays finite."""
-    if sim_target not in ('avg', 'max'):
-        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    use_max = _use_max(sim_target)
     if loss_mode not in LOSS_MODES:
         raise ValueError("loss_mode must be 'separate', 'same' or 'no_conf' (infer.py FLAGS.loss_mode)")
     _check(proj_embds, 2, 'projection_losses')
     n = proj_embds.shape[0]
     dev = proj_embds.device
-    if not torch.is_tensor(confs) or confs.device != dev or confs.dtype != torch.float32 or confs.numel() != n:
-        raise RuntimeError('projection_losses: confs must be a float32 GPU tensor of n elements (no CPU fallback)')
-    if not torch.is_tensor(labs) or labs.device != dev or labs.dtype != torch.int64 or labs.numel() != n:
-        raise RuntimeError('projection_losses: labs must be an int64 GPU tensor of n elements')
-    use_max = 1 if sim_target == 'max' else 0
-    m = int(sel['proto'].numel())
-    idx = []
-    for key, dtype, count in (('proto0', torch.int64, m), ('valid', torch.bool, m), ('proto', torch.int64, m), ('nearest', torch.int64, n)):
-        if key == 'nearest' and not use_max:
-            idx.append(None)
-            continue
-        t = sel[key]
-        if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or t.numel() != count:
-            raise RuntimeError('projection_losses: sel[%r] must be a %s GPU tensor of %d elements' % (key, dtype, count))
-        idx.append(t.detach().reshape(count).contiguous())
+    _check_vector(confs, dev, torch.float32, n, 'projection_losses', 'confs')
+    _check_vector(labs, dev, torch.int64, n, 'projection_losses', 'labs')
+    m, idx = _sel_indices(sel, dev, n, use_max, 'projection_losses')
     if torch.is_tensor(cls_id):
         cls = (0, cls_id.detach().to(device=dev, dtype=torch.int64).reshape(1))
     else:
         cls = (int(cls_id), None)
-    out = _ProjectionLosses.apply(proj_embds, confs, dot_mult, dot_add, labs.detach().reshape(n).contiguous(), cls, tuple(idx), m,
-                                  use_max, LOSS_MODES[loss_mode], float(margin))
+    out = _ProjectionLosses.apply(proj_embds, confs, dot_mult, dot_add, _flat(labs, n), cls, idx, m, use_max, LOSS_MODES[loss_mode], float(margin))
     return {'clust_loss': out[0], 'embds_loss': out[1], 'obj_loss': out[2], 'inner_target': out[3],
             'stats': dict(zip(STAT_NAMES, out[4].unbind(0))), 'counts': out[5]}
 
@@ -319,10 +325,8 @@ def _sel_indices(sel, dev, n, use_max, what):
         if key == 'nearest' and not use_max:
             idx.append(None)
             continue
-        t = sel[key]
-        if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or t.numel() != count:
-            raise RuntimeError('%s: sel[%r] must be a %s GPU tensor of %d elements' % (what, key, dtype, count))
-        idx.append(t.detach().reshape(count).contiguous())
+        _check_vector(sel[key], dev, dtype, count, what, 'sel[%r]' % key)
+        idx.append(_flat(sel[key], count))
     return m, tuple(idx)
 
 
@@ -354,17 +358,13 @@ class _SupportLoss(torch.autograd.Function):
         st.e = proj_embds.detach().contiguous()
         st.n, st.d = st.e.shape
         dev = st.e.device
-        st.c = confs.detach().reshape(st.n).contiguous()
-        st.x = logits.detach().reshape(st.n).contiguous()
+        st.c, st.x = _flat(confs, st.n), _flat(logits, st.n)
         st.idx, st.m, st.use_max, st.thresh_grad = idx, m, use_max, thresh_grad
-        st.ws_floats = lib.effdet_episode_supp_loss_workspace_floats(st.n, st.d, m) if st.n > 0 and m > 0 else -1
-        if st.ws_floats < 0:
-            raise ValueError('need n >= num prototypes, at most 64 prototypes, d <= 512 and prototypes * d <= 16384')
+        st.ws, st.ws_floats = _workspace(lib.effdet_episode_supp_loss_workspace_floats, st.n, st.d, m, dev, LOSS_LIMITS)
         st.dm, st.da, st.dots = _dots(dot_mult, dot_add, dev)
-        st.ws = torch.empty(st.ws_floats, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         target = torch.empty(st.n, dtype=torch.float32, device=dev)
-        _lib.check(lib.effdet_episode_supp_loss(torch.cuda.current_stream(dev).cuda_stream, *st.args(), st.ws.data_ptr(), st.ws_floats,
+        _lib.check(lib.effdet_episode_supp_loss(_stream(dev), *st.args(), st.ws.data_ptr(), st.ws_floats,
                                                 loss.data_ptr(), target.data_ptr()), 'effdet_episode_supp_loss')
         ctx.st = st
         ctx.dot_tensors = tuple(torch.is_tensor(t) for t in (dot_mult, dot_add))
@@ -395,7 +395,7 @@ class _SupportLossGrad(torch.autograd.Function):
         d_e = torch.empty(st.n, st.d, dtype=torch.float32, device=dev)
         d_cx = torch.empty(2, st.n, dtype=torch.float32, device=dev)
         d_dots = torch.empty(2, dtype=torch.float32, device=dev)
-        _lib.check(lib.effdet_episode_supp_loss_backward(torch.cuda.current_stream(dev).cuda_stream, *st.args(1 if st.thresh_grad else 0),
+        _lib.check(lib.effdet_episode_supp_loss_backward(_stream(dev), *st.args(1 if st.thresh_grad else 0),
                                                          gup.data_ptr(), st.ws.data_ptr(), st.ws_floats, d_e.data_ptr(), d_cx[0].data_ptr(),
                                                          d_cx[1].data_ptr(), d_dots.data_ptr()), 'effdet_episode_supp_loss_backward')
         ctx.st, ctx.gup = st, gup
@@ -418,7 +418,7 @@ class _SupportLossGrad(torch.autograd.Function):
         h_e = torch.empty(st.n, st.d, dtype=torch.float32, device=dev)
         h_cx = torch.empty(2, st.n, dtype=torch.float32, device=dev)
         h_dots = torch.empty(2, dtype=torch.float32, device=dev)
-        _lib.check(lib.effdet_episode_supp_loss_backward2(torch.cuda.current_stream(dev).cuda_stream, *st.args(1 if st.thresh_grad else 0),
+        _lib.check(lib.effdet_episode_supp_loss_backward2(_stream(dev), *st.args(1 if st.thresh_grad else 0),
                                                           ctx.gup.data_ptr(), *(ptr for _, ptr in keep), st.ws.data_ptr(), st.ws_floats,
                                                           d_g.data_ptr(), h_e.data_ptr(), h_cx[0].data_ptr(), h_cx[1].data_ptr(),
                                                           h_dots.data_ptr()), 'effdet_episode_supp_loss_backward2')
@@ -441,15 +441,12 @@ def support_loss(proj_embds, confs, cls_logits, sel, dot_mult, dot_add, sim_targ
     max(x, 0) - x t + log1p(exp(-|x|)) holds as it is.  Returns dict(loss: 0-d, target: [n] detached, equal to cluster's).
     An empty valid set gives NaN loss, target and gradients for 'max', as the reference does.  Third order is not built.  With
     nothing requiring grad only the forward runs; without create_graph the gradient records nothing."""
-    if sim_target not in ('avg', 'max'):
-        raise ValueError("sim_target must be 'avg' or 'max' (infer.py FLAGS.sim_target)")
+    use_max = _use_max(sim_target)
     _check(proj_embds, 2, 'support_loss')
     n = proj_embds.shape[0]
     dev = proj_embds.device
-    for name, t in (('confs', confs), ('cls_logits', cls_logits)):
-        if not torch.is_tensor(t) or t.device != dev or t.dtype != torch.float32 or t.numel() != n:
-            raise RuntimeError('support_loss: %s must be a float32 GPU tensor of n elements (no CPU fallback)' % name)
-    use_max = 1 if sim_target == 'max' else 0
+    _check_vector(confs, dev, torch.float32, n, 'support_loss', 'confs')
+    _check_vector(cls_logits, dev, torch.float32, n, 'support_loss', 'cls_logits')
     m, idx = _sel_indices(sel, dev, n, use_max, 'support_loss')
     loss, target = _SupportLoss.apply(proj_embds, confs, cls_logits, dot_mult, dot_add, idx, m, use_max, bool(thresh_grad))
     return {'loss': loss, 'target': target}
@@ -514,7 +511,7 @@ class _InnerUpdate(torch.autograd.Function):
         gc = [g.detach().contiguous() for g in gs]
         outs = [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in pc]
         lr_ptr, lr_val = _lr_table(lr_spec, lrs)
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = _stream(dev)
         for run in _inner_update_launches(index, lib.effdet_inner_update_max_tensors()):
             _lib.check(lib.effdet_inner_update(st, len(run), _ptrs([pc[t].data_ptr() for t in run]), _ptrs([gc[t].data_ptr() for t in run]),
                                                _ptrs([outs[t].data_ptr() for t in run]), _lls([pc[t].numel() for t in run]),
@@ -551,7 +548,7 @@ class _InnerUpdate(torch.autograd.Function):
                 ws_doubles = max(lib.effdet_inner_update_workspace_doubles(len(r), _lls([gc[t].numel() for t in r])) for r in runs)
                 ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev)
                 dlr = torch.empty(len(lr_spec), dtype=torch.float32, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = _stream(dev)
             for i, r in enumerate(runs):            # one stream: a later run reuses the partials' space after the earlier one has added them up
                 _lib.check(lib.effdet_inner_update_backward(
                     st, len(r), _ptrs([G[t].data_ptr() for t in r]), _ptrs([gc[t].data_ptr() for t in r]),

@@ -13,25 +13,15 @@ import torch
 import torch.nn.functional as F
 
 import _episode_ref as ref
+from _episode_cases import A, DEV, NUM_IMAGES, OFFSET, _head_like, _levels, _meta_head, _same
 
 pytestmark = pytest.mark.gpu
-
-DEV = 'cuda:0'
-A = 9
 
 
 def _proj_net(fpn_channels, width=64, seed=0):
     from ood_object_detection_amd.effdet.efficientdet import ProjectionNet
     torch.manual_seed(seed)
     return ProjectionNet(types.SimpleNamespace(fpn_channels=fpn_channels), width).to(DEV)
-
-
-def _head_like(vals, side):
-    """vals [B, N] -> [B, A, H, W] view of [B, H, W, A] memory inside a larger per-image buffer, as the MetaHead returns it"""
-    B, N = vals.shape
-    buf = torch.zeros(B, N + 45, device=DEV)
-    buf[:, :N] = vals.to(DEV)
-    return buf[:, :N].view(B, side, side, A).permute(0, 3, 1, 2)
 
 
 # ---- 1. selection -------------------------------------------------------------------------------------------------------------
@@ -85,13 +75,6 @@ def test_selection_ties_go_to_the_lower_index():
 
 
 # ---- 2. feed ------------------------------------------------------------------------------------------------------------------
-
-def _levels(seed, B, Fc, sides):
-    gen = torch.Generator().manual_seed(seed)
-    activs = [torch.randn(B, s, s, Fc, generator=gen).to(DEV).permute(0, 3, 1, 2) for s in sides]
-    confs = [_head_like(ref.tie_free_confs(seed + s, B, A * s * s), s) for s in sides]
-    return activs, confs
-
 
 @pytest.mark.parametrize('first_level,sides', [(0, [16, 8, 4, 2]), (2, [8, 4, 2])])
 @pytest.mark.parametrize('Fc', [64, 88, 160, 66])            # 66: no 16-byte pieces, the kernel's scalar copy
@@ -212,29 +195,6 @@ def test_cluster_at_the_projection_phase_size_without_an_n_by_n_buffer():
 
 # ---- 5. end to end ------------------------------------------------------------------------------------------------------------
 
-OFFSET = 2                          # supp_level_offset
-SIDES = [32, 16, 8, 4, 2]           # 256 px
-NUM_IMAGES = 25
-
-
-def _meta_head(golden, seed):
-    from _seeded import meta_nets_case
-    from ood_object_detection_amd.effdet.config import get_efficientdet_config
-    from ood_object_detection_amd.effdet.efficientdet import MetaHead, ProjectionNet
-    c = meta_nets_case(golden('meta_nets'))
-    cfg = get_efficientdet_config('tf_efficientdet_d0')
-    torch.manual_seed(seed)
-    mh = MetaHead(cfg, pretrain_init=c['init'])
-    with torch.no_grad():
-        mh.predict_pw.copy_(c['extra']['predict_pw']); mh.predict_pb.copy_(c['extra']['predict_pb'])
-    proj_net = ProjectionNet(cfg, 512)                                          # 106 -> 512 -> 256
-    with torch.no_grad():
-        proj_net.dot_mult.fill_(1.5); proj_net.dot_add.fill_(0.25)
-    gen = torch.Generator().manual_seed(seed)
-    xs = [torch.randn(NUM_IMAGES, c['F'], s, s, generator=gen) for s in SIDES]
-    return mh.to(DEV), proj_net.to(DEV), xs
-
-
 def _e2e_loss(target, conf_logits):
     return F.binary_cross_entropy_with_logits(conf_logits, target)              # infer.py:656
 
@@ -311,16 +271,12 @@ def test_whole_chain_in_one_graph_replays_bit_for_bit():
             out = episode.cluster(embds, conf.reshape(-1), B, proj_net.dot_mult, proj_net.dot_add, valid_threshold=0.1)
         return [feed, conf, embds] + [out[k] for k in sorted(out)] + sel
 
-    def same(a, b):
-        return all(torch.equal(x, y) or bool((torch.isnan(x) == torch.isnan(y)).all() and torch.equal(x.nan_to_num(), y.nan_to_num()))
-                   for x, y in zip(a, b))
-
     a1, c1 = _levels(31, B, Fc, sides)
     a2, c2 = _levels(32, B, Fc, sides)
     static_a = [t.clone(memory_format=torch.preserve_format) for t in a1]
     static_c = [t.clone(memory_format=torch.preserve_format) for t in c1]
     eager1 = [t.clone() for t in chain(a1, c1)]
-    assert same(eager1, chain(a1, c1))                                           # two eager runs are bit-identical
+    assert _same(eager1, chain(a1, c1))                                           # two eager runs are bit-identical
     eager2 = [t.clone() for t in chain(a2, c2)]
     assert not torch.equal(eager1[0], eager2[0])
     side = torch.cuda.Stream()
@@ -338,4 +294,4 @@ def test_whole_chain_in_one_graph_replays_bit_for_bit():
             s.copy_(t)
         graph.replay()
         torch.cuda.synchronize()
-        assert same(captured, eager)
+        assert _same(captured, eager)

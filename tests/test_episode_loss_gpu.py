@@ -21,10 +21,10 @@ import torch
 
 import _episode_loss_ref as lref
 import _episode_ref as ref
+from _episode_cases import DEV, NUM_IMAGES, OFFSET, _device_sel, _levels, _meta_head, _same
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 CLS = lref.CLS_ID
 CONFIGS = [('max', 'separate'), ('max', 'same'), ('max', 'no_conf'), ('avg', 'separate')]
 SIZES = [(25, 252, 256, 2), (7, 100, 64, 3), (64, 5, 256, 4), (5, 37, 100, 6)]        # num, rows, d, clustered_rows seed
@@ -49,10 +49,6 @@ def _inputs(num, rows, d, seed, sim_target, saturated=False):
 @functools.lru_cache(maxsize=None)
 def _labels(seed, n, first_is_task, pool=lref.LABEL_POOL):
     return lref.draw_labels(seed, n, first_is_task, pool)
-
-
-def _device_sel(sel):
-    return {k: v.to(DEV) for k, v in sel.items()}
 
 
 def _gpu(x, confs, labs, sel, dm, da, sim_target, loss_mode, margin, cls=CLS, grad=True, weights=WEIGHTS):
@@ -232,29 +228,6 @@ def test_projection_phase_size_without_an_n_by_n_buffer():
 
 # ---- 5. determinism and capture ----------------------------------------------------------------------------------------------------
 
-A = 9
-OFFSET = 2
-
-
-def _head_like(vals, side):
-    B, N = vals.shape
-    buf = torch.zeros(B, N + 45, device=DEV)
-    buf[:, :N] = vals.to(DEV)
-    return buf[:, :N].view(B, side, side, A).permute(0, 3, 1, 2)
-
-
-def _levels(seed, B, Fc, sides):
-    gen = torch.Generator().manual_seed(seed)
-    activs = [torch.randn(B, s, s, Fc, generator=gen).to(DEV).permute(0, 3, 1, 2) for s in sides]
-    confs = [_head_like(ref.tie_free_confs(seed + s, B, A * s * s), s) for s in sides]
-    return activs, confs
-
-
-def _same(a, b):
-    return all(torch.equal(x, y) or bool((torch.isnan(x) == torch.isnan(y)).all() and torch.equal(x.nan_to_num(), y.nan_to_num()))
-               for x, y in zip(a, b))
-
-
 def _flat(out, grads):
     return [out['clust_loss'], out['embds_loss'], out['obj_loss'], out['inner_target'], out['counts']] + \
         [out['stats'][k] for k in lref.STAT_NAMES] + list(grads)
@@ -344,28 +317,6 @@ def test_empty_valid_set_gives_nan_clust_loss_and_a_finite_obj_loss():
 
 # ---- 7. end to end -------------------------------------------------------------------------------------------------------------------
 
-SIDES = [32, 16, 8, 4, 2]           # 256 px
-NUM_IMAGES = 25
-
-
-def _meta_head(golden, seed):
-    from _seeded import meta_nets_case
-    from ood_object_detection_amd.effdet.config import get_efficientdet_config
-    from ood_object_detection_amd.effdet.efficientdet import MetaHead, ProjectionNet
-    c = meta_nets_case(golden('meta_nets'))
-    cfg = get_efficientdet_config('tf_efficientdet_d0')
-    torch.manual_seed(seed)
-    mh = MetaHead(cfg, pretrain_init=c['init'])
-    with torch.no_grad():
-        mh.predict_pw.copy_(c['extra']['predict_pw']); mh.predict_pb.copy_(c['extra']['predict_pb'])
-    proj_net = ProjectionNet(cfg, 512)                                          # 106 -> 512 -> 256
-    with torch.no_grad():
-        proj_net.dot_mult.fill_(1.5); proj_net.dot_add.fill_(0.25)
-    gen = torch.Generator().manual_seed(seed)
-    xs = [torch.randn(NUM_IMAGES, c['F'], s, s, generator=gen) for s in SIDES]
-    return c, mh.to(DEV), proj_net.to(DEV), xs
-
-
 def _final_loss(o):
     return 0.03 * (30. * (o['embds_loss'] + o['clust_loss']) + 1e-4 * o['obj_loss'])       # infer.py:787-789, default coefficients
 
@@ -376,7 +327,7 @@ def test_end_to_end_projection_phase_step(golden):
     through the confidences, gathered with the selection."""
     from oracle import model as om
     from ood_object_detection_amd import episode
-    c, mh, proj_net, xs = _meta_head(golden, 21)
+    c, mh, proj_net, xs = _meta_head(golden, 21, with_case=True)
     confs, activs = mh([t.to(DEV) for t in xs], ret_activs=True, level_offset=OFFSET)
     sel = episode.select_anchors(confs)
     feed, conf = episode.projection_feed(activs, confs, sel, proj_net, first_level=OFFSET)

@@ -17,10 +17,10 @@ import torch
 
 import _episode_ref as ref
 import _support_loss_ref as sref
+from _episode_cases import DEV, OFFSET, _device_sel, _levels, _same
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 ALL = (0, 1, 2, 3, 4)
 # num, rows, d, seed
 SHAPES = [(1, 7, 40, 1),           # m = 1, d below one wave
@@ -46,10 +46,6 @@ def _case(shape, sim_target, saturated=False):
 @functools.lru_cache(maxsize=None)
 def _ref(shape, sim_target, dtype, thresh_grad=True, shared_head=False, present=ALL, saturated=False):
     return sref.orders(_case(shape, sim_target, saturated), 'lean', dtype, sim_target, thresh_grad, shared_head, present)
-
-
-def _device_sel(sel):
-    return {k: v.to(DEV) for k, v in sel.items()}
 
 
 def _gpu(case, sim_target='max', thresh_grad=True, shared_head=False, present=ALL, second=True, sel=None):
@@ -257,29 +253,6 @@ def test_two_calls_of_all_three_passes_give_the_same_bits(sim_target):
 
 
 # ---- 7. graph capture -----------------------------------------------------------------------------------------------------------
-
-A = 9
-OFFSET = 2
-
-
-def _head_like(vals, side):
-    B, N = vals.shape
-    buf = torch.zeros(B, N + 45, device=DEV)
-    buf[:, :N] = vals.to(DEV)
-    return buf[:, :N].view(B, side, side, A).permute(0, 3, 1, 2)
-
-
-def _levels(seed, B, Fc, sides):
-    gen = torch.Generator().manual_seed(seed)
-    activs = [torch.randn(B, s, s, Fc, generator=gen).to(DEV).permute(0, 3, 1, 2) for s in sides]
-    confs = [_head_like(ref.tie_free_confs(seed + s, B, A * s * s), s) for s in sides]
-    return activs, confs
-
-
-def _same(a, b):
-    return all(torch.equal(x, y) or bool((torch.isnan(x) == torch.isnan(y)).all() and torch.equal(x.nan_to_num(), y.nan_to_num()))
-               for x, y in zip(a, b))
-
 
 def test_chain_with_all_three_passes_in_one_graph_replays_bit_for_bit():
     from ood_object_detection_amd import episode

@@ -1,4 +1,4 @@
-// A CPU model of the SIMT execution, enough to run csrc/episode_support.hip as host C++ (tools/simt_model/run.py copies the kernel
+// A CPU model of the SIMT execution, enough to run csrc/episode_loss.hip and csrc/episode_support.hip as host C++ (tools/simt_model/run.py copies the kernel
 // source beside this file, where `#include "common.h"` finds it instead of csrc/common.h): one std::thread per thread of a
 // workgroup, the workgroups one after another, a barrier for __syncthreads and one per wave for the shuffles and the ballot.
 // __shared__ is a function-local static, shared by the threads of the one workgroup that is running.  It checks the arithmetic and
@@ -42,6 +42,9 @@ static inline unsigned long long __ballot(bool p) {
     return r;
 }
 DEV float wave_reduce_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
+DEV float wave_reduce_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64)); return v; }
+static inline float __int_as_float(int v) { float f; std::memcpy(&f, &v, 4); return f; }
+static inline int __float_as_int(float f) { int v; std::memcpy(&v, &f, 4); return v; }
 template <class K, class... A>
 void sim_launch(K kernel, dim3 grid, dim3 block, A... args) {
     const int nt = block.x, nw = (nt + 63) / 64;
