@@ -504,6 +504,40 @@ int effdet_train_gemm_nt_relu(void* stream, const float* A, const float* W, floa
 int effdet_train_gemm_nt_mask(void* stream, const float* A, const float* W, const float* mask, float* C, long long M, int K, int N);
 int effdet_train_relu_mask(void* stream, const float* g, const float* y, float* out, long long n);
 
+/* ---- host-only plan queries of the training GEMMs and depthwise entries (launch nothing) ------------------------------------------
+ * What the launchers of effdet_train_gemm_nt* / _gemm_tn* / _dwconv_* decide from the shape, the row maps and the pointer
+ * alignment, answered by the launchers' own decision code.  Contract of effdet_mbconv_plan_describe: fills min(n, *_PLAN_INTS) ints
+ * of `out` and returns that count, or EFFDET_EINVAL (out == NULL, n <= 0, or arguments the entry points refuse).
+ * A row-map side is (levels, rpi, img_stride, ld): levels == 0 -> the (rpi, img_stride, ld) map of effdet_train_gemm_nt (zeros:
+ * dense rows); levels != 0 -> the level-packed map of the *_levels entries with img_stride = pk_img_stride, ld = pk_ld.
+ * `align`: address mod 16 (0, 4, 8 or 12) of each pointer; entries of absent operands are ignored.
+ * gemm_nt: operands = EFFDET_NT_HAS_* bits; epi 0 none / 1 relu / 2 mask (needs HAS_MASK); align[8] = A, W, C, bias, R, C2,
+ *          a_scale, mask.  Slots: 0 VEC, 1 KS, 2 FAST, 3 EPI (template arguments of the kernel), 4 floats per store (4 / 2 / 1 -> 0),
+ *          5 workgroups, 6 kchunk: the k range of one wave of the split-K form (0 when KS == 1)
+ * gemm_tn: x_scale_rows > 0 -> effdet_train_gemm_tn_scaled (dense rows); align[3] = dY, X, x_scale.  Slots: 0 body (0 gemm_tn_kernel,
+ *          1 the pipelined _v, 2 the 128-column _w), 1 VY (width of the dY loads), 2 VX (plain body; 1 for the others), 3 DENSE,
+ *          4 SCALED, 5 S (slices over M), 6 rows_per_slice, 7 empty trailing slices, 8-10 grid x, y, z
+ * dwconv:  which 0 effdet_train_dwconv_fwd / 1 _bwd_dx[_silu] / 2 _bwd_dw; k may carry EFFDET_PAD_SYMMETRIC.  Slots (those of the
+ *          other entries 0): 0 Ho, 1 Wo, 2 pad_t, 3 pad_l, 4 channel groups of 64; forward: 5 blocks_per_image (= _fwd_parts),
+ *          6 strips_x; d input: 7 kernel (1 the 4-pixel stride-1 form, 0 general), 8 workgroups; d taps: 9 seg, 10 segments per
+ *          row, 11 segs_per_chunk, 12 chunks (workspace = chunks * (k * k + 1) * C floats) */
+#define EFFDET_NT_HAS_BIAS 1
+#define EFFDET_NT_HAS_R 2
+#define EFFDET_NT_HAS_C2 4
+#define EFFDET_NT_HAS_A_SCALE 8
+#define EFFDET_NT_ACCUMULATE 16
+#define EFFDET_NT_HAS_MASK 32
+#define EFFDET_TRAIN_GEMM_NT_PLAN_INTS 7
+#define EFFDET_TRAIN_GEMM_TN_PLAN_INTS 11
+#define EFFDET_TRAIN_DWCONV_PLAN_INTS 13
+int effdet_train_gemm_nt_plan_describe(long long M, int K, int N, int a_levels, long long a_rpi, long long a_img_stride,
+                                       long long a_ld, int c_levels, long long c_rpi, long long c_img_stride, long long c_ld,
+                                       int operands, long long a_scale_rows, int epi, const int* align, int* out, int n);
+int effdet_train_gemm_tn_plan_describe(long long M, int N, int K, int y_levels, long long y_rpi, long long y_img_stride,
+                                       long long y_ld, int x_levels, long long x_rpi, long long x_img_stride, long long x_ld,
+                                       long long x_scale_rows, const int* align, int* out, int n);
+int effdet_train_dwconv_plan_describe(int which, int H, int W, int C, int k, int stride, int B, int* out, int n);
+
 /* ---- the head towers over the whole pyramid in one launch per layer (effdet/efficientdet.py:438-452: conv weights shared by
  * the levels, BatchNorm per level).  "Packed pyramid" = float32 [sum_l B*Hs[l]*Ws[l]][C], level-major: the NHWC tensors of the L
  * levels (L <= 8) one behind the other.  A 1x1 conv over it is ONE GEMM: effdet_train_gemm_nt_levels / _tn_levels are

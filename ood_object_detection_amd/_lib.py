@@ -159,6 +159,11 @@ SIGNATURES = {
     'effdet_train_fpn_input_bwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_int, c_int, c_int, c_int]),
     'effdet_train_dwconv_fwd_parts': (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    'effdet_train_gemm_nt_plan_describe': (c_int, [c_ll, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_int, c_ll, c_ll, c_ll, c_int, c_ll, c_int,
+                                                   P(c_int), P(c_int), c_int]),
+    'effdet_train_gemm_tn_plan_describe': (c_int, [c_ll, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_int, c_ll, c_ll, c_ll, c_ll,
+                                                   P(c_int), P(c_int), c_int]),
+    'effdet_train_dwconv_plan_describe': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, P(c_int), c_int]),
     'effdet_train_dwconv_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int]),
     'effdet_train_se_gate': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1524,8 +1524,11 @@ extern "C" int effdet_train_grads_table(void* stream, const void* table, int n, 
 // ================================================================================================================
 // C ABI
 // ================================================================================================================
-template <int EPI = 0>
-static int launch_gemm_nt(hipStream_t st, GemmNtArgs& p) {
+// What launch_gemm_nt decides from the shape, the row maps and the pointer alignment alone (effdet_train_gemm_nt_plan_describe
+// reports it): the template arguments of gemm_nt_kernel, the store width (GemmNtArgs::vec_out: 1 = 16-byte, 2 = 8-byte, 0 = scalar
+// stores), the grid and the k range of one wave of the split-K form.
+struct GemmNtPlan { int VEC, KS, FAST, vec_out; long long grid; int kchunk; };
+static int gemm_nt_plan(const GemmNtArgs& p, GemmNtPlan& pl) {
     const float* A = p.A; const float* W = p.W; const float* bias = p.bias; float* C = p.C; float* C2 = p.C2;
     const long long M = p.M; const int K = p.K, N = p.N;
     long long gx = (M + 127) / 128;                          // 4 waves x 32 rows
@@ -1535,36 +1538,97 @@ static int launch_gemm_nt(hipStream_t st, GemmNtArgs& p) {
     if (splitk) gx = (M + 31) / 32;
     const bool vec = K % 4 == 0 && p.am.ld % 4 == 0 && p.am.img_stride % 4 == 0 &&
                      reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0;
-    p.vec_out = N % 4 == 0 && p.cm.ld % 4 == 0 && p.cm.img_stride % 4 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
-                (bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 16 == 0) &&
-                (C2 == nullptr || reinterpret_cast<uintptr_t>(C2) % 16 == 0) &&
-                (p.R == nullptr || reinterpret_cast<uintptr_t>(p.R) % 16 == 0) &&
-                (p.mask == nullptr || reinterpret_cast<uintptr_t>(p.mask) % 16 == 0);
-    if (!p.vec_out && N % 2 == 0 && p.cm.ld % 2 == 0 && p.cm.img_stride % 2 == 0 && reinterpret_cast<uintptr_t>(C) % 8 == 0 &&
+    pl.vec_out = N % 4 == 0 && p.cm.ld % 4 == 0 && p.cm.img_stride % 4 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
+                 (bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 16 == 0) &&
+                 (C2 == nullptr || reinterpret_cast<uintptr_t>(C2) % 16 == 0) &&
+                 (p.R == nullptr || reinterpret_cast<uintptr_t>(p.R) % 16 == 0) &&
+                 (p.mask == nullptr || reinterpret_cast<uintptr_t>(p.mask) % 16 == 0);
+    if (!pl.vec_out && N % 2 == 0 && p.cm.ld % 2 == 0 && p.cm.img_stride % 2 == 0 && reinterpret_cast<uintptr_t>(C) % 8 == 0 &&
         (bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 8 == 0) && (C2 == nullptr || reinterpret_cast<uintptr_t>(C2) % 8 == 0) &&
         (p.R == nullptr || reinterpret_cast<uintptr_t>(p.R) % 8 == 0) &&
-        (p.mask == nullptr || reinterpret_cast<uintptr_t>(p.mask) % 8 == 0)) p.vec_out = 2;
+        (p.mask == nullptr || reinterpret_cast<uintptr_t>(p.mask) % 8 == 0)) pl.vec_out = 2;
     if (gx * ((N + 63) / 64) > 0x7fffffffLL) return EFFDET_EINVAL;
-    const dim3 grid((unsigned)(gx * ((N + 63) / 64)));
+    pl.grid = gx * ((N + 63) / 64);
     const bool vec2 = K % 2 == 0 && p.am.ld % 2 == 0 && p.am.img_stride % 2 == 0 &&
                       reinterpret_cast<uintptr_t>(A) % 8 == 0 && reinterpret_cast<uintptr_t>(W) % 8 == 0;
     const bool fast = vec && K >= 4 && p.am.nlev == 0 && p.am.img_stride == 0 && M < 0x7fffffffLL &&
                       (!p.a_scale || (reinterpret_cast<uintptr_t>(p.a_scale) % 16 == 0 && p.a_scale_rpi < 0x7fffffffLL));
-    if (fast) {
+    pl.KS = splitk ? 4 : 1;
+    pl.FAST = fast ? 1 : 0;
+    pl.VEC = (fast || vec) ? 4 : vec2 ? 2 : 1;
+    pl.kchunk = splitk ? (K + 16 * 4 - 1) / (16 * 4) * 16 : 0;       // as gemm_nt_kernel<*, 4> computes it
+    return 0;
+}
+
+template <int EPI = 0>
+static int launch_gemm_nt(hipStream_t st, GemmNtArgs& p) {
+    GemmNtPlan pl;
+    const int rc = gemm_nt_plan(p, pl);
+    if (rc) return rc;
+    p.vec_out = pl.vec_out;
+    const dim3 grid((unsigned)pl.grid);
+    const bool splitk = pl.KS == 4;
+    if (pl.FAST) {
         if (splitk) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, true, EPI>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_nt_kernel<4, 1, true, EPI>), grid, dim3(256), 0, st, p);
         return effdet_check_launch();
     }
     if (splitk) {
-        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, false, EPI>), grid, dim3(256), 0, st, p);
-        else if (vec2) hipLaunchKernelGGL((gemm_nt_kernel<2, 4, false, EPI>), grid, dim3(256), 0, st, p);
+        if (pl.VEC == 4) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, false, EPI>), grid, dim3(256), 0, st, p);
+        else if (pl.VEC == 2) hipLaunchKernelGGL((gemm_nt_kernel<2, 4, false, EPI>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_nt_kernel<1, 4, false, EPI>), grid, dim3(256), 0, st, p);
     } else {
-        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<4, 1, false, EPI>), grid, dim3(256), 0, st, p);
-        else if (vec2) hipLaunchKernelGGL((gemm_nt_kernel<2, 1, false, EPI>), grid, dim3(256), 0, st, p);
+        if (pl.VEC == 4) hipLaunchKernelGGL((gemm_nt_kernel<4, 1, false, EPI>), grid, dim3(256), 0, st, p);
+        else if (pl.VEC == 2) hipLaunchKernelGGL((gemm_nt_kernel<2, 1, false, EPI>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_nt_kernel<1, 1, false, EPI>), grid, dim3(256), 0, st, p);
     }
     return effdet_check_launch();
+}
+
+// a stand-in address with the given residue mod 16, for the plan queries (never dereferenced)
+static float* plan_ptr(int present, int align) { return present ? reinterpret_cast<float*>((uintptr_t)4096 + (uintptr_t)align) : nullptr; }
+static bool plan_align_ok(const int* align, int n) {
+    if (!align) return false;
+    for (int i = 0; i < n; ++i)
+        if (align[i] < 0 || align[i] > 12 || align[i] % 4) return false;
+    return true;
+}
+// side of a plan query: levels != 0 -> the level-packed map (img_stride, ld = pk_img_stride, pk_ld), else make_rowmap's
+static bool plan_rowmap(RowMap& r, int levels, long long rpi, long long img_stride, long long ld, long long M, int cols) {
+    if (levels) {
+        if (img_stride <= 0 || ld < cols || M >= 0x7fffffffLL) return false;
+        r = make_rowmap(0, 0, ld, 1, ld);
+        r.nlev = 1; r.img_stride = img_stride;
+        return true;
+    }
+    r = make_rowmap(rpi, img_stride, ld, M, cols);
+    return true;
+}
+
+// Host-only: what gemm_nt_plan() - the launcher's own decision - chooses; nothing is launched.  `operands`: EFFDET_NT_HAS_* bits;
+// epi 0 / 1 (relu) / 2 (mask, needs EFFDET_NT_HAS_MASK); align[8]: address mod 16 of A, W, C, bias, R, C2, a_scale, mask (absent
+// operands ignored).  Slots: VEC, KS, FAST, EPI, vec_out (4 / 2 / 0 floats per store), grid, kchunk (0 without split-K).
+extern "C" int effdet_train_gemm_nt_plan_describe(long long M, int K, int N, int a_levels, long long a_rpi, long long a_img_stride,
+                                                  long long a_ld, int c_levels, long long c_rpi, long long c_img_stride, long long c_ld,
+                                                  int operands, long long a_scale_rows, int epi, const int* align, int* out, int n) {
+    if (!out || n <= 0 || M <= 0 || K <= 0 || N <= 0 || epi < 0 || epi > 2 || operands < 0 || operands >= 64 || !plan_align_ok(align, 8) ||
+        (a_levels && c_levels)) return EFFDET_EINVAL;
+    const bool has_scale = operands & EFFDET_NT_HAS_A_SCALE, has_mask = operands & EFFDET_NT_HAS_MASK;
+    if (has_mask != (epi == 2) || (has_scale && (a_scale_rows <= 0 || K % 4 || align[6]))) return EFFDET_EINVAL;
+    GemmNtArgs p;
+    p.A = plan_ptr(1, align[0]); p.W = plan_ptr(1, align[1]); p.C = plan_ptr(1, align[2]);
+    p.bias = plan_ptr(operands & EFFDET_NT_HAS_BIAS, align[3]); p.R = plan_ptr(operands & EFFDET_NT_HAS_R, align[4]);
+    p.C2 = plan_ptr(operands & EFFDET_NT_HAS_C2, align[5]); p.a_scale = plan_ptr(has_scale, align[6]); p.mask = plan_ptr(has_mask, align[7]);
+    p.a_scale_rpi = has_scale ? a_scale_rows : 1;
+    p.M = M; p.K = K; p.N = N; p.accumulate = (operands & EFFDET_NT_ACCUMULATE) ? 1 : 0; p.vec_out = 0;
+    if (!plan_rowmap(p.am, a_levels, a_rpi, a_img_stride, a_ld, M, K) || !plan_rowmap(p.cm, c_levels, c_rpi, c_img_stride, c_ld, M, N))
+        return EFFDET_EINVAL;
+    GemmNtPlan pl;
+    if (gemm_nt_plan(p, pl)) return EFFDET_EINVAL;
+    const int v[EFFDET_TRAIN_GEMM_NT_PLAN_INTS] = {pl.VEC, pl.KS, pl.FAST, epi, pl.vec_out == 1 ? 4 : pl.vec_out, (int)pl.grid, pl.kchunk};
+    const int m = n < EFFDET_TRAIN_GEMM_NT_PLAN_INTS ? n : EFFDET_TRAIN_GEMM_NT_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = v[i];
+    return m;
 }
 
 extern "C" int effdet_train_gemm_nt(void* stream, const float* A, long long a_rpi, long long a_img_stride, long long a_ld,
@@ -1657,54 +1721,70 @@ extern "C" long long effdet_train_gemm_tn_workspace_floats(long long M, int N, i
     return (long long)tn_slices(M, N, K) * N * (K + 1);
 }
 
-static int launch_gemm_tn(hipStream_t st, GemmTnArgs& p, float* out, float* workspace, long long workspace_floats) {
+// What launch_gemm_tn decides (effdet_train_gemm_tn_plan_describe reports it): body 0 gemm_tn_kernel<VY, VX>, 1 the pipelined
+// gemm_tn_kernel_v<DENSE, SCALED, VY>, 2 the 128-column gemm_tn_kernel_w<DENSE, VY>; the slices over M and the grid.
+struct GemmTnPlan { int body, VY, VX, DENSE, SCALED, S; long long rows_per_slice; int empty_slices; unsigned gx, gy, gz; };
+static void gemm_tn_plan(const GemmTnArgs& p, GemmTnPlan& pl) {
     const long long M = p.M; const int N = p.N, K = p.K;
     const int S = tn_slices(M, N, K);
-    if (workspace_floats < (long long)S * N * (K + 1)) return EFFDET_EINVAL;
-    p.partial = workspace; p.S = S;
+    pl.S = S;
     long long rps = (M + S - 1) / S;
     rps = (rps + 31) / 32 * 32;
-    p.rows_per_slice = rps;
-    const dim3 grid((unsigned)((N + 31) / 32), (unsigned)((K + 1 + 63) / 64), (unsigned)S);
+    pl.rows_per_slice = rps;
+    pl.empty_slices = S - (int)((M + rps - 1) / rps);         // trailing slices that start past the last row
+    pl.gx = (unsigned)((N + 31) / 32); pl.gy = (unsigned)((K + 1 + 63) / 64); pl.gz = (unsigned)S;
     const bool vy = p.ym.ld % 4 == 0 && p.ym.img_stride % 4 == 0 && reinterpret_cast<uintptr_t>(p.dY) % 16 == 0;
     const bool vx = p.xm.ld % 4 == 0 && p.xm.img_stride % 4 == 0 && reinterpret_cast<uintptr_t>(p.X) % 16 == 0;
     const bool vy2 = N % 2 == 0 && p.ym.ld % 2 == 0 && p.ym.img_stride % 2 == 0 && reinterpret_cast<uintptr_t>(p.dY) % 8 == 0;
+    const bool dense = p.ym.nlev == 0 && p.xm.nlev == 0 && p.ym.img_stride == 0 && p.xm.img_stride == 0;
+    pl.DENSE = 0; pl.SCALED = 0; pl.VX = vx ? 1 : 0;
     if (N >= 256 && vx && K % 4 == 0 && !p.x_scale && ((vy && N % 4 == 0) || vy2)) {
-        const bool dense_w = p.ym.nlev == 0 && p.xm.nlev == 0 && p.ym.img_stride == 0 && p.xm.img_stride == 0;
-        const dim3 gw((unsigned)((N + 127) / 128), (unsigned)((K + 1 + 63) / 64), (unsigned)S);
-        if (vy && N % 4 == 0) {
-            if (dense_w) hipLaunchKernelGGL((gemm_tn_kernel_w<true, 4>), gw, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((gemm_tn_kernel_w<false, 4>), gw, dim3(256), 0, st, p);
-        } else {
-            if (dense_w) hipLaunchKernelGGL((gemm_tn_kernel_w<true, 2>), gw, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((gemm_tn_kernel_w<false, 2>), gw, dim3(256), 0, st, p);
-        }
-        int rcw = effdet_check_launch();
-        if (rcw) return rcw;
-        ReduceSplitArgs rw{workspace, out, N, K, S};
-        const long long rbw = ((long long)N * (K + 1) + 15) / 16;
-        if (rbw > 0x7fffffffLL) return EFFDET_EINVAL;
-        hipLaunchKernelGGL(reduce_split_kernel, dim3((unsigned)rbw), dim3(256), 0, st, rw);
-        return effdet_check_launch();
+        pl.body = 2; pl.DENSE = dense ? 1 : 0; pl.VY = (vy && N % 4 == 0) ? 4 : 2;
+        pl.gx = (unsigned)((N + 127) / 128);
+        return;
     }
     const bool xs_ok = !p.x_scale || (reinterpret_cast<uintptr_t>(p.x_scale) % 16 == 0 && M < 0x7fffffffLL && p.x_scale_rpi < 0x7fffffffLL);
-    const bool dense = p.ym.nlev == 0 && p.xm.nlev == 0 && p.ym.img_stride == 0 && p.xm.img_stride == 0;
-    if (vy && vx && N % 4 == 0 && K % 4 == 0 && xs_ok) {
-        if (dense && p.x_scale) hipLaunchKernelGGL((gemm_tn_kernel_v<true, true, 4>), grid, dim3(256), 0, st, p);
+    if (vy && vx && N % 4 == 0 && K % 4 == 0 && xs_ok) { pl.body = 1; pl.DENSE = dense ? 1 : 0; pl.SCALED = p.x_scale ? 1 : 0; pl.VY = 4; }
+    else if (vy2 && vx && K % 4 == 0 && !p.x_scale) { pl.body = 1; pl.DENSE = dense ? 1 : 0; pl.VY = 2; }
+    else if (vy && vx) { pl.body = 0; pl.VY = 4; }
+    else if (vx) { pl.body = 0; pl.VY = vy2 ? 2 : 1; }
+    else if (vy) { pl.body = 0; pl.VY = 4; }
+    else { pl.body = 0; pl.VY = 1; }
+}
+
+static int launch_gemm_tn(hipStream_t st, GemmTnArgs& p, float* out, float* workspace, long long workspace_floats) {
+    const int N = p.N, K = p.K;
+    GemmTnPlan pl;
+    gemm_tn_plan(p, pl);
+    const int S = pl.S;
+    if (workspace_floats < (long long)S * N * (K + 1)) return EFFDET_EINVAL;
+    p.partial = workspace; p.S = S;
+    p.rows_per_slice = pl.rows_per_slice;
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    const bool dense = pl.DENSE != 0;
+    if (pl.body == 2) {
+        if (pl.VY == 4) {
+            if (dense) hipLaunchKernelGGL((gemm_tn_kernel_w<true, 4>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((gemm_tn_kernel_w<false, 4>), grid, dim3(256), 0, st, p);
+        } else {
+            if (dense) hipLaunchKernelGGL((gemm_tn_kernel_w<true, 2>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((gemm_tn_kernel_w<false, 2>), grid, dim3(256), 0, st, p);
+        }
+    } else if (pl.body == 1 && pl.VY == 4) {
+        if (dense && pl.SCALED) hipLaunchKernelGGL((gemm_tn_kernel_v<true, true, 4>), grid, dim3(256), 0, st, p);
         else if (dense) hipLaunchKernelGGL((gemm_tn_kernel_v<true, false, 4>), grid, dim3(256), 0, st, p);
-        else if (p.x_scale) hipLaunchKernelGGL((gemm_tn_kernel_v<false, true, 4>), grid, dim3(256), 0, st, p);
+        else if (pl.SCALED) hipLaunchKernelGGL((gemm_tn_kernel_v<false, true, 4>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_tn_kernel_v<false, false, 4>), grid, dim3(256), 0, st, p);
-    }
-    else if (vy2 && vx && K % 4 == 0 && !p.x_scale) {
+    } else if (pl.body == 1) {
         if (dense) hipLaunchKernelGGL((gemm_tn_kernel_v<true, false, 2>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_tn_kernel_v<false, false, 2>), grid, dim3(256), 0, st, p);
     }
-    else if (vy && vx) hipLaunchKernelGGL((gemm_tn_kernel<4, true>), grid, dim3(256), 0, st, p);
-    else if (vx) {
-        if (vy2) hipLaunchKernelGGL((gemm_tn_kernel<2, true>), grid, dim3(256), 0, st, p);
+    else if (pl.VY == 4 && pl.VX) hipLaunchKernelGGL((gemm_tn_kernel<4, true>), grid, dim3(256), 0, st, p);
+    else if (pl.VX) {
+        if (pl.VY == 2) hipLaunchKernelGGL((gemm_tn_kernel<2, true>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_tn_kernel<1, true>), grid, dim3(256), 0, st, p);
     }
-    else if (vy) hipLaunchKernelGGL((gemm_tn_kernel<4, false>), grid, dim3(256), 0, st, p);
+    else if (pl.VY == 4) hipLaunchKernelGGL((gemm_tn_kernel<4, false>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((gemm_tn_kernel<1, false>), grid, dim3(256), 0, st, p);
     int rc = effdet_check_launch();
     if (rc) return rc;
@@ -1713,6 +1793,30 @@ static int launch_gemm_tn(hipStream_t st, GemmTnArgs& p, float* out, float* work
     if (rb > 0x7fffffffLL) return EFFDET_EINVAL;
     hipLaunchKernelGGL(reduce_split_kernel, dim3((unsigned)rb), dim3(256), 0, st, r);
     return effdet_check_launch();
+}
+
+// Host-only: what gemm_tn_plan() - the launcher's own decision - chooses; nothing is launched.  x_scale_rows > 0: the scaled entry
+// (dense rows, K % 4 == 0); align[3]: address mod 16 of dY, X, x_scale.  Slots: body (0 plain / 1 v / 2 w), VY, VX (plain body),
+// DENSE, SCALED, S, rows_per_slice, empty trailing slices, grid x / y / z.
+extern "C" int effdet_train_gemm_tn_plan_describe(long long M, int N, int K, int y_levels, long long y_rpi, long long y_img_stride,
+                                                  long long y_ld, int x_levels, long long x_rpi, long long x_img_stride, long long x_ld,
+                                                  long long x_scale_rows, const int* align, int* out, int n) {
+    if (!out || n <= 0 || M <= 0 || N <= 0 || K <= 0 || x_scale_rows < 0 || !plan_align_ok(align, 3) || x_levels) return EFFDET_EINVAL;
+    const bool scaled = x_scale_rows > 0;
+    if (scaled && (K % 4 || align[2] || y_levels || y_rpi > 0 || x_rpi > 0 || y_ld > 0 || x_ld > 0)) return EFFDET_EINVAL;
+    GemmTnArgs p;
+    p.dY = plan_ptr(1, align[0]); p.X = plan_ptr(1, align[1]); p.x_scale = plan_ptr(scaled, align[2]);
+    p.x_scale_rpi = scaled ? x_scale_rows : 1;
+    p.M = M; p.N = N; p.K = K; p.partial = nullptr; p.S = 0; p.rows_per_slice = 0;
+    if (!plan_rowmap(p.ym, y_levels, y_rpi, y_img_stride, y_ld, M, N) || !plan_rowmap(p.xm, 0, x_rpi, x_img_stride, x_ld, M, K))
+        return EFFDET_EINVAL;
+    GemmTnPlan pl;
+    gemm_tn_plan(p, pl);
+    const int v[EFFDET_TRAIN_GEMM_TN_PLAN_INTS] = {pl.body, pl.VY, pl.body == 0 ? pl.VX : 1, pl.DENSE, pl.SCALED, pl.S, (int)pl.rows_per_slice,
+                                                   pl.empty_slices, (int)pl.gx, (int)pl.gy, (int)pl.gz};
+    const int m = n < EFFDET_TRAIN_GEMM_TN_PLAN_INTS ? n : EFFDET_TRAIN_GEMM_TN_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = v[i];
+    return m;
 }
 
 extern "C" int effdet_train_gemm_tn(void* stream, const float* dY, long long y_rpi, long long y_img_stride, long long y_ld,
@@ -1809,6 +1913,12 @@ extern "C" int effdet_train_dwconv_fwd(void* stream, const float* X, float* Z, f
     return effdet_check_launch();
 }
 
+// -> workgroups of the d input kernel; *s1: the 4-pixel stride-1 kernel (dw_bwd_dx_s1_kernel) or the general one
+static long long dw_bwd_dx_plan(const DwBwdArgs& a, int* s1) {
+    *s1 = a.stride == 1;
+    const long long total = *s1 ? (long long)a.B * a.H * ((a.W + 3) / 4) * (a.C / 4) : (long long)a.B * a.H * a.W * (a.C / 4);
+    return (total + 255) / 256;
+}
 static int launch_dw_bwd_dx(void* stream, const float* dY, const float* taps, const float* Z, float* dX,
                             int B, int H, int W, int C, int k, int stride);
 extern "C" int effdet_train_dwconv_bwd_dx(void* stream, const float* dY, const float* taps, float* dX,
@@ -1829,18 +1939,12 @@ static int launch_dw_bwd_dx(void* stream, const float* dY, const float* taps, co
     if (!dY || !taps || !dX || dw_fill(a, B, H, W, C, k, stride)) return EFFDET_EINVAL;
     a.dY = dY; a.taps = taps; a.dX = dX; a.X = nullptr; a.partial = nullptr; a.segs_per_chunk = 0; a.seg = 0; a.Z = Z;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (stride == 1) {
-        const long long total = (long long)B * H * ((W + 3) / 4) * (C / 4);
-        const long long blocks = (total + 255) / 256;
-        if (blocks > 0x7fffffffLL) return EFFDET_EINVAL;
-        if (k == 3) hipLaunchKernelGGL(dw_bwd_dx_s1_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(dw_bwd_dx_s1_kernel<5>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-        return effdet_check_launch();
-    }
-    const long long total = (long long)B * H * W * (C / 4);
-    const long long blocks = (total + 255) / 256;
+    int s1;
+    const long long blocks = dw_bwd_dx_plan(a, &s1);
     if (blocks > 0x7fffffffLL) return EFFDET_EINVAL;
-    hipLaunchKernelGGL(dw_bwd_dx_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    if (s1 && k == 3) hipLaunchKernelGGL(dw_bwd_dx_s1_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    else if (s1) hipLaunchKernelGGL(dw_bwd_dx_s1_kernel<5>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(dw_bwd_dx_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
     return effdet_check_launch();
 }
 
@@ -1884,6 +1988,39 @@ extern "C" int effdet_train_dwconv_bwd_dw(void* stream, const float* dY, const f
     int rc = effdet_check_launch();
     if (rc) return rc;
     return effdet_launch_reduce_mid_tr(st, workspace, 1, (int)chunks, (long long)(k * k + 1) * C, out, 0, 1.0f, cmajor ? C : 0, k * k);
+}
+
+// Host-only: the geometry that the depthwise entries derive (dwf_fill, dw_bwd_dx_plan, dw_chunks - the launchers' own code);
+// nothing is launched.  which 0 forward / 1 d input / 2 d taps; k may carry EFFDET_PAD_SYMMETRIC.  Slots (those of the other
+// entries 0): Ho, Wo, pad_t, pad_l, channel groups of 64, then forward: blocks_per_image, strips_x; d input: kernel (1 = the
+// 4-pixel stride-1 form, 0 = general), workgroups; d taps: seg, segments per row, segs_per_chunk, chunks.
+extern "C" int effdet_train_dwconv_plan_describe(int which, int H, int W, int C, int k, int stride, int B, int* out, int n) {
+    if (!out || n <= 0 || which < 0 || which > 2) return EFFDET_EINVAL;
+    int v[EFFDET_TRAIN_DWCONV_PLAN_INTS] = {0};
+    if (which == 0) {
+        DwFwdArgs a;
+        if (dwf_fill(a, B, H, W, C, k, stride)) return EFFDET_EINVAL;
+        v[0] = a.Ho; v[1] = a.Wo; v[2] = a.pad_t; v[3] = a.pad_l; v[4] = (C + 63) / 64; v[5] = a.blocks_per_image; v[6] = a.strips_x;
+    } else {
+        DwBwdArgs a;
+        if (dw_fill(a, B, H, W, C, k, stride)) return EFFDET_EINVAL;
+        v[0] = a.Ho; v[1] = a.Wo; v[2] = a.pad_t; v[3] = a.pad_l; v[4] = (C + 63) / 64;
+        if (which == 1) {
+            int s1;
+            const long long blocks = dw_bwd_dx_plan(a, &s1);
+            if (blocks > 0x7fffffffLL) return EFFDET_EINVAL;
+            v[7] = s1; v[8] = (int)blocks;
+        } else {
+            long long per;
+            int seg;
+            const long long chunks = dw_chunks(a, &per, &seg);
+            if (chunks > 0x7fffffffLL || per > 0x7fffffffLL) return EFFDET_EINVAL;
+            v[9] = seg; v[10] = (a.Wo + seg - 1) / seg; v[11] = (int)per; v[12] = (int)chunks;
+        }
+    }
+    const int m = n < EFFDET_TRAIN_DWCONV_PLAN_INTS ? n : EFFDET_TRAIN_DWCONV_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = v[i];
+    return m;
 }
 
 extern "C" int effdet_train_ew(void* stream, int op, float* out, const float* a, const float* b, const float* c,
