@@ -678,6 +678,36 @@ int effdet_ood_image_score(void* stream, const float* energy, int B, long long N
  * counts[0] = #{(i,j): pos_i > neg_j}, counts[1] = #{pos_i == neg_j};  AUROC = (counts[0] + counts[1]/2) / (n_pos*n_neg). */
 int effdet_auroc_counts(void* stream, const float* pos, const float* neg, int n_pos, int n_neg, unsigned long long* counts);
 
+/* ---- detection-level OOD evaluation (csrc/ood_eval.hip): AUROC, AUPR in / out, FPR at a TPR level ----
+ * Two multisets of float32 scores, pos (in-distribution, the positive class) and neg (OOD); higher = more in-distribution.
+ * Each side is a flat device buffer of `capacity` floats (<= 2^27) filled from a device cursor; `state` is 4 unsigned words
+ * on the device, zeroed by the caller to reset: {pos cursor, pos flags, neg cursor, neg flags}, side flags 1 = a NaN was
+ * appended, 2 = the capacity overflowed (the surplus was dropped).  No call below synchronises with the host or allocates, so
+ * all of them can be captured in a graph; the workspace (size from the query, pure host code like the tile query) is shared
+ * by all three and must not be used by anything else between the sort and the metrics call. */
+long long effdet_ood_eval_workspace_bytes(long long capacity_pos, long long capacity_neg);
+/* keys one workgroup handles per radix pass */
+int effdet_ood_eval_sort_tile(void);
+/* byte offset in the workspace of the sorted float32 scores of side 0 (pos) / 1 (neg) after the sort call (pure host code) */
+long long effdet_ood_eval_sorted_offset(long long capacity_pos, long long capacity_neg, int side);
+/* Appends the kept entries of the [B, K] matrix scores[b * pitch + j * stride] to `buffer` in (b, j) order: entry (b, j) is
+ * kept when j < count[b] (count NULL: all K; int32, or int64 when count_is_int64) and, with det_score != NULL, when
+ * det_score[b * det_pitch + j * det_stride] >= min_score.  negate: the value is stored negated (energy -> score).  -0.0 is
+ * stored as +0.0.  side_state = state + 2 * side.  B * K <= 2^27.  Three launches: counts, bases, writes. */
+int effdet_ood_eval_append(void* stream, const float* scores, long long pitch, long long stride, int B, int K,
+                           const void* count, int count_is_int64, const float* det_score, long long det_pitch,
+                           long long det_stride, float min_score, int negate, float* buffer, long long capacity,
+                           unsigned int* side_state, void* workspace, long long workspace_bytes);
+/* Sorts both sides (keys only, 4 radix passes of histogram / scan / scatter launches); the buffers are left as they are. */
+int effdet_ood_eval_sort(void* stream, const float* pos, long long capacity_pos, const float* neg, long long capacity_neg,
+                         const unsigned int* state, void* workspace, long long workspace_bytes);
+/* After the sort: result = 12 words of 8 bytes {P, N, pairs_gt, pairs_eq, tp, fp, flags, k} as uint64, {aupr_in, aupr_out}
+ * as float64, the float32 threshold in the low half of word 10, 0.  flags = pos side flags | neg side flags << 2 | 16 (pos
+ * empty) | 32 (neg empty).  The threshold is the k-th largest positive, k the smallest integer with k / P >= level (float64
+ * division); tp / fp count the positives / negatives >= it.  0 < level <= 1.  Two launches; bit-identical from run to run. */
+int effdet_ood_eval_metrics(void* stream, long long capacity_pos, long long capacity_neg, const unsigned int* state,
+                            void* workspace, long long workspace_bytes, double level, void* result);
+
 /* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
 
 /* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at

@@ -73,6 +73,13 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p]),
     'effdet_ood_image_score': (c_int, [c_void_p, c_void_p, c_int, c_ll, c_void_p]),
     'effdet_auroc_counts': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'effdet_ood_eval_workspace_bytes': (c_ll, [c_ll, c_ll]),
+    'effdet_ood_eval_sort_tile': (c_int, []),
+    'effdet_ood_eval_sorted_offset': (c_ll, [c_ll, c_ll, c_int]),
+    'effdet_ood_eval_append': (c_int, [c_void_p, c_void_p, c_ll, c_ll, c_int, c_int, c_void_p, c_int, c_void_p, c_ll, c_ll, c_float,
+                                       c_int, c_void_p, c_ll, c_void_p, c_void_p, c_ll]),
+    'effdet_ood_eval_sort': (c_int, [c_void_p, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_ll]),
+    'effdet_ood_eval_metrics': (c_int, [c_void_p, c_ll, c_ll, c_void_p, c_void_p, c_ll, c_double, c_void_p]),
     'effdet_sepconv_meta': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_sepconv_tiles': (c_int, [c_int, c_int, c_void_p, c_void_p]),

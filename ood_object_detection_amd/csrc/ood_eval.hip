@@ -1,0 +1,506 @@
+// Detection-level OOD evaluation on the device: AUROC pair counts, AUPR (in / out) and FPR at a TPR level over two multisets of
+// float32 scores, `pos` (in-distribution, P values) and `neg` (OOD, N values); a higher score means more in-distribution.
+//
+//   append   [B, K] score matrix -> one side's flat buffer, in (b, j) order from a cursor that lives on the device:
+//            block counts -> bases (one workgroup, also moves the cursor) -> writes.  No atomic decides a position.
+//   sort     both sides through the same launches (a two-entry problem table, blockIdx.y = side): LSD radix sort of the 32-bit
+//            order-preserving keys, 8 bits a pass, every pass = histogram launch, scan launch, stable scatter launch.
+//   metrics  everything follows from the two sorted arrays by binary search: one launch of per-workgroup partials (uint64 pair
+//            counts, float64 AUPR terms), one workgroup that adds them in a fixed order and fills the result block.
+//
+// Launch boundaries are the only synchronisation between workgroups.  Every loop has a trip count known at its entry, every
+// scatter index is compared with the segment length before the store, and the element counts are read from the device cursors
+// (grids are sized by the capacities; workgroups beyond the live count exit), so the host never reads anything back.
+#include "common.h"
+
+// all lanes of a wave have issued the LDS accesses before this point (the CPU model of tools/simt_model defines its own)
+#ifndef OE_WAVE_SYNC
+#define OE_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
+#endif
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int OE_THREADS = 256;
+constexpr int OE_SORT_ITEMS = 16;
+constexpr int OE_SORT_TILE = OE_THREADS * OE_SORT_ITEMS;          // keys of one workgroup per pass
+constexpr int OE_APPEND_ITEMS = 8;
+constexpr int OE_APPEND_TILE = OE_THREADS * OE_APPEND_ITEMS;      // matrix entries of one workgroup
+constexpr int OE_MET_ITEMS = 8;
+constexpr int OE_MET_TILE = OE_THREADS * OE_MET_ITEMS;            // sorted scores of one workgroup
+constexpr long long OE_MAX_SCORES = 1ll << 27;                    // per side, and per append call
+constexpr long long OE_APPEND_MAX_BLOCKS = OE_MAX_SCORES / OE_APPEND_TILE;
+
+// flag bits of a side's state word 1, and of the result block
+constexpr unsigned OE_SIDE_NAN = 1u, OE_SIDE_OVERFLOW = 2u;
+constexpr unsigned OE_RES_EMPTY_IN = 16u, OE_RES_EMPTY_OOD = 32u;
+
+// ---- workspace layout (host) -------------------------------------------------------------------------------------------------
+struct OeLayout {
+    long long append_counts;                    // [OE_APPEND_MAX_BLOCKS] unsigned: kept entries per append workgroup, then bases
+    long long keys_a[2], keys_b[2];             // [capacity] unsigned each; the sorted float32 scores end in keys_b
+    long long hist[2];                          // [256][tiles] unsigned: digit counts per tile, then exclusive tile prefixes
+    long long totals[2];                        // [256] unsigned: digit totals of the pass
+    long long part_gt[2], part_eq[2], part_ap[2];   // [metric blocks] partials
+    long long total;
+    unsigned tiles[2], mblocks[2];
+};
+
+bool oe_layout(long long cap_pos, long long cap_neg, OeLayout* L) {
+    if (cap_pos < 1 || cap_neg < 1 || cap_pos > OE_MAX_SCORES || cap_neg > OE_MAX_SCORES) return false;
+    long long off = 0;
+    auto take = [&off](long long bytes) { const long long o = off; off += (bytes + 255) & ~255ll; return o; };
+    L->append_counts = take(OE_APPEND_MAX_BLOCKS * 4);
+    const long long caps[2] = {cap_pos, cap_neg};
+    for (int s = 0; s < 2; ++s) {
+        L->tiles[s] = (unsigned)((caps[s] + OE_SORT_TILE - 1) / OE_SORT_TILE);
+        L->mblocks[s] = (unsigned)((caps[s] + OE_MET_TILE - 1) / OE_MET_TILE);
+        L->keys_a[s] = take(caps[s] * 4);
+        L->keys_b[s] = take(caps[s] * 4);
+        L->hist[s] = take(256ll * L->tiles[s] * 4);
+        L->totals[s] = take(256 * 4);
+        L->part_gt[s] = take((long long)L->mblocks[s] * 8);
+        L->part_eq[s] = take((long long)L->mblocks[s] * 8);
+        L->part_ap[s] = take((long long)L->mblocks[s] * 8);
+    }
+    L->total = off;
+    return true;
+}
+
+// ---- small device helpers ----------------------------------------------------------------------------------------------------
+DEV unsigned oe_min(unsigned a, unsigned b) { return a < b ? a : b; }
+DEV unsigned oe_popc(u64 m) { return (unsigned)__builtin_popcountll(m); }
+// float32 bits -> key whose unsigned order is the order of the floats, and back
+DEV unsigned oe_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : (bits ^ 0x80000000u); }
+DEV unsigned oe_unkey(unsigned key) { return (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key; }
+// largest power of two <= n (0 for 0)
+DEV unsigned oe_floor_pow2(unsigned n) {
+    n |= n >> 1; n |= n >> 2; n |= n >> 4; n |= n >> 8; n |= n >> 16;
+    return n - (n >> 1);
+}
+// a[0 .. n) holds float32 bits in ascending order: the number of entries whose key is < k (strict == 0) or <= k (strict != 0).
+// The trip count follows from n alone, and every read is at an index < n.
+DEV unsigned oe_bound(const unsigned* a, unsigned n, unsigned k, int upper) {
+    unsigned lo = 0;
+    for (unsigned step = oe_floor_pow2(n); step > 0; step >>= 1) {
+        const unsigned nxt = lo + step;
+        if (nxt <= n) {
+            const unsigned v = oe_key(a[nxt - 1]);
+            if (upper ? v <= k : v < k) lo = nxt;
+        }
+    }
+    return lo;
+}
+
+// All OE_THREADS threads call these; sh: [OE_THREADS] of T in LDS.  Fixed order, so a float64 sum has the same bits every run.
+template <typename T> DEV T oe_block_sum(T v, T* sh, int tid) {
+    sh[tid] = v;
+    __syncthreads();
+    for (int s = OE_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
+        __syncthreads();
+    }
+    const T r = sh[0];
+    __syncthreads();
+    return r;
+}
+DEV unsigned oe_block_excl_scan(unsigned v, unsigned* sh, int tid, unsigned* total) {
+    sh[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < OE_THREADS; off <<= 1) {
+        const unsigned t = tid >= off ? sh[tid - off] : 0u;
+        __syncthreads();
+        sh[tid] += t;
+        __syncthreads();
+    }
+    const unsigned incl = sh[tid];
+    *total = sh[OE_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+// ---- append ------------------------------------------------------------------------------------------------------------------
+struct OeAppend {
+    const float* scores; long long pitch, stride;
+    const void* count; int count_i64;
+    const float* det; long long det_pitch, det_stride; float min_score;
+    int negate, K;
+    unsigned total;                             // B * K
+    float* buffer; unsigned capacity;
+    unsigned* state;                            // the side's {cursor, flags}
+    unsigned* counts; unsigned nblocks;
+};
+
+// is entry i = b * K + j kept?  src: its offset in `scores`
+DEV bool oe_keep(const OeAppend& a, unsigned i, long long* src) {
+    if (i >= a.total) return false;
+    const unsigned b = i / (unsigned)a.K, j = i - b * (unsigned)a.K;
+    if (a.count) {
+        const long long c = a.count_i64 ? reinterpret_cast<const long long*>(a.count)[b] : (long long)reinterpret_cast<const int*>(a.count)[b];
+        if ((long long)j >= c) return false;
+    }
+    if (a.det && !(a.det[(long long)b * a.det_pitch + (long long)j * a.det_stride] >= a.min_score)) return false;
+    *src = (long long)b * a.pitch + (long long)j * a.stride;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void oe_append_count_kernel(OeAppend a) {
+    __shared__ unsigned sh[OE_THREADS];
+    const int tid = threadIdx.x;
+    const unsigned base = (unsigned)blockIdx.x * OE_APPEND_TILE;
+    unsigned c = 0;
+    for (int r = 0; r < OE_APPEND_ITEMS; ++r) {
+        long long src;
+        c += oe_keep(a, base + r * OE_THREADS + tid, &src) ? 1u : 0u;
+    }
+    const unsigned tot = oe_block_sum<unsigned>(c, sh, tid);
+    if (tid == 0) a.counts[blockIdx.x] = tot;
+}
+
+// one workgroup: counts -> first positions of the workgroups, and the cursor moves (clamped to the capacity, overflow flagged)
+__global__ __launch_bounds__(256) void oe_append_base_kernel(OeAppend a) {
+    __shared__ unsigned sh[OE_THREADS];
+    const int tid = threadIdx.x;
+    const unsigned c0 = oe_min(a.state[0], a.capacity);
+    const unsigned chunk = (a.nblocks + OE_THREADS - 1) / OE_THREADS;
+    const unsigned lo = oe_min((unsigned)tid * chunk, a.nblocks), hi = oe_min(lo + chunk, a.nblocks);
+    unsigned sum = 0;
+    for (unsigned k = lo; k < hi; ++k) sum += a.counts[k];
+    unsigned total;
+    unsigned run = c0 + oe_block_excl_scan(sum, sh, tid, &total);        // the scan's barriers order the read of the cursor before its write
+    for (unsigned k = lo; k < hi; ++k) { const unsigned c = a.counts[k]; a.counts[k] = run; run += c; }
+    if (tid == 0) {
+        const u64 end = (u64)c0 + total;
+        if (end > a.capacity) a.state[1] |= OE_SIDE_OVERFLOW;
+        a.state[0] = end > a.capacity ? a.capacity : (unsigned)end;
+    }
+}
+
+// wave w of a workgroup owns entries [w * 512, (w + 1) * 512) of its tile, 64 consecutive ones per round: positions follow (b, j)
+__global__ __launch_bounds__(256) void oe_append_write_kernel(OeAppend a) {
+    __shared__ unsigned wsum[OE_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned base = (unsigned)blockIdx.x * OE_APPEND_TILE + (unsigned)wave * (64 * OE_APPEND_ITEMS);
+    const u64 below = (1ull << lane) - 1ull;
+    long long src[OE_APPEND_ITEMS];
+    unsigned rank[OE_APPEND_ITEMS];
+    unsigned keep = 0, wtot = 0;
+#pragma unroll
+    for (int r = 0; r < OE_APPEND_ITEMS; ++r) {
+        src[r] = 0;
+        const bool k = oe_keep(a, base + r * 64 + lane, &src[r]);
+        const u64 bal = __ballot(k);
+        rank[r] = wtot + oe_popc(bal & below);
+        wtot += oe_popc(bal);
+        keep |= (k ? 1u : 0u) << r;
+    }
+    if (lane == 0) wsum[wave] = wtot;
+    __syncthreads();
+    unsigned first = a.counts[blockIdx.x];
+    for (int w = 0; w < OE_THREADS / 64; ++w) first += w < wave ? wsum[w] : 0u;
+    bool nan = false;
+#pragma unroll
+    for (int r = 0; r < OE_APPEND_ITEMS; ++r) {
+        if (keep & (1u << r)) {
+            float v = a.scores[src[r]];
+            if (a.negate) v = -v;
+            if (v != v) nan = true;
+            if (v == 0.f) v = 0.f;                                      // -0.0 is stored as +0.0: the two tie
+            const unsigned p = first + rank[r];
+            if (p < a.capacity) a.buffer[p] = v;                        // beyond the capacity: dropped (the base launch set the flag)
+        }
+    }
+    if (nan) atomicOr(&a.state[1], OE_SIDE_NAN);                        // an OR of a flag bit: no order to depend on
+}
+
+// ---- sort --------------------------------------------------------------------------------------------------------------------
+struct OeSortSide {
+    const unsigned* src; unsigned* dst;
+    const unsigned* cursor;                     // live count = min(*cursor, capacity)
+    unsigned* hist; unsigned* totals;
+    unsigned capacity, tiles;                   // tiles by capacity: the row pitch of hist
+};
+struct OeSortTable { OeSortSide s[2]; int shift, first, last; };      // first: src holds float bits; last: dst receives float bits
+
+DEV unsigned oe_sort_load(const OeSortSide& S, const OeSortTable& t, unsigned i) {
+    const unsigned v = S.src[i];
+    return t.first ? oe_key(v) : v;
+}
+
+__global__ __launch_bounds__(256) void oe_sort_hist_kernel(OeSortTable t) {
+    __shared__ unsigned h[256];
+    const OeSortSide S = t.s[blockIdx.y];
+    const int tid = threadIdx.x;
+    const unsigned n = oe_min(S.cursor[0], S.capacity), tile = blockIdx.x;
+    if (tile >= (n + OE_SORT_TILE - 1) / OE_SORT_TILE) return;          // the same for the whole workgroup
+    h[tid] = 0;
+    __syncthreads();
+    for (int r = 0; r < OE_SORT_ITEMS; ++r) {
+        const unsigned i = tile * OE_SORT_TILE + r * OE_THREADS + tid;
+        if (i < n) atomicAdd(&h[(oe_sort_load(S, t, i) >> t.shift) & 255u], 1u);      // integer counts in LDS: order independent
+    }
+    __syncthreads();
+    S.hist[(unsigned)tid * S.tiles + tile] = h[tid];
+}
+
+// workgroup d of a side: exclusive prefix of digit d's counts over the live tiles (in place), and the digit's total
+__global__ __launch_bounds__(256) void oe_sort_scan_kernel(OeSortTable t) {
+    __shared__ unsigned sh[OE_THREADS];
+    const OeSortSide S = t.s[blockIdx.y];
+    const int tid = threadIdx.x;
+    const unsigned n = oe_min(S.cursor[0], S.capacity), ntiles = (n + OE_SORT_TILE - 1) / OE_SORT_TILE;
+    unsigned* row = S.hist + (unsigned)blockIdx.x * S.tiles;
+    const unsigned chunk = (ntiles + OE_THREADS - 1) / OE_THREADS;
+    const unsigned lo = oe_min((unsigned)tid * chunk, ntiles), hi = oe_min(lo + chunk, ntiles);
+    unsigned sum = 0;
+    for (unsigned k = lo; k < hi; ++k) sum += row[k];
+    unsigned total;
+    unsigned run = oe_block_excl_scan(sum, sh, tid, &total);
+    for (unsigned k = lo; k < hi; ++k) { const unsigned c = row[k]; row[k] = run; run += c; }
+    if (tid == 0) S.totals[blockIdx.x] = total;
+}
+
+// Stable scatter of one tile.  Wave w owns keys [w * 1024, (w + 1) * 1024) of the tile, 64 consecutive ones per round.  A key's
+// rank among the equal digits of its wave = the wave's running count of the digit + the equal digits in lower lanes (ballots);
+// the waves' counts are then prefixed per digit on top of (digits below in the array) + (this digit in earlier tiles).
+__global__ __launch_bounds__(256) void oe_sort_scatter_kernel(OeSortTable t) {
+    __shared__ unsigned wcnt[OE_THREADS / 64][256];
+    __shared__ unsigned sh[OE_THREADS];
+    const OeSortSide S = t.s[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned n = oe_min(S.cursor[0], S.capacity), tile = blockIdx.x;
+    if (tile >= (n + OE_SORT_TILE - 1) / OE_SORT_TILE) return;
+    for (int w = 0; w < OE_THREADS / 64; ++w) wcnt[w][tid] = 0;
+    unsigned total;
+    const unsigned digit_first = oe_block_excl_scan(S.totals[tid], sh, tid, &total) + S.hist[(unsigned)tid * S.tiles + tile];
+    // (the scan's barriers also publish the zeroed counters)
+    const u64 below = (1ull << lane) - 1ull;
+    const unsigned seg = tile * OE_SORT_TILE + (unsigned)wave * (64 * OE_SORT_ITEMS);
+    unsigned key[OE_SORT_ITEMS], rank[OE_SORT_ITEMS];
+#pragma unroll
+    for (int r = 0; r < OE_SORT_ITEMS; ++r) {
+        const unsigned i = seg + r * 64 + lane;
+        const bool valid = i < n;
+        const unsigned k = valid ? oe_sort_load(S, t, i) : 0xFFFFFFFFu;
+        const unsigned d = (k >> t.shift) & 255u;
+        u64 same = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const u64 bal = __ballot(bit);
+            same &= bit ? bal : ~bal;
+        }
+        const unsigned lower = oe_popc(same & below);
+        const unsigned prev = valid ? wcnt[wave][d] : 0u;
+        OE_WAVE_SYNC();
+        if (valid && lower == 0) wcnt[wave][d] = prev + oe_popc(same);     // one lane per digit present in the round
+        OE_WAVE_SYNC();
+        key[r] = k;
+        rank[r] = prev + lower;
+    }
+    __syncthreads();
+    {   // thread d: the waves' counts of digit d -> first positions
+        unsigned run = digit_first;
+        for (int w = 0; w < OE_THREADS / 64; ++w) { const unsigned c = wcnt[w][tid]; wcnt[w][tid] = run; run += c; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < OE_SORT_ITEMS; ++r) {
+        const unsigned i = seg + r * 64 + lane;
+        if (i < n) {
+            const unsigned p = wcnt[wave][(key[r] >> t.shift) & 255u] + rank[r];
+            if (p < n) S.dst[p] = t.last ? oe_unkey(key[r]) : key[r];
+        }
+    }
+}
+
+// ---- metrics -----------------------------------------------------------------------------------------------------------------
+struct OeMetrics {
+    const unsigned* sorted[2];                  // float32 bits, ascending
+    const unsigned* state;                      // {cursor, flags} of pos, then of neg
+    unsigned capacity[2];
+    u64* part_gt[2]; u64* part_eq[2]; double* part_ap[2];
+    double level;
+    u64* result;
+};
+
+// blockIdx.y = 0: the positives' shares of pairs_gt / pairs_eq and the terms of aupr_in; 1: the terms of aupr_out
+__global__ __launch_bounds__(256) void oe_metrics_part_kernel(OeMetrics m) {
+    __shared__ u64 shu[OE_THREADS];
+    __shared__ double shd[OE_THREADS];
+    const int tid = threadIdx.x, side = blockIdx.y;
+    const unsigned P = oe_min(m.state[0], m.capacity[0]), N = oe_min(m.state[2], m.capacity[1]);
+    const unsigned n_own = side == 0 ? P : N, n_other = side == 0 ? N : P;
+    if (P == 0 || N == 0 || (unsigned)blockIdx.x * OE_MET_TILE >= n_own) return;
+    const unsigned* own = m.sorted[side];
+    const unsigned* other = m.sorted[1 - side];
+    u64 gt = 0, eq = 0;
+    double ap = 0.0;
+    for (int r = 0; r < OE_MET_ITEMS; ++r) {
+        const unsigned i = (unsigned)blockIdx.x * OE_MET_TILE + r * OE_THREADS + tid;
+        if (i < n_own) {
+            const unsigned k = oe_key(own[i]);
+            const bool group_end = i + 1 == n_own || oe_key(own[i + 1]) != k;
+            if (side == 0) {
+                const unsigned lb = oe_bound(other, n_other, k, 0), ub = oe_bound(other, n_other, k, 1);
+                gt += lb; eq += ub - lb;
+                if (group_end) {
+                    const unsigned first = oe_bound(own, n_own, k, 0);
+                    const unsigned c = i + 1 - first, tp = n_own - first, fp = n_other - lb;
+                    ap += ((double)c / (double)P) * ((double)tp / (double)((u64)tp + fp));
+                }
+            } else if (group_end) {
+                const unsigned first = oe_bound(own, n_own, k, 0);
+                const unsigned c = i + 1 - first, le_own = i + 1, le_other = oe_bound(other, n_other, k, 1);
+                ap += ((double)c / (double)N) * ((double)le_own / (double)((u64)le_own + le_other));
+            }
+        }
+    }
+    gt = oe_block_sum<u64>(gt, shu, tid);
+    eq = oe_block_sum<u64>(eq, shu, tid);
+    ap = oe_block_sum<double>(ap, shd, tid);
+    if (tid == 0) { m.part_gt[side][blockIdx.x] = gt; m.part_eq[side][blockIdx.x] = eq; m.part_ap[side][blockIdx.x] = ap; }
+}
+
+// one workgroup: the partials in a fixed order, the operating point at the TPR level, the result block
+__global__ __launch_bounds__(256) void oe_metrics_final_kernel(OeMetrics m) {
+    __shared__ u64 shu[OE_THREADS];
+    __shared__ double shd[OE_THREADS];
+    const int tid = threadIdx.x;
+    const unsigned P = oe_min(m.state[0], m.capacity[0]), N = oe_min(m.state[2], m.capacity[1]);
+    const bool empty = P == 0 || N == 0;
+    const unsigned nb0 = empty ? 0u : (P + OE_MET_TILE - 1) / OE_MET_TILE, nb1 = empty ? 0u : (N + OE_MET_TILE - 1) / OE_MET_TILE;
+    u64 gt = 0, eq = 0;
+    double ap_in = 0.0, ap_out = 0.0;
+    for (unsigned k = tid; k < nb0; k += OE_THREADS) { gt += m.part_gt[0][k]; eq += m.part_eq[0][k]; ap_in += m.part_ap[0][k]; }
+    for (unsigned k = tid; k < nb1; k += OE_THREADS) ap_out += m.part_ap[1][k];
+    gt = oe_block_sum<u64>(gt, shu, tid);
+    eq = oe_block_sum<u64>(eq, shu, tid);
+    ap_in = oe_block_sum<double>(ap_in, shd, tid);
+    ap_out = oe_block_sum<double>(ap_out, shd, tid);
+    if (tid != 0) return;
+    u64 flags = (u64)(m.state[1] & 3u) | ((u64)(m.state[3] & 3u) << 2);
+    if (P == 0) flags |= OE_RES_EMPTY_IN;
+    if (N == 0) flags |= OE_RES_EMPTY_OOD;
+    u64 tp = 0, fp = 0, rank = 0;
+    unsigned thr = 0;
+    if (!empty) {
+        // the smallest k with (double)k / (double)P >= level: level * P rounds once, so the candidate is off by one at the most
+        const double dp = (double)P;
+        long long k = (long long)ceil(m.level * dp);
+        if (k < 1) k = 1;
+        if (k > (long long)P) k = P;
+        for (int s = 0; s < 2; ++s) if (k > 1 && (double)(k - 1) / dp >= m.level) --k;
+        for (int s = 0; s < 2; ++s) if (k < (long long)P && (double)k / dp < m.level) ++k;
+        rank = (u64)k;
+        thr = m.sorted[0][P - (unsigned)k];                             // the k-th largest positive
+        const unsigned key = oe_key(thr);
+        tp = P - oe_bound(m.sorted[0], P, key, 0);
+        fp = N - oe_bound(m.sorted[1], N, key, 0);
+    }
+    u64* res = m.result;
+    res[0] = P; res[1] = N; res[2] = gt; res[3] = eq; res[4] = tp; res[5] = fp; res[6] = flags; res[7] = rank;
+    reinterpret_cast<double*>(res)[8] = ap_in;
+    reinterpret_cast<double*>(res)[9] = ap_out;
+    res[10] = (u64)thr;                                                 // float32 bits of the threshold in the low word
+    res[11] = 0;
+}
+
+}  // namespace
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------------
+extern "C" int effdet_ood_eval_sort_tile(void) { return OE_SORT_TILE; }
+
+extern "C" long long effdet_ood_eval_workspace_bytes(long long capacity_pos, long long capacity_neg) {
+    OeLayout L;
+    return oe_layout(capacity_pos, capacity_neg, &L) ? L.total : (long long)EFFDET_EINVAL;
+}
+
+extern "C" long long effdet_ood_eval_sorted_offset(long long capacity_pos, long long capacity_neg, int side) {
+    OeLayout L;
+    if ((side != 0 && side != 1) || !oe_layout(capacity_pos, capacity_neg, &L)) return EFFDET_EINVAL;
+    return L.keys_b[side];
+}
+
+extern "C" int effdet_ood_eval_append(void* stream, const float* scores, long long pitch, long long stride, int B, int K,
+                                      const void* count, int count_is_int64, const float* det_score, long long det_pitch,
+                                      long long det_stride, float min_score, int negate, float* buffer, long long capacity,
+                                      unsigned int* side_state, void* workspace, long long workspace_bytes) {
+    EFFDET_ENTER();
+    if (!scores || !buffer || !side_state || !workspace || B <= 0 || K <= 0 || pitch < 0 || stride < 0 || det_pitch < 0 || det_stride < 0)
+        return EFFDET_EINVAL;
+    if (capacity < 1 || capacity > OE_MAX_SCORES || (long long)B * K > OE_MAX_SCORES || workspace_bytes < OE_APPEND_MAX_BLOCKS * 4)
+        return EFFDET_EINVAL;
+    OeAppend a;
+    a.scores = scores; a.pitch = pitch; a.stride = stride;
+    a.count = count; a.count_i64 = count_is_int64 ? 1 : 0;
+    a.det = det_score; a.det_pitch = det_pitch; a.det_stride = det_stride; a.min_score = min_score;
+    a.negate = negate ? 1 : 0; a.K = K;
+    a.total = (unsigned)((long long)B * K);
+    a.buffer = buffer; a.capacity = (unsigned)capacity;
+    a.state = side_state;
+    a.counts = reinterpret_cast<unsigned*>(workspace);                  // OeLayout::append_counts is the head of the workspace
+    a.nblocks = (a.total + OE_APPEND_TILE - 1) / OE_APPEND_TILE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(oe_append_count_kernel, dim3(a.nblocks), dim3(OE_THREADS), 0, st, a);
+    hipLaunchKernelGGL(oe_append_base_kernel, dim3(1), dim3(OE_THREADS), 0, st, a);
+    hipLaunchKernelGGL(oe_append_write_kernel, dim3(a.nblocks), dim3(OE_THREADS), 0, st, a);
+    return effdet_check_launch();
+}
+
+extern "C" int effdet_ood_eval_sort(void* stream, const float* pos, long long capacity_pos, const float* neg, long long capacity_neg,
+                                    const unsigned int* state, void* workspace, long long workspace_bytes) {
+    EFFDET_ENTER();
+    OeLayout L;
+    if (!pos || !neg || !state || !workspace || !oe_layout(capacity_pos, capacity_neg, &L) || workspace_bytes < L.total) return EFFDET_EINVAL;
+    char* ws = reinterpret_cast<char*>(workspace);
+    const float* in[2] = {pos, neg};
+    const long long caps[2] = {capacity_pos, capacity_neg};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const unsigned grid_x = L.tiles[0] > L.tiles[1] ? L.tiles[0] : L.tiles[1];
+    for (int pass = 0; pass < 4; ++pass) {
+        OeSortTable t;
+        t.shift = 8 * pass; t.first = pass == 0; t.last = pass == 3;
+        for (int s = 0; s < 2; ++s) {
+            unsigned* a = reinterpret_cast<unsigned*>(ws + L.keys_a[s]);
+            unsigned* b = reinterpret_cast<unsigned*>(ws + L.keys_b[s]);
+            t.s[s].src = pass == 0 ? reinterpret_cast<const unsigned*>(in[s]) : (pass & 1) ? a : b;      // in -> a -> b -> a -> b
+            t.s[s].dst = (pass & 1) ? b : a;
+            t.s[s].cursor = state + 2 * s;
+            t.s[s].hist = reinterpret_cast<unsigned*>(ws + L.hist[s]);
+            t.s[s].totals = reinterpret_cast<unsigned*>(ws + L.totals[s]);
+            t.s[s].capacity = (unsigned)caps[s];
+            t.s[s].tiles = L.tiles[s];
+        }
+        hipLaunchKernelGGL(oe_sort_hist_kernel, dim3(grid_x, 2), dim3(OE_THREADS), 0, st, t);
+        hipLaunchKernelGGL(oe_sort_scan_kernel, dim3(256, 2), dim3(OE_THREADS), 0, st, t);
+        hipLaunchKernelGGL(oe_sort_scatter_kernel, dim3(grid_x, 2), dim3(OE_THREADS), 0, st, t);
+    }
+    return effdet_check_launch();
+}
+
+extern "C" int effdet_ood_eval_metrics(void* stream, long long capacity_pos, long long capacity_neg, const unsigned int* state,
+                                       void* workspace, long long workspace_bytes, double level, void* result) {
+    EFFDET_ENTER();
+    OeLayout L;
+    if (!state || !workspace || !result || !oe_layout(capacity_pos, capacity_neg, &L) || workspace_bytes < L.total) return EFFDET_EINVAL;
+    if (!(level > 0.0 && level <= 1.0)) return EFFDET_EINVAL;
+    char* ws = reinterpret_cast<char*>(workspace);
+    OeMetrics m;
+    for (int s = 0; s < 2; ++s) {
+        m.sorted[s] = reinterpret_cast<const unsigned*>(ws + L.keys_b[s]);
+        m.part_gt[s] = reinterpret_cast<u64*>(ws + L.part_gt[s]);
+        m.part_eq[s] = reinterpret_cast<u64*>(ws + L.part_eq[s]);
+        m.part_ap[s] = reinterpret_cast<double*>(ws + L.part_ap[s]);
+    }
+    m.state = state;
+    m.capacity[0] = (unsigned)capacity_pos; m.capacity[1] = (unsigned)capacity_neg;
+    m.level = level;
+    m.result = reinterpret_cast<u64*>(result);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const unsigned grid_x = L.mblocks[0] > L.mblocks[1] ? L.mblocks[0] : L.mblocks[1];
+    hipLaunchKernelGGL(oe_metrics_part_kernel, dim3(grid_x, 2), dim3(OE_THREADS), 0, st, m);
+    hipLaunchKernelGGL(oe_metrics_final_kernel, dim3(1), dim3(OE_THREADS), 0, st, m);
+    return effdet_check_launch();
+}

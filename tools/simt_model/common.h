@@ -41,6 +41,10 @@ static inline unsigned long long __ballot(bool p) {
     simctx.wave->arrive_and_wait();
     return r;
 }
+// integer atomics (csrc/ood_eval.hip: LDS digit counts, flag bits) and a barrier for the lanes of one wave
+template <class T> static inline T atomicAdd(T* p, T v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+template <class T> static inline T atomicOr(T* p, T v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
+static inline void sim_wave_sync() { simctx.wave->arrive_and_wait(); }
 DEV float wave_reduce_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
 DEV float wave_reduce_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64)); return v; }
 static inline float __int_as_float(int v) { float f; std::memcpy(&f, &v, 4); return f; }
