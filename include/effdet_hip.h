@@ -434,7 +434,7 @@ int effdet_train_se_bwd(void* stream, const float* pool_sum, int hw, const float
  * fold: scale = gamma / sqrt(var + eps), shift = beta - mean * scale, rstd; Wf [N][K] = W * scale[n], WfT [K][N] = Wf^T,
  * WT [K][N] = W^T (each matrix optional).  grads: from dWext = effdet_train_gemm_tn's output ([N][K] then N sums; or the
  * depthwise [(K+1)][N] layout when transposed != 0): dW [N][K] = scale * dWraw, d gamma = rstd * (sum_k W * dWraw - mean * dsum),
- * d beta = dsum. */
+ * d beta = dsum.  Each is one record of the stage tables below handed to the same device code by value (nothing is uploaded). */
 int effdet_train_fold_bn(void* stream, const float* W, int N, int K, const float* gamma, const float* beta,
                          const float* mean, const float* var, float eps,
                          float* Wf, float* WfT, float* WT, float* scale, float* shift, float* rstd);
@@ -463,12 +463,13 @@ int effdet_train_bn_var_finalize(void* stream, const float* a, const float* mean
 int effdet_train_bn_bwd_sums(void* stream, const float* dy, const float* c, const float* mean, const float* rstd,
                              long long R, int C, float* out, float* workspace, long long workspace_floats);
 
-/* Table-driven forms of effdet_train_fold_bn / plain transposes and of effdet_train_convbn_grads: one launch for all convs of
- * a stage.  `table` = n records in DEVICE memory:
+/* Stage tables: the records of effdet_train_fold_bn / plain transposes / effdet_train_fpn_weights and of
+ * effdet_train_convbn_grads for all convs of a stage in one launch; a record computes bit for bit what the single call does
+ * (one device body, csrc/train_param.h).  `table` = n records in DEVICE memory:
  *   prep  { int kind, rows, cols; float eps; const float *src, *gamma, *beta, *mean, *var; float *dst0, *dst1, *dst2, *scale,
  *           *shift, *rstd; }   kind 0: dst0 [cols][rows] = src [rows][cols] transposed; kind 1: fold_bn with W = src [N = rows][K = cols],
  *           dst0 = Wf, dst1 = WfT, dst2 = WT (each optional); kind 2: effdet_train_fpn_weights with src = edge_weights [rows],
- *           method = (int) eps ('fastattn' 0 | 'attn' 1), dst0 = {w0, w1, w2, den}
+ *           cols = 1, method = (int) eps, dst0 = {w0, w1, w2, den}
  *   grads { const float *dWext, *W, *scale, *rstd, *mean; float *dW, *dgamma, *dbeta; int N, K, transposed, pad; } */
 int effdet_train_prep_table(void* stream, const void* table, int n, long long max_elems);
 int effdet_train_grads_table(void* stream, const void* table, int n, int max_n);
@@ -552,7 +553,8 @@ int effdet_train_dwconv_plan_describe(int which, int H, int W, int C, int k, int
  *   levels_bn_finalize nn.BatchNorm2d bookkeeping of the L layers (pointer tables of their parameters / buffers; train[l] != 0:
  *                      batch statistics mean = sum * inv_m, var = sq * inv_m, running stats updated; else running statistics)
  *                      -> mean, scale = gamma * rstd, shift = beta - mean * scale, rstd, all [L][C]
- *   levels_bn_bwd_prep sums [L][2][C] of mode 4 -> d gamma, d beta, v1, v3 ([L][C]; as effdet_train_bn_bwd_prep)
+ *   levels_bn_bwd_prep sums [L][2][C] of mode 4 -> d gamma, d beta, v1, v3 ([L][C]; per level and channel the arithmetic of
+ *                      effdet_train_bn_bwd_prep, as levels_bn_finalize shares effdet_train_bn_finalize's: csrc/train_param.h)
  *   levels_ew          op 3: out = a * v0[l][c] + v1[l][c] (out2 = silu(out) when given); op 6: BatchNorm backward
  *                      v0 (a' - v1 - (b - v2) v3) for levels with train[l] != 0, a' v0 otherwise; a' as in mode 4 */
 int effdet_train_gemm_nt_levels(void* stream, const float* A, int a_packed, const float* W, const float* bias, float* C,

@@ -47,6 +47,7 @@ DEV float fast_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + fast_exp(
 // INFERENCE parity path keeps silu_f.
 DEV float sigmoid_train(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
 DEV float silu_train(float x) { return x * sigmoid_train(x); }
+DEV float silu_grad(float z) { const float s = sigmoid_train(z); return s * (1.0f + z * (1.0f - s)); }      // silu'(z)
 
 struct bf16p_t;                                     // the two-term bf16 dtype (below): hardware transcendentals like bf16
 template <typename T> struct FastMath { static constexpr bool value = sizeof(T) == 2; };

@@ -2,7 +2,7 @@
 // resolution - identity, nearest x2 upsample, or 3x3 / s2 TF-SAME max-pool - then fused with normalised edge weights, then SiLU).
 // float32, NHWC.  The resampled inputs are never materialised: each kernel reads the SOURCE tensors at their own resolution.
 //   effdet_train_fpn_weights   edge_weights parameter -> {w0, w1, w2, den} on the device ('fastattn': relu, den = sum + 1e-4;
-//                              'attn': softmax, den = 1; 'sum': ones, den = 1)
+//                              'attn': softmax, den = 1; 'sum': ones, den = 1): a prep op of train_net.hip (train_param.h)
 //   effdet_train_fpn_combine   fused = sum_i (R_i(x_i) * w_i) / den,  act = silu(fused)                       (forward)
 //   effdet_train_fpn_dots      S[i][c] = sum_pixels dfused * R_i(x_i),  dfused = dact * silu'(fused)            (backward 1)
 //   effdet_train_fpn_wgrad     S -> d edge_weights (closed form of the normalisation)                           (backward 2)
@@ -18,8 +18,6 @@ struct FpnArgs {
     const float* dact; const float* fused; float* out; float* out2; float* partial;
     int B, H, W, C; long long rows_per_slice; int S;
 };
-
-DEV float fpn_silu_grad(float z) { const float s = sigmoid_train(z); return s * (1.0f + z * (1.0f - s)); }
 
 // value of resampled input `in` at pixel (b, y, x), 4 channels from c
 DEV f32x4 fpn_sample(const FpnIn& in, long long b, int y, int x, int c, int C) {
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(256) void fpn_dots_kernel(FpnArgs p) {
             f32x4 d = *reinterpret_cast<const f32x4*>(p.dact + r * p.C + c);
             const f32x4 z = *reinterpret_cast<const f32x4*>(p.fused + r * p.C + c);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) d[j] *= fpn_silu_grad(z[j]);
+            for (int j = 0; j < 4; ++j) d[j] *= silu_grad(z[j]);
 #pragma unroll
             for (int i = 0; i < 3; ++i)
                 if (i < p.n) acc[i] += d * fpn_sample(p.in[i], b, y, x, c, p.C);
@@ -137,27 +135,6 @@ __global__ __launch_bounds__(64) void fpn_wgrad_kernel(FpnWgArgs p) {
     }
 }
 
-struct FpnWArgs { const float* ewp; float* wdev; int n, method; };
-__global__ __launch_bounds__(64) void fpn_weights_kernel(FpnWArgs p) {
-    if (threadIdx.x != 0) return;
-    float w[3] = {0.f, 0.f, 0.f};
-    float den = 1.0f;
-    if (p.method == 0) {
-        float s = 0.f;
-        for (int i = 0; i < p.n; ++i) { w[i] = fmaxf(p.ewp[i], 0.f); s += w[i]; }
-        den = s + 0.0001f;
-    } else if (p.method == 1) {
-        float m = p.ewp[0];
-        for (int i = 1; i < p.n; ++i) m = fmaxf(m, p.ewp[i]);
-        float s = 0.f;
-        for (int i = 0; i < p.n; ++i) { w[i] = expf(p.ewp[i] - m); s += w[i]; }
-        for (int i = 0; i < p.n; ++i) w[i] = w[i] / s;
-    } else {
-        for (int i = 0; i < p.n; ++i) w[i] = 1.0f;
-    }
-    p.wdev[0] = w[0]; p.wdev[1] = w[1]; p.wdev[2] = w[2]; p.wdev[3] = den;
-}
-
 // d x = coef * R^T(dfused) (+ acc), one thread per 4 channels of a SOURCE pixel
 struct FpnBwdArgs {
     FpnIn in; int idx; const float* wdev; const float* dact; const float* fused; const float* acc; float* out; int B, H, W, C;
@@ -167,7 +144,7 @@ DEV f32x4 fpn_dfused(const FpnBwdArgs& p, long long b, int y, int x, int c) {
     const f32x4 d = *reinterpret_cast<const f32x4*>(p.dact + o), z = *reinterpret_cast<const f32x4*>(p.fused + o);
     f32x4 r;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = d[j] * fpn_silu_grad(z[j]);
+    for (int j = 0; j < 4; ++j) r[j] = d[j] * silu_grad(z[j]);
     return r;
 }
 __global__ __launch_bounds__(256) void fpn_input_bwd_kernel(FpnBwdArgs p) {
@@ -242,14 +219,6 @@ inline int fpn_slices(long long R, int C, long long* rps) {
 }
 
 }  // namespace
-
-extern "C" int effdet_train_fpn_weights(void* stream, const float* edge_weights, int n, int method, float* wdev) {
-    EFFDET_ENTER();
-    if (!wdev || n < 2 || n > 3 || method < 0 || method > 2 || (method < 2 && !edge_weights)) return EFFDET_EINVAL;
-    FpnWArgs p{edge_weights, wdev, n, method};
-    hipLaunchKernelGGL(fpn_weights_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p);
-    return effdet_check_launch();
-}
 
 // srcs / hs / ws: the n source tensors [B][hs[i]][ws[i]][C] (same size as the node, half of it, or twice it)
 extern "C" int effdet_train_fpn_combine(void* stream, int n, const void* const* srcs, const int* hs, const int* ws, int method,

@@ -14,6 +14,7 @@
 // dropped: finishing the reduction inside the first launch (the workgroup that arrives last at an agent-scope counter adds the
 // partial rows) - with the 150 - 770 partial rows these shapes need, that one workgroup's serial pass cost 120 - 560 us.
 #include "common.h"
+#include "train_param.h"
 
 namespace {
 
@@ -37,8 +38,6 @@ inline int fill_levels(Levels& lv, int B, int L, const int* Hs, const int* Ws) {
     }
     return 0;
 }
-
-DEV float lv_silu_grad(float z) { const float s = sigmoid_train(z); return s * (1.0f + z * (1.0f - s)); }
 
 DEV int level_of(const Levels& lv, long long row) {
     int l = 0;
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(256) void lv_col_reduce_kernel(LvColArgs p) {
                 if (p.pre) {
                     const f32x4 z = *reinterpret_cast<const f32x4*>(p.pre + r * p.C + c);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) ad[j] = a[j] * lv_silu_grad(z[j]);
+                    for (int j = 0; j < 4; ++j) ad[j] = a[j] * silu_grad(z[j]);
                 }
                 acc += ad;
                 acc2 += ad * (*reinterpret_cast<const f32x4*>(p.b + r * p.C + c) - vc);
@@ -233,15 +232,13 @@ __global__ __launch_bounds__(256) void lv_bn_finalize_kernel(LvBnFinArgs p) {
     if (p.train[l]) {
         m = p.sum[o] * p.invM[l];
         v = p.sq[o] * p.invM[l];
-        p.rmean[l][c] = p.rmean[l][c] * (1.0f - p.momentum[l]) + p.momentum[l] * m;
-        p.rvar[l][c] = p.rvar[l][c] * (1.0f - p.momentum[l]) + p.momentum[l] * (v * p.unbias[l]);
+        bn_track(p.rmean[l] + c, p.rvar[l] + c, m, v, p.momentum[l], p.unbias[l]);
     } else { m = p.rmean[l][c]; v = p.rvar[l][c]; }
-    const float rs = 1.0f / sqrtf(v + p.eps[l]);
-    const float sc = p.gamma[l][c] * rs;
+    const BnAffine a = bn_affine(p.gamma[l][c], p.beta[l][c], m, v, p.eps[l]);
     p.mean[o] = m;
-    p.rstd[o] = rs;
-    p.scale[o] = sc;
-    p.shift[o] = p.beta[l][c] - m * sc;
+    p.rstd[o] = a.rstd;
+    p.scale[o] = a.scale;
+    p.shift[o] = a.shift;
 }
 
 struct LvBnBwdArgs { const float* sums; const float* rstd; float invM[MAXL]; int L, C; float* dgamma; float* dbeta; float* v1; float* v3; };
@@ -252,11 +249,7 @@ __global__ __launch_bounds__(256) void lv_bn_bwd_prep_kernel(LvBnBwdArgs p) {
     if (c >= p.C) return;
     const long long o = (long long)l * p.C + c;
     const float s1 = p.sums[((long long)l * 2) * p.C + c], s2 = p.sums[((long long)l * 2 + 1) * p.C + c];
-    const float rs = p.rstd[o];
-    p.dgamma[o] = s2 * rs;
-    p.dbeta[o] = s1;
-    p.v1[o] = s1 * p.invM[l];
-    p.v3[o] = rs * rs * s2 * p.invM[l];
+    bn_bwd_vectors(s1, s2, p.rstd[o], p.invM[l], p.dgamma + o, p.dbeta + o, p.v1 + o, p.v3 + o);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(256) void lv_ew_kernel(LvEwArgs p) {
         if (p.pre) {
             const f32x4 z = *reinterpret_cast<const f32x4*>(p.pre + i);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] *= lv_silu_grad(z[j]);
+            for (int j = 0; j < 4; ++j) a[j] *= silu_grad(z[j]);
         }
         if (p.train[l]) {
             const f32x4 b = *reinterpret_cast<const f32x4*>(p.b + i);

@@ -15,6 +15,7 @@
 // MFMA 16x16x4 f32 carries the GEMMs; operands are streamed from HBM/L2 straight into registers (the weight side is
 // small and L2 resident); D holds 4 consecutive output channels of one pixel per lane -> 16-byte stores.
 #include "common.h"
+#include "train_param.h"
 
 namespace {
 
@@ -699,19 +700,13 @@ __global__ __launch_bounds__(256) void reduce_bn_kernel(ReduceBnArgs p) {
     if (p.kind == 0) {
         if (c == 0 && p.nbt) *p.nbt += 1;
         const float m = p.mean[c], v = t0 * p.alpha;
-        p.running_mean[c] = p.running_mean[c] * (1.0f - p.momentum) + p.momentum * m;
-        p.running_var[c] = p.running_var[c] * (1.0f - p.momentum) + p.momentum * (v * p.unbias);
-        const float rs = 1.0f / sqrtf(v + p.eps);
-        const float sc = p.gamma[c] * rs;
-        p.rstd_out[c] = rs;
-        p.scale[c] = sc;
-        p.shift[c] = p.beta[c] - m * sc;
+        bn_track(p.running_mean + c, p.running_var + c, m, v, p.momentum, p.unbias);
+        const BnAffine a = bn_affine(p.gamma[c], p.beta[c], m, v, p.eps);
+        p.rstd_out[c] = a.rstd;
+        p.scale[c] = a.scale;
+        p.shift[c] = a.shift;
     } else {
-        const float rs = p.rstd_in[c];
-        p.dgamma[c] = t1 * rs;
-        p.dbeta[c] = t0;
-        p.v1[c] = t0 * p.invM;
-        p.v3[c] = rs * rs * t1 * p.invM;
+        bn_bwd_vectors(t0, t1, p.rstd_in[c], p.invM, p.dgamma + c, p.dbeta + c, p.v1 + c, p.v3 + c);
     }
 }
 
@@ -763,8 +758,6 @@ namespace {
 inline int launch_reduce_mid(hipStream_t st, const float* in, int G, int S, long long L, float* out, int accumulate, float alpha = 1.0f) {
     return effdet_launch_reduce_mid(st, in, G, S, L, out, accumulate, alpha);
 }
-
-DEV float silu_grad(float z) { const float s = sigmoid_train(z); return s * (1.0f + z * (1.0f - s)); }
 
 // ------------------------------------------------------------------------------------------------------------
 // depthwise backward
@@ -1341,174 +1334,61 @@ __global__ __launch_bounds__(1024) void se_bwd_kernel(SeBwdArgs p) {
 
 
 // ------------------------------------------------------------------------------------------------------------
-// parameter-sized helpers of conv + BatchNorm(running statistics): one launch instead of a dozen tiny tensor ops
+// parameter-sized helpers (formulas: train_param.h): one launch instead of a dozen tiny tensor ops
 // ------------------------------------------------------------------------------------------------------------
-struct FoldArgs {
-    const float* W; int N, K; const float* gamma; const float* beta; const float* mean; const float* var; float eps;
-    float* Wf; float* WfT; float* WT; float* scale; float* shift; float* rstd;
-};
-// scale = gamma * rsqrt(var + eps), shift = beta - mean * scale; Wf [N][K] = W * scale[n], WfT [K][N] its transpose,
-// WT [K][N] = W transposed (each optional).  One workgroup per output channel.
-__global__ __launch_bounds__(256) void fold_bn_kernel(FoldArgs p) {
-    const int n = blockIdx.x;
-    const float rs = 1.0f / sqrtf(p.var[n] + p.eps);
-    const float sc = p.gamma[n] * rs;
-    if (threadIdx.x == 0) {
-        p.scale[n] = sc;
-        p.shift[n] = p.beta[n] - p.mean[n] * sc;
-        p.rstd[n] = rs;
-    }
-    for (int k = threadIdx.x; k < p.K; k += 256) {
-        const float w = p.W[(long long)n * p.K + k];
-        if (p.Wf) p.Wf[(long long)n * p.K + k] = w * sc;
-        if (p.WfT) p.WfT[(long long)k * p.N + n] = w * sc;
-        if (p.WT) p.WT[(long long)k * p.N + n] = w;
-    }
-}
-
-struct FinArgs {
-    const float* dWext; int N, K, transposed; const float* W; const float* scale; const float* rstd; const float* mean;
-    float* dW; float* dgamma; float* dbeta;
-};
-// z = scale * conv(x; W) + shift, dWraw = dz^T x, dsum = sum dz  ->  dW = scale * dWraw,
-// d gamma = rstd * (sum_k W * dWraw - mean * dsum), d beta = dsum.   dWext: [N][K] then [N] sums (or [(K+1)][N] when transposed).
-__global__ __launch_bounds__(256) void convbn_grads_kernel(FinArgs p) {
-    __shared__ float sm[4];
-    const int n = blockIdx.x;
-    const float sc = p.scale[n];
-    float acc = 0.f;
-    for (int k = threadIdx.x; k < p.K; k += 256) {
-        const float v = p.transposed ? p.dWext[(long long)k * p.N + n] : p.dWext[(long long)n * p.K + k];
-        p.dW[(long long)n * p.K + k] = sc * v;
-        acc += p.W[(long long)n * p.K + k] * v;
-    }
-    acc = wave_reduce_sum(acc);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float tot = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-        const float dsum = p.dWext[(long long)p.K * p.N + n];      // both layouts keep the N sums behind the N*K gradients
-        p.dgamma[n] = p.rstd[n] * (tot - p.mean[n] * dsum);
-        p.dbeta[n] = dsum;
-    }
-}
-
 struct BnFinArgs {
     const float* mean; const float* var; const float* gamma; const float* beta;
     float* running_mean; float* running_var; long long* nbt; int C, train; float momentum, unbias, eps;
     float* scale; float* shift; float* rstd;
 };
-// nn.BatchNorm2d bookkeeping in one launch: running statistics (training: r = (1-m) r + m * batch, unbiased variance),
-// rstd = 1/sqrt(var + eps), scale = gamma * rstd, shift = beta - mean * scale
+// nn.BatchNorm2d bookkeeping in one launch: running statistics when training, then rstd, scale, shift (train_param.h)
 __global__ __launch_bounds__(256) void bn_finalize_kernel(BnFinArgs p) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c == 0 && p.train && p.nbt) *p.nbt += 1;
     if (c >= p.C) return;
     const float m = p.mean[c], v = p.var[c];
-    if (p.train) {
-        p.running_mean[c] = p.running_mean[c] * (1.0f - p.momentum) + p.momentum * m;
-        p.running_var[c] = p.running_var[c] * (1.0f - p.momentum) + p.momentum * (v * p.unbias);
-    }
-    const float rs = 1.0f / sqrtf(v + p.eps);
-    const float sc = p.gamma[c] * rs;
-    p.rstd[c] = rs;
-    p.scale[c] = sc;
-    p.shift[c] = p.beta[c] - m * sc;
+    if (p.train) bn_track(p.running_mean + c, p.running_var + c, m, v, p.momentum, p.unbias);
+    const BnAffine a = bn_affine(p.gamma[c], p.beta[c], m, v, p.eps);
+    p.rstd[c] = a.rstd;
+    p.scale[c] = a.scale;
+    p.shift[c] = a.shift;
 }
 
 struct BnBwdArgs { const float* s1; const float* s2c; const float* rstd; int C; float invM; float* dgamma; float* dbeta; float* v1; float* v3; };
-// d gamma = rstd * sum(dy (c - mean)), d beta = sum(dy); v1 = sum(dy)/M, v3 = rstd^2 * sum(dy (c - mean))/M for op 6 of the
-// element-wise family
 __global__ __launch_bounds__(256) void bn_bwd_prep_kernel(BnBwdArgs p) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= p.C) return;
-    const float rs = p.rstd[c], s1 = p.s1[c], s2 = p.s2c[c];
-    p.dgamma[c] = s2 * rs;
-    p.dbeta[c] = s1;
-    p.v1[c] = s1 * p.invM;
-    p.v3[c] = rs * rs * s2 * p.invM;
+    bn_bwd_vectors(p.s1[c], p.s2c[c], p.rstd[c], p.invM, p.dgamma + c, p.dbeta + c, p.v1 + c, p.v3 + c);
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Table-driven forms of the parameter-sized helpers: ONE launch for every conv of a stage instead of one per conv.
+// The op records of train_param.h as launches: a stage table in device memory (grid row y = record y: ONE launch for every conv
+// of a stage), or one record by value (the recording step and the stem conv: nothing is uploaded, so they stay graph-capturable).
+// Both forms run the same device body.
 // ------------------------------------------------------------------------------------------------------------
-struct PrepOp {                                 // mirrored by train_engine._PrepOp (ctypes)
-    int kind, rows, cols; float eps;            // kind 0: transpose src [rows][cols] -> dst0 [cols][rows]; 1: fold_bn (rows = N, cols = K); 2: BiFPN edge weights
-    const float* src; const float* gamma; const float* beta; const float* mean; const float* var;
-    float* dst0; float* dst1; float* dst2; float* scale; float* shift; float* rstd;      // fold: Wf, WfT, WT (each optional)
-};
-__global__ __launch_bounds__(256) void prep_table_kernel(const PrepOp* ops, int n) {
-    const PrepOp p = ops[blockIdx.y];
-    const long long total = (long long)p.rows * p.cols;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int r = (int)(e / p.cols), c = (int)(e - (long long)r * p.cols);
-        if (p.kind == 2) {                                   // BiFPN edge weights (rows = n inputs, cols = 1, eps = method): dst0 = {w0, w1, w2, den}
-            if (e != 0) break;
-            const int method = (int)p.eps;
-            float w[3] = {0.f, 0.f, 0.f};
-            float den = 1.0f;
-            if (method == 0) {
-                float sum = 0.f;
-                for (int i = 0; i < p.rows; ++i) { w[i] = fmaxf(p.src[i], 0.f); sum += w[i]; }
-                den = sum + 0.0001f;
-            } else if (method == 1) {
-                float m = p.src[0];
-                for (int i = 1; i < p.rows; ++i) m = fmaxf(m, p.src[i]);
-                float sum = 0.f;
-                for (int i = 0; i < p.rows; ++i) { w[i] = expf(p.src[i] - m); sum += w[i]; }
-                for (int i = 0; i < p.rows; ++i) w[i] = w[i] / sum;
-            }
-            p.dst0[0] = w[0]; p.dst0[1] = w[1]; p.dst0[2] = w[2]; p.dst0[3] = den;
-            break;
-        }
-        const float w = p.src[e];
-        if (p.kind == 0) { p.dst0[(long long)c * p.rows + r] = w; continue; }
-        const float rs = 1.0f / sqrtf(p.var[r] + p.eps);
-        const float sc = p.gamma[r] * rs;
-        if (c == 0) { p.scale[r] = sc; p.shift[r] = p.beta[r] - p.mean[r] * sc; p.rstd[r] = rs; }
-        if (p.dst0) p.dst0[e] = w * sc;
-        if (p.dst1) p.dst1[(long long)c * p.rows + r] = w * sc;
-        if (p.dst2) p.dst2[(long long)c * p.rows + r] = w;
-    }
-}
+__global__ __launch_bounds__(256) void prep_table_kernel(const PrepOp* ops) { const PrepOp op = ops[blockIdx.y]; prep_op_run(op); }
+__global__ __launch_bounds__(256) void prep_op_kernel(PrepOp op) { prep_op_run(op); }
+__global__ __launch_bounds__(256) void grads_table_kernel(const GradOp* ops) { const GradOp op = ops[blockIdx.y]; grad_op_run(op); }
+__global__ __launch_bounds__(256) void grad_op_kernel(GradOp op) { grad_op_run(op); }
 
-struct GradOp {                                 // mirrored by train_engine._GradOp: effdet_train_convbn_grads per table row
-    const float* dWext; const float* W; const float* scale; const float* rstd; const float* mean;
-    float* dW; float* dgamma; float* dbeta; int N, K, transposed, pad;
-};
-__global__ __launch_bounds__(256) void grads_table_kernel(const GradOp* ops, int n) {
-    __shared__ float sm[4];
-    const GradOp p = ops[blockIdx.y];
-    const int nn = blockIdx.x;
-    if (nn >= p.N) return;                       // uniform per workgroup
-    const float sc = p.scale[nn];
-    float acc = 0.f;
-    for (int k = threadIdx.x; k < p.K; k += 256) {
-        const float v = p.transposed ? p.dWext[(long long)k * p.N + nn] : p.dWext[(long long)nn * p.K + k];
-        p.dW[(long long)nn * p.K + k] = sc * v;
-        acc += p.W[(long long)nn * p.K + k] * v;
-    }
-    acc = wave_reduce_sum(acc);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float tot = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-        const float dsum = p.dWext[(long long)p.K * p.N + nn];
-        p.dgamma[nn] = p.rstd[nn] * (tot - p.mean[nn] * dsum);
-        p.dbeta[nn] = dsum;
-    }
+// grid x of a prep launch: the workgroups stride over max_elems elements
+inline unsigned prep_grid_x(long long max_elems) {
+    const long long gx = (max_elems + 255) / 256;
+    return (unsigned)(gx > 64 ? 64 : gx);
+}
+inline int launch_prep_op(void* stream, const PrepOp& op) {
+    hipLaunchKernelGGL(prep_op_kernel, dim3(prep_grid_x((long long)op.rows * op.cols)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), op);
+    return effdet_check_launch();
 }
 
 }  // namespace
 
-// table: n PrepOp records in device memory (layout above); max_elems = the largest rows * cols in the table
+// table: n PrepOp records in device memory (train_param.h); max_elems = the largest rows * cols in the table
 extern "C" int effdet_train_prep_table(void* stream, const void* table, int n, long long max_elems) {
     EFFDET_ENTER();
     if (!table || n <= 0 || n > 65535 || max_elems <= 0) return EFFDET_EINVAL;
-    long long gx = (max_elems + 255) / 256;
-    if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(prep_table_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       static_cast<const PrepOp*>(table), n);
+    hipLaunchKernelGGL(prep_table_kernel, dim3(prep_grid_x(max_elems), (unsigned)n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const PrepOp*>(table));
     return effdet_check_launch();
 }
 
@@ -1517,7 +1397,7 @@ extern "C" int effdet_train_grads_table(void* stream, const void* table, int n, 
     EFFDET_ENTER();
     if (!table || n <= 0 || n > 65535 || max_n <= 0) return EFFDET_EINVAL;
     hipLaunchKernelGGL(grads_table_kernel, dim3((unsigned)max_n, (unsigned)n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       static_cast<const GradOp*>(table), n);
+                       static_cast<const GradOp*>(table));
     return effdet_check_launch();
 }
 
@@ -2209,9 +2089,14 @@ extern "C" int effdet_train_fold_bn(void* stream, const float* W, int N, int K, 
                                     float* Wf, float* WfT, float* WT, float* scale, float* shift, float* rstd) {
     EFFDET_ENTER();
     if (!W || !gamma || !beta || !mean || !var || !scale || !shift || !rstd || N <= 0 || K <= 0) return EFFDET_EINVAL;
-    FoldArgs p{W, N, K, gamma, beta, mean, var, eps, Wf, WfT, WT, scale, shift, rstd};
-    hipLaunchKernelGGL(fold_bn_kernel, dim3((unsigned)N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-    return effdet_check_launch();
+    return launch_prep_op(stream, PrepOp{1, N, K, eps, W, gamma, beta, mean, var, Wf, WfT, WT, scale, shift, rstd});
+}
+
+extern "C" int effdet_train_fpn_weights(void* stream, const float* edge_weights, int n, int method, float* wdev) {
+    EFFDET_ENTER();
+    if (!wdev || n < 2 || n > 3 || method < 0 || method > 2 || (method < 2 && !edge_weights)) return EFFDET_EINVAL;
+    return launch_prep_op(stream, PrepOp{2, n, 1, (float)method, edge_weights, nullptr, nullptr, nullptr, nullptr, wdev,
+                                         nullptr, nullptr, nullptr, nullptr, nullptr});
 }
 
 extern "C" int effdet_train_convbn_grads(void* stream, const float* dWext, int N, int K, int transposed, const float* W,
@@ -2219,8 +2104,8 @@ extern "C" int effdet_train_convbn_grads(void* stream, const float* dWext, int N
                                          float* dW, float* dgamma, float* dbeta) {
     EFFDET_ENTER();
     if (!dWext || !W || !scale || !rstd || !mean || !dW || !dgamma || !dbeta || N <= 0 || K <= 0) return EFFDET_EINVAL;
-    FinArgs p{dWext, N, K, transposed, W, scale, rstd, mean, dW, dgamma, dbeta};
-    hipLaunchKernelGGL(convbn_grads_kernel, dim3((unsigned)N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+    GradOp op{dWext, W, scale, rstd, mean, dW, dgamma, dbeta, N, K, transposed, 0};
+    hipLaunchKernelGGL(grad_op_kernel, dim3((unsigned)N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), op);
     return effdet_check_launch();
 }
 

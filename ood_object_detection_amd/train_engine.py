@@ -52,56 +52,48 @@ class _StageTables(object):
 
     def __init__(self, ops):
         self.ops, self.lib = ops, ops.lib
-        self.prep, self.grad = {}, {}              # key -> (op record, tensors kept alive)
+        self.prep, self.grad = {}, {}              # key -> (op record, derived tensors, sources) / (op record, tensors kept alive)
         self.ptab = self.gtab = None
         self.frozen = False                        # True once the tables are on the device
 
-    def _check_src(self, entry, src, extra=()):
-        # `extra`: (recorded pointer, tensor) pairs of the other sources of the record (BN gamma / beta / running statistics)
-        if entry[0].src != src.data_ptr() or any(ptr != t.data_ptr() for ptr, t in extra):
-            raise RuntimeError('a parameter was re-allocated after the training engine recorded it; build a new TrainEngine')
-
-    def transpose(self, key, src2d):
-        """-> persistent [cols, rows] transpose of the contiguous 2-D parameter view src2d (None while recording: caller computes)"""
+    def _derived(self, key, srcs, make):
+        """-> the persistent tensors of prep record `key`.  Recorded: checked against the sources `srcs` (tensors, in the order of
+        the record's src, gamma, beta, mean, var) and handed out.  While recording: make() -> (record, tensors); it computes them once"""
         if key in self.prep:
-            self._check_src(self.prep[key], src2d)
-            return self.prep[key][1][0]
+            op, out = self.prep[key][:2]
+            if any(ptr != t.data_ptr() for ptr, t in zip((op.src, op.gamma, op.beta, op.mean, op.var), srcs)):
+                raise RuntimeError('a parameter was re-allocated after the training engine recorded it; build a new TrainEngine')
+            return out
         if self.frozen:
             raise RuntimeError('unrecorded derived weight %r' % (key,))
-        rows, cols = src2d.shape
-        dst = self.ops.new(cols, rows)
-        dst.copy_(src2d.t())
-        op = _PrepOp(0, rows, cols, 0.0, src2d.data_ptr(), None, None, None, None, dst.data_ptr(), None, None, None, None, None)
-        self.prep[key] = (op, (dst, src2d))
-        return dst
+        op, out = make()
+        self.prep[key] = (op, out, srcs)            # the sources are kept alive with the record
+        return out
+
+    def transpose(self, key, src2d):
+        """-> persistent [cols, rows] transpose of the contiguous 2-D parameter view src2d"""
+        def make():
+            rows, cols = src2d.shape
+            dst = self.ops.new(cols, rows)
+            dst.copy_(src2d.t())
+            return _PrepOp(0, rows, cols, 0.0, src2d.data_ptr(), None, None, None, None, dst.data_ptr(), None, None, None, None, None), dst
+        return self._derived(key, (src2d,), make)
 
     def edge_weights(self, key, ewp, n, method, compute):
         """-> persistent {w0, w1, w2, den} of a BiFPN node's edge_weights parameter ('fastattn' / 'attn')"""
-        if key in self.prep:
-            self._check_src(self.prep[key], ewp)
-            return self.prep[key][1][0]
-        if self.frozen:
-            raise RuntimeError('unrecorded derived weight %r' % (key,))
-        wdev = compute()
-        op = _PrepOp(2, n, 1, float(method), ewp.data_ptr(), None, None, None, None, wdev.data_ptr(), None, None, None, None, None)
-        self.prep[key] = (op, (wdev, ewp))
-        return wdev
+        def make():
+            wdev = compute()
+            return _PrepOp(2, n, 1, float(method), ewp.data_ptr(), None, None, None, None, wdev.data_ptr(), None, None, None, None, None), wdev
+        return self._derived(key, (ewp,), make)
 
-    def fold(self, key, W, bn, want_wf, want_wft, want_wt, compute):
-        if key in self.prep:
-            op = self.prep[key][0]
-            self._check_src(self.prep[key], W, ((op.gamma, bn.weight), (op.beta, bn.bias), (op.mean, bn.running_mean),
-                                                (op.var, bn.running_var)))
-            return self.prep[key][1][0]
-        if self.frozen:
-            raise RuntimeError('unrecorded derived weight %r' % (key,))
-        out = compute()                             # (Wf, WfT, WT, scale, shift, rstd) from effdet_train_fold_bn: these buffers persist
-        p = lambda t: None if t is None else t.data_ptr()
-        N, K = W.shape
-        op = _PrepOp(1, N, K, float(bn.eps), W.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                     bn.running_var.data_ptr(), p(out[0]), p(out[1]), p(out[2]), out[3].data_ptr(), out[4].data_ptr(), out[5].data_ptr())
-        self.prep[key] = (op, (out, W, bn))
-        return out
+    def fold(self, key, W, bn, compute):
+        """-> persistent (Wf, WfT, WT, scale, shift, rstd) of effdet_train_fold_bn (compute() makes them; absent matrices are None)"""
+        def make():
+            out = compute()
+            N, K = W.shape
+            return _PrepOp(1, N, K, float(bn.eps), W.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                           bn.running_var.data_ptr(), *[None if t is None else t.data_ptr() for t in out]), out
+        return self._derived(key, (W, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
 
     def grad_entry(self, key, rec, transposed):
         """-> (dWext buffer the backward GEMM writes, dW, dgb, deferred) for conv `key`; deferred: run_grads() will fill dW / dgb"""
@@ -511,8 +503,7 @@ class TrainEngine(object):
         # the raw addresses of the 'fh' set, and a stage that records a subset of 'fh' (no class head) must not freeze that set
         self._tables = {'bb': _StageTables(self.ops), 'fh': _StageTables(self.ops), 'nc': _StageTables(self.ops)}
         self._stage = None                          # the stage whose forward / backward is running (None: called from outside, e.g. meta_grad)
-        import os
-        self.use_tables = os.environ.get('EFFDET_TRAIN_TABLES', '1') != '0'     # 0: every derived weight / gradient conv by conv (debugging)
+        self.use_tables = True          # False (effdet/meta_grad.py): every derived weight / gradient conv by conv, nothing recorded
         self.direct_grad = False        # True: parameter gradients are added into existing `.grad`s by one multi-tensor launch
 
     def _const(self, C, v):
@@ -543,7 +534,7 @@ class TrainEngine(object):
 
         if self._stage is None or key is None:
             return compute()
-        return self._tables[self._stage].fold(key, W, bn, want_wf, want_wft, want_wt, compute)
+        return self._tables[self._stage].fold(key, W, bn, compute)
 
     def _transposed(self, key, src2d):
         """contiguous transpose of a 2-D parameter view: from the stage's table inside a stage, computed on the spot otherwise"""

@@ -272,6 +272,16 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.effdet_topk_workspace_bytes(4, 1000) > 4 * (16384 * 8 + 1000 * 8)
 
 
+def test_stage_table_records_mirror_the_c_structs():
+    """train_engine._PrepOp / _GradOp are uploaded as bytes and read as csrc/train_param.h's PrepOp / GradOp: the sizes the C side
+    pins with static_assert are the sizes of the ctypes mirrors"""
+    from ood_object_detection_amd.train_engine import _GradOp, _PrepOp
+    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'train_param.h')).read()
+    pinned = {name: int(n) for name, n in re.findall(r'static_assert\(sizeof\((\w+)\) == (\d+),', src)}
+    assert pinned == {'PrepOp': 104, 'GradOp': 80}
+    assert ctypes.sizeof(_PrepOp) == 104 and ctypes.sizeof(_GradOp) == 80
+
+
 @pytest.mark.parametrize('sizes', [(640, 128), (500, 128), (37, 48), (48, 37), (1280, 128), (128, 128)])
 def test_pil_coefficient_tables_match_oracle(sizes):
     """The product's vectorised Pillow coefficient tables equal the oracle's scalar restatement (pinned against PIL)."""
