@@ -662,6 +662,45 @@ long long effdet_eval_ap_workspace_bytes(int n);
 int effdet_eval_ap(void* stream, const float* scores, const int* classes, const int* tp, int n, int num_classes,
                    const int* gt_count, double* ap, void* workspace, long long workspace_bytes);
 
+/* ---- dataset-scale detection evaluation (csrc/eval_scale.hip): sorted AP at up to 16 IoU thresholds, `difficult` flags ------ */
+
+/* effdet_eval_match for `num_thresholds` (1..16) ascending IoU thresholds (a HOST array) and optional `difficult` flags
+ * gt_difficult [B,M] bytes (NULL: none).  A detection's candidate is the ground-truth box of its class with the largest IoU
+ * (first on ties, difficult boxes included); at threshold t with IoU >= thresholds[t]: candidate difficult -> the detection is
+ * ignored at t; candidate free at t -> true positive, the box is taken at t; otherwise false positive.  flags [B,max_det]:
+ * bit t = true positive at t, bit 16 + t = ignored at t, bit 31 = dropped (padding row, degenerate box, class outside
+ * 1..num_classes, NaN score; with 16 thresholds bit 31 is also `ignored at all of them`, which drops the row just the same).
+ * kept (NULL, or [2 B] for effdet_eval_append): slots of image b without bit 31, then its NaN
+ * scores.  gt_count [C] (boxes that are not difficult), gt_imgs [C] (images with the class, difficult or not) and
+ * correct_imgs [T][C] (CorLoc, difficult boxes count as ground truth) are accumulated (+=).  B * max_det <= 2^24. */
+int effdet_eval_match_multi(void* stream, const float* det, const int* det_count, const float* gt_boxes, const long long* gt_cls,
+                            const unsigned char* gt_difficult, int B, int max_det, int M, int num_classes,
+                            const float* thresholds, int num_thresholds, unsigned int* flags, int* kept,
+                            int* gt_count, int* gt_imgs, int* correct_imgs);
+/* Appends (score, 0-based class, flag word) of every slot without bit 31 to the `capacity`-sized buffers (<= 2^24) at the device
+ * cursor, in (image, slot) order; -0.0 is stored as +0.0.  state: 4 unsigned words on the device, zeroed by the caller to reset:
+ * {cursor, entries lost beyond the capacity, NaN scores, 0}.  Two launches; the host reads nothing back. */
+int effdet_eval_append(void* stream, const float* det, const unsigned int* flags, const int* kept, int B, int max_det,
+                       float* scores, int* classes, unsigned int* out_flags, long long capacity, unsigned int* state);
+/* entries one workgroup handles per radix pass */
+int effdet_eval_scale_sort_tile(void);
+/* pure host queries: workspace size; byte offset in the workspace of the sorted 64-bit keys (which = 0: class << 32 | ~k(score),
+ * k = the order-preserving map of the float32 bits) and of their flag words (which = 1) after effdet_eval_ap_sorted; size of the
+ * result block */
+long long effdet_eval_ap_sorted_workspace_bytes(long long capacity, int num_classes);
+long long effdet_eval_ap_sorted_offset(long long capacity, int num_classes, int which);
+long long effdet_eval_ap_sorted_result_bytes(int num_thresholds, int num_classes);
+/* VOC all-points AP per (threshold, class) over the first n entries (n < 0: min(state[0], capacity), read on the device) without
+ * n x n work: a stable radix sort by (class, score descending; equal scores in arrival order), then per class and threshold
+ * rank = running count of the entries not ignored, precision = cumulative TP / rank (float64), envelope = maximum over the later
+ * entries, AP = sum over the true positives of (recall step) * envelope in a fixed order.  Entries with bit 31, a class outside
+ * 0..num_classes-1 or a NaN score take no part.  result: 8-byte words {n, lost, NaN scores, T, C, 0, 0, 0}, AP [T][C] float64
+ * (NaN without ground truth, 0 with ground truth and no detection), then int64 gt_count [C], gt_imgs [C], correct_imgs [T][C].
+ * num_classes <= 65535.  Capturable; bit-identical from run to run. */
+int effdet_eval_ap_sorted(void* stream, const float* scores, const int* classes, const unsigned int* flags, long long capacity,
+                          long long n, const unsigned int* state, int num_thresholds, int num_classes, const int* gt_count,
+                          const int* gt_imgs, const int* correct_imgs, void* workspace, long long workspace_bytes, void* result);
+
 /* ---- OOD evaluation helpers -------------------------------------------- */
 
 /* The fork's novelty score (infer.py:425-427, 465-471, 607-616), reported beside energy / max-logit:

@@ -133,6 +133,15 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_eval_ap_workspace_bytes': (c_ll, [c_int]),
     'effdet_eval_ap': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_eval_match_multi': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_eval_append': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'effdet_eval_scale_sort_tile': (c_int, []),
+    'effdet_eval_ap_sorted_workspace_bytes': (c_ll, [c_ll, c_int]),
+    'effdet_eval_ap_sorted_offset': (c_ll, [c_ll, c_int, c_int]),
+    'effdet_eval_ap_sorted_result_bytes': (c_ll, [c_int, c_int]),
+    'effdet_eval_ap_sorted': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
     'effdet_train_fold_bn': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_train_convbn_grads': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1,1 +1,2 @@
 from .detection_evaluator import ObjectDetectionEvaluator, PascalDetectionEvaluator  # noqa: F401
+from .dataset_evaluator import DatasetDetectionEvaluator  # noqa: F401

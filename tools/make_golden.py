@@ -16,6 +16,8 @@ Fixtures written
                               NMS step comes from the oracle via the torchvision stub)
     loss.npz                  loss.loss_fn values and autograd gradients
     evaluation.npz            ObjectDetectionEvaluator mAP / CorLoc on seeded detections
+    evaluation_scale.npz      the same with `difficult` ground truth at IoU thresholds 0.5, 0.55, 0.75 (one reference
+                              evaluator per threshold): per-class AP / CorLoc, the means, the difficult arrays
     labeler.npz               anchors.AnchorLabeler.batch_label_anchors
     labeler_edges.npz         TargetAssigner.assign on edge cases (ties, shared best anchor, IoU 0 / 1, zero area, rows of
                               class -1 with and without filter_valid, 40 boxes); compact: int16 matches, box targets at
@@ -608,6 +610,44 @@ def gen_evaluation():
     save('evaluation', **out)
 
 
+EVAL_SCALE_THRESHOLDS = (0.5, 0.55, 0.75)
+
+
+def gen_evaluation_scale():
+    """gen_evaluation with `difficult` ground truth (drawn per image, in order, from one RandomState(5) per case), one
+    reference evaluator per IoU threshold.  eval_case has distinct scores, so the reference's unstable sort does not matter.
+    The second case is seed 34: seeds 32 and 33 leave fewer than two classes with 0 < AP < 1 at some threshold."""
+    np.float, np.bool, np.NAN = float, bool, np.nan      # as in gen_evaluation
+    from effdet.evaluation.detection_evaluator import ObjectDetectionEvaluator
+    out = {'thresholds': np.array(EVAL_SCALE_THRESHOLDS, np.float64)}
+    for tag, seed, n_img, C, n_det in (('a', 31, 10, 6, 40), ('b', 34, 3, 20, 100)):
+        cats = [{'id': i + 1, 'name': 'c%d' % i} for i in range(C)]
+        images = eval_case(seed, n_img, C, n_det)
+        rs = np.random.RandomState(5)
+        difficult = [rs.uniform(size=len(im['gt_classes'])) < 0.3 for im in images]
+        ap, cl, mean_ap, mean_cl = [], [], [], []
+        for thr in EVAL_SCALE_THRESHOLDS:
+            ev = ObjectDetectionEvaluator(cats, matching_iou_threshold=thr, evaluate_corlocs=True)
+            for i, im in enumerate(images):
+                ev.add_single_ground_truth_image_info(i, {'bbox': im['gt_boxes'], 'cls': im['gt_classes'], 'difficult': difficult[i]})
+                ev.add_single_detected_image_info(i, {'bbox': im['det_boxes'], 'scores': im['det_scores'], 'cls': im['det_classes']})
+            with np.errstate(all='ignore'):
+                m = ev.evaluate(['c%d' % i for i in range(C)])
+            ap.append([m['AP@{}IOU/c{}'.format(thr, i)] for i in range(C)])
+            cl.append([m['CorLoc@{}IOU/c{}'.format(thr, i)] for i in range(C)])
+            mean_ap.append(m['Precision/mAP@{}IOU'.format(thr)])
+            mean_cl.append(m['Precision/meanCorLoc@{}IOU'.format(thr)])
+            inside = np.sum((np.array(ap[-1]) > 0) & (np.array(ap[-1]) < 1))
+            assert inside >= 2, 'case %s at %s: %d classes with 0 < AP < 1 - the fixture would not discriminate' % (tag, thr, inside)
+        out[tag + '_meta'] = np.array([seed, n_img, C, n_det])
+        out[tag + '_difficult'] = np.concatenate(difficult).astype(np.uint8)
+        out[tag + '_ap'] = np.array(ap, np.float64)
+        out[tag + '_cl'] = np.array(cl, np.float64)
+        out[tag + '_map'] = np.array(mean_ap, np.float64)
+        out[tag + '_corloc'] = np.array(mean_cl, np.float64)
+    save_reproducible('evaluation_scale', **out)
+
+
 def gen_transforms():
     """The reference's own transform pipelines (effdet/data/transforms.py:304-368) under a seeded `random` / `np.random`.  What PIL
     is asked to do is recorded by wrapping Image.transpose / resize / crop for the duration of a call."""
@@ -687,6 +727,6 @@ def gen_transforms():
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ['anchors', 'post_process', 'decode', 'soft_nms', 'generate_detections', 'loss',
-                             'labeler', 'labeler_edges', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'meta_nets', 'aux_losses', 'transforms']
+                             'labeler', 'labeler_edges', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'evaluation_scale', 'meta_nets', 'aux_losses', 'transforms']
     for w in which:
         globals()['gen_' + w]()
