@@ -749,6 +749,39 @@ int effdet_ood_eval_sort(void* stream, const float* pos, long long capacity_pos,
 int effdet_ood_eval_metrics(void* stream, long long capacity_pos, long long capacity_neg, const unsigned int* state,
                             void* workspace, long long workspace_bytes, double level, void* result);
 
+/* ---- feature-space OOD scores (csrc/feature_ood.hip): Mahalanobis distance with a tied covariance, and its relative form ----
+ * Rows are features of the BiFPN pyramid, read through a level table of num_levels (<= 8) host arrays: level l holds
+ * level_cells[l] cells; the F channels (float32 or bfloat16, dtype = EFFDET_F32 / EFFDET_BF16; channel stride 1, anything else
+ * is refused) of cell p of image b start at level_bases[l] + b * level_batch_strides[l] + p * level_cell_strides[l] (elements).
+ * P = sum of the cell counts, B * P <= 2^31.  Row (b, j), j < K, is anchor anchor_index[b * K + j] (int64; NULL: anchor j) and
+ * sits on cell anchor / A; it counts when j < count[b] (NULL: all K; int32, or int64 when count_is_int64) and the anchor lies in
+ * [0, A * P).  F is one of 64, 88, 112, 160, 224, 288; 1 <= C <= 1024; B * K <= 2^27.  Bad arguments return -22 before any
+ * launch.  No call synchronises with the host or allocates; results are bit-identical from run to run. */
+/* bytes of the fit workspace for `rows` = B * K rows of width F (pure host code; -22 for a bad argument) */
+long long effdet_feature_ood_workspace_bytes(long long rows, int F);
+/* Adds the valid rows to the running statistics n_c [C] int64, s_c [C][F] float64 (sum of the rows of a class) and S [F][F]
+ * float64 (sum of f f^T over all valid rows).  The class of row (b, j) is classes[b * class_pitch + j * class_stride] -
+ * class_offset (class_dtype 0: int32, 1: int64, 2: float32, truncated); a row whose class lies outside [0, C) is skipped.
+ * Six launches: valid-row counts, bases, compaction in (b, j) order, S partials over 16 fixed row chunks, their sum in chunk
+ * order added to S, one workgroup per class for s_c / n_c.  No floating-point atomics. */
+int effdet_feature_ood_fit(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                           const long long* level_batch_strides, const long long* level_cell_strides,
+                           const long long* level_channel_strides, int F, int C, int A, int B, long long K,
+                           const long long* anchor_index, const void* classes, int class_dtype, long long class_pitch,
+                           long long class_stride, long long class_offset, const void* count, int count_is_int64,
+                           long long* n_c, double* s_c, double* S, void* workspace, long long workspace_bytes);
+/* Scores every row in float32: xc = f - mu0, z = W xc, z0 = W0 xc, d_c = |z|^2 - 2 z.M_c + m2_c,
+ * mahalanobis = -min_c d_c, relative = -(min_c d_c - |z0|^2), nearest = argmin_c d_c (ties to the lower class).  With
+ * Fp = F rounded up to 16 and Cp = C rounded up to 32: W, W0 [Fp][Fp] and M [Cp][Fp] row-major and mu0 [Fp], zero in the padding;
+ * m2 [Cp], +inf for the padding and for classes without rows.  Outputs [B][K]: float32, float32, int32; a row that does not
+ * count holds 0, 0, -1.  The products run on the float32-input MFMA.  One launch. */
+int effdet_feature_ood_score(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                             const long long* level_batch_strides, const long long* level_cell_strides,
+                             const long long* level_channel_strides, int F, int C, int A, int B, long long K,
+                             const long long* anchor_index, const void* count, int count_is_int64, const float* W,
+                             const float* W0, const float* M, const float* m2, const float* mu0, float* mahalanobis,
+                             float* relative, int* nearest);
+
 /* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
 
 /* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at

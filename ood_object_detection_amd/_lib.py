@@ -80,6 +80,13 @@ SIGNATURES = {
                                        c_int, c_void_p, c_ll, c_void_p, c_void_p, c_ll]),
     'effdet_ood_eval_sort': (c_int, [c_void_p, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p, c_ll]),
     'effdet_ood_eval_metrics': (c_int, [c_void_p, c_ll, c_ll, c_void_p, c_void_p, c_ll, c_double, c_void_p]),
+    'effdet_feature_ood_workspace_bytes': (c_ll, [c_ll, c_int]),
+    'effdet_feature_ood_fit': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), c_int, c_int, c_int, c_int,
+                                       c_ll, c_void_p, c_void_p, c_int, c_ll, c_ll, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_ll]),
+    'effdet_feature_ood_score': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), c_int, c_int, c_int,
+                                         c_int, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
     'effdet_sepconv_meta': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_sepconv_tiles': (c_int, [c_int, c_int, c_void_p, c_void_p]),

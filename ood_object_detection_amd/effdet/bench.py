@@ -100,9 +100,13 @@ class DetBenchPredict(nn.Module):
     """`streams` (extension, default: automatic): with two streams the batch is processed as two concurrent
     half-batches - images are independent, so results are identical - and the narrow, latency-bound launches of
     one half (SE gates, top-k sort, NMS: 64 workgroups on a 256-CU chip) overlap with the wide kernels of the
-    other.  The halves run on shallow copies of the model (same parameters, own launch plans and buffers)."""
+    other.  The halves run on shallow copies of the model (same parameters, own launch plans and buffers).
 
-    def __init__(self, model, streams=None):
+    `feature_ood` (extension, default None: nothing changes): a fitted `ood_features.FeatureOOD`; every (sub-)batch is then
+    scored from its engine's pyramid through the gathered anchor index and `last_ood` gains `mahalanobis`,
+    `relative_mahalanobis` and `nearest_class` [B, max_det] (0, 0, -1 beyond `last_count`)."""
+
+    def __init__(self, model, streams=None, feature_ood=None):
         super().__init__()
         self.model = model
         self.config = model.config
@@ -113,6 +117,7 @@ class DetBenchPredict(nn.Module):
         self.max_det_per_image = model.config.max_det_per_image
         self.soft_nms = model.config.soft_nms
         self.streams = streams
+        self.feature_ood = feature_ood
         self.last_count = None
         self.last_ood = None
         self._replicas = None       # [(model copy, stream)], built on first use
@@ -139,7 +144,10 @@ class DetBenchPredict(nn.Module):
                                          model.ood_max_logit.data_ptr(), model.ood_energy.shape[1], B, k,
                                          self.max_det_per_image, energy.data_ptr(), maxlogit.data_ptr(), anchor.data_ptr()),
                    'effdet_gather_ood')
-        return det, count, energy, maxlogit, anchor
+        feat = None
+        if self.feature_ood is not None:
+            feat = self.feature_ood.score(model._engine.pyramid_views(), anchor, count)
+        return det, count, energy, maxlogit, anchor, feat
 
     def _split_setup(self, x, n):
         """Shallow model copies (shared parameters) with engines that write their OOD rows into one [B, N] buffer."""
@@ -179,10 +187,12 @@ class DetBenchPredict(nn.Module):
         B = x.shape[0]
         n = self.streams if self.streams is not None else (2 if B >= 16 and B % 2 == 0 else 1)
         if n <= 1 or B % n or x.device.type != 'cuda':
-            det, count, energy, maxlogit, anchor = self._one(self.model, x, img_scale, img_size)
+            det, count, energy, maxlogit, anchor, feat = self._one(self.model, x, img_scale, img_size)
             self.last_count = count
             self.last_ood = {'energy': energy, 'max_logit': maxlogit, 'anchor_energy': self.model.ood_energy,
                              'anchor_max_logit': self.model.ood_max_logit, 'anchor_index': anchor}
+            if feat is not None:
+                self.last_ood.update(feat)
             return det
         if getattr(_fork, 'depth', 0) > 0 and torch.cuda.is_current_stream_capturing():
             raise RuntimeError('DetBenchPredict(streams=%d) would fork sub-batch streams from a stream that is itself a fork inside '
@@ -205,6 +215,8 @@ class DetBenchPredict(nn.Module):
         self.last_ood = {'energy': torch.cat([o[2] for o in outs], 0), 'max_logit': torch.cat([o[3] for o in outs], 0),
                          'anchor_energy': self._ood_buf[0], 'anchor_max_logit': self._ood_buf[1],
                          'anchor_index': torch.cat([o[4] for o in outs], 0)}
+        if outs[0][5] is not None:
+            self.last_ood.update({k: torch.cat([o[5][k] for o in outs], 0) for k in outs[0][5]})
         return det
 
     def ragged(self, det):

@@ -22,14 +22,14 @@ from .effdet.bench import DetBenchPredict
 
 
 class PipelinedPredict(object):
-    def __init__(self, model, in_flight=3, sub_batches=1, graphs=False):
+    def __init__(self, model, in_flight=3, sub_batches=1, graphs=False, feature_ood=None):
         if in_flight < 1:
             raise ValueError('in_flight must be >= 1')
         p0 = model.backbone.conv_stem.weight
         if p0.device.type != 'cuda':
             raise RuntimeError('PipelinedPredict needs the model on a GPU (no CPU fallback)')
         self.device = p0.device
-        self.slots = [DetBenchPredict(model if i == 0 else copy.copy(model), streams=sub_batches).to(self.device) for i in range(in_flight)]
+        self.slots = [DetBenchPredict(model if i == 0 else copy.copy(model), streams=sub_batches, feature_ood=feature_ood).to(self.device) for i in range(in_flight)]
         self.streams = [torch.cuda.Stream(self.device) for _ in range(in_flight)]
         self._done = [None] * in_flight         # event of the batch that occupies the slot
         self._out = [None] * in_flight
@@ -71,9 +71,12 @@ class PipelinedPredict(object):
                 xin.copy_(x, non_blocking=True)
                 g.replay()
                 # the graph's output tensors are overwritten by the slot's next replay: hand out copies of the small ones
-                self._out[k] = (outs[0].clone(), outs[1].clone(),
-                                {'energy': outs[2]['energy'].clone(), 'max_logit': outs[2]['max_logit'].clone(),
-                                 'anchor_energy': outs[2]['anchor_energy'], 'anchor_max_logit': outs[2]['anchor_max_logit']})
+                ood = {'energy': outs[2]['energy'].clone(), 'max_logit': outs[2]['max_logit'].clone(),
+                       'anchor_energy': outs[2]['anchor_energy'], 'anchor_max_logit': outs[2]['anchor_max_logit']}
+                for name in ('mahalanobis', 'relative_mahalanobis', 'nearest_class'):      # DetBenchPredict(feature_ood=...)
+                    if name in outs[2]:
+                        ood[name] = outs[2][name].clone()
+                self._out[k] = (outs[0].clone(), outs[1].clone(), ood)
             else:
                 det = bench(x, img_info)
                 self._out[k] = (det, bench.last_count, bench.last_ood)

@@ -22,7 +22,7 @@
 static inline int effdet_check_launch() { return 0; }
 typedef void* hipStream_t;
 struct dim3 { int x, y, z; dim3(int a = 1, int b = 1, int c = 1) : x(a), y(b), z(c) {} };
-struct SimCtx { std::barrier<>* block; std::barrier<>* wave; double* xf; int* xi; };
+struct SimCtx { std::barrier<>* block; std::barrier<>* wave; double* xf; int* xi; float* xm; };
 static thread_local dim3 threadIdx, blockIdx, gridDim;
 static thread_local SimCtx simctx;
 static inline void __syncthreads() { simctx.block->arrive_and_wait(); }
@@ -58,12 +58,13 @@ void sim_launch(K kernel, dim3 grid, dim3 block, A... args) {
             std::vector<std::unique_ptr<std::barrier<>>> wb;
             std::vector<std::vector<double>> xf(nw, std::vector<double>(64));
             std::vector<std::vector<int>> xi(nw, std::vector<int>(64));
+            std::vector<std::vector<float>> xm(nw, std::vector<float>(64 * 8));
             for (int w = 0; w < nw; ++w) wb.emplace_back(new std::barrier<>(std::min(64, nt - 64 * w)));
             std::vector<std::thread> th;
             for (int t = 0; t < nt; ++t)
                 th.emplace_back([&, t] {
                     threadIdx = dim3(t); blockIdx = dim3(bx, by); gridDim = grid;
-                    simctx = SimCtx{&bb, wb[t / 64].get(), xf[t / 64].data(), xi[t / 64].data()};
+                    simctx = SimCtx{&bb, wb[t / 64].get(), xf[t / 64].data(), xi[t / 64].data(), xm[t / 64].data()};
                     kernel(args...);
                 });
             for (auto& x : th) x.join();
@@ -71,3 +72,21 @@ void sim_launch(K kernel, dim3 grid, dim3 block, A... args) {
 }
 #define hipLaunchKernelGGL(k, g, b, sh, st, ...) sim_launch(k, g, b, __VA_ARGS__)
 using std::fmax; using std::sqrt; using std::exp;
+// The float32-input MFMA of csrc/common.h's mma_chunk (csrc/feature_ood.hip): four v_mfma_f32_16x16x4_f32 on a 64-byte K-chunk.
+// Lane l supplies row / column (l & 15) and K values 4 * (l >> 4) + s, s = 0 .. 3, of both operands; instruction s multiplies the
+// K values {s, 4 + s, 8 + s, 12 + s}, an fmaf chain in that order (exact float32); C/D: column l & 15, row 4 * (l >> 4) + reg.
+typedef float f32x4 __attribute__((vector_size(16)));
+static inline float __uint_as_float(unsigned v) { float f; std::memcpy(&f, &v, 4); return f; }
+template <typename T> struct Frag;
+template <> struct Frag<float> { f32x4 v; };
+template <typename T> static inline Frag<T> ld_frag(const void* p) { Frag<T> f; std::memcpy(&f.v, p, sizeof(f.v)); return f; }
+static inline void mma_chunk(const Frag<float>& a, const Frag<float>& b, f32x4& acc) {
+    const int lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
+    for (int s = 0; s < 4; ++s) { simctx.xm[lane * 8 + s] = a.v[s]; simctx.xm[lane * 8 + 4 + s] = b.v[s]; }
+    simctx.wave->arrive_and_wait();
+    for (int s = 0; s < 4; ++s)
+        for (int kg = 0; kg < 4; ++kg)
+            for (int r = 0; r < 4; ++r)
+                acc[r] = std::fmaf(simctx.xm[(16 * kg + 4 * g + r) * 8 + s], simctx.xm[(16 * kg + col) * 8 + 4 + s], acc[r]);
+    simctx.wave->arrive_and_wait();
+}
