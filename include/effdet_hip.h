@@ -782,6 +782,40 @@ int effdet_feature_ood_score(void* stream, int dtype, int num_levels, const void
                              const float* W0, const float* M, const float* m2, const float* mu0, float* mahalanobis,
                              float* relative, int* nearest);
 
+/* ---- nearest-neighbour feature OOD score (csrc/feature_knn.hip): a bank of pyramid rows and the k-th nearest of them ----------
+ * Rows are addressed as above (level table, anchor_index, count, A).  The bank is bank [capacity][Fp] float32 (Fp = F rounded up
+ * to 16, zero in the padding), norms [capacity] float32 (|r|^2 of the stored values), bank_classes [capacity] int32 and counters
+ * [3] int64 = {size, seen, lost}, all zero after a clear.  |x|^2 is summed in one fixed order everywhere: 16 partial sums over
+ * k mod 16 (k ascending), then the tree (p[j] + p[j + 8]), (.. + 4), (.. + 2), (.. + 1).  1 <= k <= 32, capacity <= 2^24,
+ * B * K <= 2^27, 0 <= splits <= 64.  Bad arguments return -22 before any launch.  No call synchronises with the host or
+ * allocates; no floating-point atomics; results are bit-identical from run to run. */
+/* bytes of the workspace for `rows` = B * K rows: of append when k = 0, of score with k and `splits` (0: the most the library may
+ * choose for these rows) otherwise (pure host code; -22 for a bad argument) */
+long long effdet_feature_knn_workspace_bytes(long long rows, int F, int k, int splits);
+/* Adds valid rows to the bank in (b, j) order.  A row is valid when j < count[b], its class (as in effdet_feature_ood_fit; C = 0:
+ * no classes, `classes` may be NULL and -1 is stored) lies in [0, C) and its anchor in [0, A * P).  The valid row with global
+ * ordinal g - counted in `seen` since the counters were cleared, across calls - is kept when g % sample_every == 0; kept rows
+ * beyond `capacity` are dropped and counted in `lost`.  normalize != 0 stores r * (1 / sqrt(max(|r|^2, 1e-24))).  Four
+ * launches: valid-row counts, bases and the counter update in one workgroup, the bank row of every entry, the rows. */
+int effdet_feature_knn_append(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                              const long long* level_batch_strides, const long long* level_cell_strides,
+                              const long long* level_channel_strides, int F, int C, int A, int B, long long K,
+                              const long long* anchor_index, const void* classes, int class_dtype, long long class_pitch,
+                              long long class_stride, long long class_offset, const void* count, int count_is_int64,
+                              int normalize, long long sample_every, long long capacity, float* bank, float* norms,
+                              int* bank_classes, long long* counters, void* workspace, long long workspace_bytes);
+/* For every row q (normalised like the bank rows when normalize != 0) and the bank rows r_i, i < M (1 <= M <= 2^24):
+ * d2_i = max((|q|^2 + |r_i|^2) - 2 q.r_i, 0) in float32, q.r_i on the float32-input MFMA.  knn [B][K] float32 = minus the
+ * min(k, M)-th smallest d2; knn_index [B][K] int32 = the lexicographic minimum of (d2, i); knn_class its class; a row that does
+ * not count holds 0, -1, -1.  The bank is walked in `splits` parts (0: chosen by the library); the outputs are bit-identical
+ * for every split count.  Two launches. */
+int effdet_feature_knn_score(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                             const long long* level_batch_strides, const long long* level_cell_strides,
+                             const long long* level_channel_strides, int F, int A, int B, long long K,
+                             const long long* anchor_index, const void* count, int count_is_int64, int normalize, int k,
+                             int splits, long long M, const float* bank, const float* norms, const int* bank_classes,
+                             float* knn, int* knn_index, int* knn_class, void* workspace, long long workspace_bytes);
+
 /* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
 
 /* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at

@@ -96,6 +96,20 @@ def forked_stream(stream):
         _fork.depth -= 1
 
 
+def _feature_scorers(feature_ood):
+    """None, one scorer or a list / tuple of them -> a tuple; the keys their score() dicts carry must not collide"""
+    if feature_ood is None:
+        return ()
+    scorers = tuple(feature_ood) if isinstance(feature_ood, (list, tuple)) else (feature_ood,)
+    seen = {}
+    for s in scorers:
+        for key in getattr(s, 'KEYS', ()):
+            if key in seen:
+                raise ValueError('feature_ood: %s and %s both write last_ood[%r]' % (type(seen[key]).__name__, type(s).__name__, key))
+            seen[key] = s
+    return scorers
+
+
 class DetBenchPredict(nn.Module):
     """`streams` (extension, default: automatic): with two streams the batch is processed as two concurrent
     half-batches - images are independent, so results are identical - and the narrow, latency-bound launches of
@@ -104,7 +118,9 @@ class DetBenchPredict(nn.Module):
 
     `feature_ood` (extension, default None: nothing changes): a fitted `ood_features.FeatureOOD`; every (sub-)batch is then
     scored from its engine's pyramid through the gathered anchor index and `last_ood` gains `mahalanobis`,
-    `relative_mahalanobis` and `nearest_class` [B, max_det] (0, 0, -1 beyond `last_count`)."""
+    `relative_mahalanobis` and `nearest_class` [B, max_det] (0, 0, -1 beyond `last_count`).  An `ood_features.KNNFeatureOOD`
+    adds `knn`, `knn_index` and `knn_class` the same way, and a list / tuple of scorers adds the keys of all of them (two scorers
+    with a common key are refused)."""
 
     def __init__(self, model, streams=None, feature_ood=None):
         super().__init__()
@@ -118,6 +134,7 @@ class DetBenchPredict(nn.Module):
         self.soft_nms = model.config.soft_nms
         self.streams = streams
         self.feature_ood = feature_ood
+        _feature_scorers(feature_ood)             # refuses colliding keys here, not in the first forward
         self.last_count = None
         self.last_ood = None
         self._replicas = None       # [(model copy, stream)], built on first use
@@ -145,8 +162,11 @@ class DetBenchPredict(nn.Module):
                                          self.max_det_per_image, energy.data_ptr(), maxlogit.data_ptr(), anchor.data_ptr()),
                    'effdet_gather_ood')
         feat = None
-        if self.feature_ood is not None:
-            feat = self.feature_ood.score(model._engine.pyramid_views(), anchor, count)
+        scorers = _feature_scorers(self.feature_ood)
+        if scorers:
+            feat = {}
+            for scorer in scorers:
+                feat.update(scorer.score(model._engine.pyramid_views(), anchor, count))
         return det, count, energy, maxlogit, anchor, feat
 
     def _split_setup(self, x, n):

@@ -9,7 +9,15 @@ distance with a tied covariance, and its relative form, over rows of the BiFPN p
 `add*` accumulate n_c, s_c = sum f and S = sum f f^T in float64 on the device (no host synchronisation, capturable in a graph,
 bit-identical from run to run); `fit` reads the (C + F) * F + C numbers back once and forms the whitening factors in float64
 with numpy; `score*` run three float32 products per row on the float32-input MFMA.  A higher score means more in-distribution,
-so both feed `ood.OODEvaluator` unchanged.  There is no CPU fallback."""
+so both feed `ood.OODEvaluator` unchanged.  There is no CPU fallback.
+
+`KNNFeatureOOD` (csrc/feature_knn.hip) is the non-parametric counterpart: a bank of in-distribution rows and minus the squared
+distance to the k-th nearest of them ("deep nearest neighbours", Sun et al. 2022), with the same `add*` / `fit` / `score*` calls:
+
+    f = KNNFeatureOOD(config.fpn_channels, num_anchors, capacity=1 << 18, k=10, num_classes=config.num_classes)
+    f.add_detections(levels, det, bench.last_ood['anchor_index'], bench.last_count)
+    f.fit()
+    bench = DetBenchPredict(model, feature_ood=[maha, f])   # last_ood gains knn, knn_index, knn_class as well"""
 import ctypes
 
 import numpy as np
@@ -92,47 +100,8 @@ def _arr(values, ctype):
     return (ctype * len(values))(*values)
 
 
-class FeatureOOD:
-    """Running class statistics of pyramid features and the two scores that follow from them (module docstring).
-    num_features: the BiFPN width (64, 88, 112, 160, 224 or 288); num_classes <= 1024; num_anchors: anchors per cell (A), so
-    that anchor n sits on cell n // A."""
-
-    def __init__(self, num_features, num_classes, num_anchors, device='cuda'):
-        self.F, self.C, self.A = int(num_features), int(num_classes), int(num_anchors)
-        if self.F not in WIDTHS:
-            raise ValueError('num_features must be one of %r, got %d' % (WIDTHS, self.F))
-        if not 1 <= self.C <= MAX_CLASSES:
-            raise ValueError('num_classes must lie in [1, %d], got %d' % (MAX_CLASSES, self.C))
-        if self.A < 1:
-            raise ValueError('num_anchors must be >= 1')
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('FeatureOOD runs on the GPU (no CPU fallback)')
-        self.shrinkage = None                # set by fit()
-        self.params = None                   # float64 numpy results of the last fit (finalize())
-        self._dev = None                     # their padded float32 uploads
-        self._stats = None
-        self._ws = None
-
-    # ---- storage ---------------------------------------------------------------------------------------------------------
-    def _setup(self):
-        if self._stats is None:
-            dev = self.device
-            self._stats = (torch.zeros(self.C, dtype=torch.int64, device=dev), torch.zeros(self.C, self.F, dtype=torch.float64, device=dev),
-                           torch.zeros(self.F, self.F, dtype=torch.float64, device=dev))
-        return self._stats
-
-    n_c = property(lambda self: self._setup()[0])
-    s_c = property(lambda self: self._setup()[1])
-    S = property(lambda self: self._setup()[2])
-
-    def _workspace(self, rows):
-        need = _lib.load().effdet_feature_ood_workspace_bytes(rows, self.F)
-        if need <= 0:
-            raise ValueError('between 1 and 2^27 rows per call, got %d' % rows)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+class _PyramidRows:
+    """Row addressing shared by the feature-space scorers: the level table and the anchor_index / count arguments of a call."""
 
     def _table(self, levels):
         """levels -> (dtype code, B, P, ctypes arrays of the level table, tensors to keep alive)"""
@@ -147,7 +116,7 @@ class FeatureOOD:
         keep, rows = [], []
         for t in views:
             if not torch.is_tensor(t) or t.device.type != 'cuda':
-                raise RuntimeError('FeatureOOD: features must be GPU tensors (no CPU fallback)')
+                raise RuntimeError('%s: features must be GPU tensors (no CPU fallback)' % type(self).__name__)
             if t.dim() != 4 or t.shape[1] != self.F or t.shape[0] != views[0].shape[0] or t.dtype != views[0].dtype or t.device != views[0].device:
                 raise ValueError('levels must be [B, %d, H, W] tensors of one batch size, dtype and device' % self.F)
             if t.dtype not in (torch.float32, torch.bfloat16):
@@ -185,6 +154,50 @@ class FeatureOOD:
         if K < 1 or B * K > MAX_ROWS:
             raise ValueError('between 1 and 2^27 rows per call')
         return K, ai_ptr, cnt_ptr, cnt64, keep
+
+
+class FeatureOOD(_PyramidRows):
+    """Running class statistics of pyramid features and the two scores that follow from them (module docstring).
+    num_features: the BiFPN width (64, 88, 112, 160, 224 or 288); num_classes <= 1024; num_anchors: anchors per cell (A), so
+    that anchor n sits on cell n // A."""
+    KEYS = ('mahalanobis', 'relative_mahalanobis', 'nearest_class')       # of the dict score() returns
+
+    def __init__(self, num_features, num_classes, num_anchors, device='cuda'):
+        self.F, self.C, self.A = int(num_features), int(num_classes), int(num_anchors)
+        if self.F not in WIDTHS:
+            raise ValueError('num_features must be one of %r, got %d' % (WIDTHS, self.F))
+        if not 1 <= self.C <= MAX_CLASSES:
+            raise ValueError('num_classes must lie in [1, %d], got %d' % (MAX_CLASSES, self.C))
+        if self.A < 1:
+            raise ValueError('num_anchors must be >= 1')
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('FeatureOOD runs on the GPU (no CPU fallback)')
+        self.shrinkage = None                # set by fit()
+        self.params = None                   # float64 numpy results of the last fit (finalize())
+        self._dev = None                     # their padded float32 uploads
+        self._stats = None
+        self._ws = None
+
+    # ---- storage ---------------------------------------------------------------------------------------------------------
+    def _setup(self):
+        if self._stats is None:
+            dev = self.device
+            self._stats = (torch.zeros(self.C, dtype=torch.int64, device=dev), torch.zeros(self.C, self.F, dtype=torch.float64, device=dev),
+                           torch.zeros(self.F, self.F, dtype=torch.float64, device=dev))
+        return self._stats
+
+    n_c = property(lambda self: self._setup()[0])
+    s_c = property(lambda self: self._setup()[1])
+    S = property(lambda self: self._setup()[2])
+
+    def _workspace(self, rows):
+        need = _lib.load().effdet_feature_ood_workspace_bytes(rows, self.F)
+        if need <= 0:
+            raise ValueError('between 1 and 2^27 rows per call, got %d' % rows)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
 
     # ---- fit -------------------------------------------------------------------------------------------------------------
     def clear(self):
@@ -301,4 +314,220 @@ class FeatureOOD:
         for dst, k in zip(self._setup(), ('n_c', 's_c', 'S')):
             dst.add_(torch.as_tensor(od[k]).to(device=self.device, dtype=dst.dtype))
         self.shrinkage = self.params = self._dev = None
+        return self
+
+
+class KNNFeatureOOD(_PyramidRows):
+    """A bank of in-distribution pyramid rows and the k-nearest-neighbour score against it (csrc/feature_knn.hip).
+
+    `add*` append the valid rows to the bank on the device (no host synchronisation, capturable in a graph): the valid row with
+    ordinal g since `clear()` - counted across calls - is kept when g % sample_every == 0, so the bank does not depend on how the
+    rows are split into calls; rows beyond `capacity` are dropped and counted in `lost`.  With `normalize` a row r is stored as
+    r * (1 / sqrt(max(|r|^2, 1e-24))), and queries are treated alike.  `fit` reads the three counters once and fixes the bank size
+    M and k; `score*` return, per row, float32
+
+        knn        = -d2 of the min(k, M)-th nearest bank row,  d2_i = max((|q|^2 + |r_i|^2) - 2 q.r_i, 0)
+        knn_index  = the nearest bank row (the lower row on a tie), knn_class = its class (-1 without classes)
+
+    and 0, -1, -1 at or beyond count[b].  The SQUARED distance is emitted, not its root as in Sun et al.: it is monotone in their
+    score, so every metric of `ood.OODEvaluator` is the same, and its float32 error is absolute and bounded, which the root's is
+    not near zero.  The dot products run on the float32-input MFMA; results are bit-identical from run to run and for every
+    `splits`.  num_features: the BiFPN width; capacity <= 2^24 rows; 1 <= k <= 32; num_classes None: rows carry no class and
+    `classes` may be None.  There is no CPU fallback."""
+    MAX_K, MAX_CAPACITY, MAX_SPLITS = 32, 1 << 24, 64
+    KEYS = ('knn', 'knn_index', 'knn_class')
+
+    def __init__(self, num_features, num_anchors, capacity, k=10, num_classes=None, normalize=True, sample_every=1, device='cuda'):
+        self.F, self.A = int(num_features), int(num_anchors)
+        self.C = 0 if num_classes is None else int(num_classes)
+        self.capacity, self.k, self.normalize, self.sample_every = int(capacity), int(k), bool(normalize), int(sample_every)
+        if self.F not in WIDTHS:
+            raise ValueError('num_features must be one of %r, got %d' % (WIDTHS, self.F))
+        if num_classes is not None and self.C < 1:
+            raise ValueError('num_classes must be >= 1 or None')
+        if self.A < 1:
+            raise ValueError('num_anchors must be >= 1')
+        if not 1 <= self.capacity <= self.MAX_CAPACITY:
+            raise ValueError('capacity must lie in [1, 2^24], got %d' % self.capacity)
+        if not 1 <= self.k <= self.MAX_K:
+            raise ValueError('k must lie in [1, %d], got %d' % (self.MAX_K, self.k))
+        if self.sample_every < 1:
+            raise ValueError('sample_every must be >= 1')
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('KNNFeatureOOD runs on the GPU (no CPU fallback)')
+        self.Fp = (self.F + 15) // 16 * 16
+        self.splits = 0                      # bank parts of a score call; 0: chosen by the library (the results do not depend on it)
+        self.M = None                        # bank rows the scores look at, set by fit()
+        self._bank = None
+
+    # ---- storage ---------------------------------------------------------------------------------------------------------
+    def _setup(self):
+        if self._bank is None:
+            dev = self.device
+            self._bank = (torch.zeros(self.capacity, self.Fp, dtype=torch.float32, device=dev),
+                          torch.zeros(self.capacity, dtype=torch.float32, device=dev),
+                          torch.zeros(self.capacity, dtype=torch.int32, device=dev), torch.zeros(3, dtype=torch.int64, device=dev))
+        return self._bank
+
+    rows = property(lambda self: self._setup()[0])
+    norms = property(lambda self: self._setup()[1])
+    classes = property(lambda self: self._setup()[2])
+    counters = property(lambda self: self._setup()[3])       # size, seen, lost (device, int64)
+
+    def _counts(self):
+        return [int(v) for v in self.counters.cpu()]
+
+    size = property(lambda self: self._counts()[0])          # these three synchronise
+    seen = property(lambda self: self._counts()[1])
+    lost = property(lambda self: self._counts()[2])
+
+    def _workspace(self, rows, k, splits, dev):
+        """A workspace of this call's own (the caching allocator hands it out per stream, so the sub-batch streams of a
+        `DetBenchPredict` do not share one; inside a graph capture it comes from the graph's pool)."""
+        need = _lib.load().effdet_feature_knn_workspace_bytes(rows, self.F, k, splits)
+        if need <= 0:
+            raise ValueError('between 1 and 2^27 rows per call, got %d' % rows)
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+
+    # ---- bank ------------------------------------------------------------------------------------------------------------
+    def clear(self):
+        """Forget every row and the fit (a device-side reset, no synchronisation)."""
+        self.counters.zero_()
+        self.M = None
+
+    def add(self, levels, classes=None, anchor_index=None, count=None, class_offset=0):
+        """Append rows (arguments as `FeatureOOD.add`).  Without num_classes `classes` may be None; with it, a row whose class
+        lies outside [0, num_classes) is skipped."""
+        dt, B, P, table, keep = self._table(levels)
+        dev = keep[0].device
+        K, ai_ptr, cnt_ptr, cnt64, keep2 = self._rows(B, dev, anchor_index, count, self.A * P)
+        cls_ptr, cdt, pitch, stride = None, 0, 0, 0
+        if self.C:
+            if not torch.is_tensor(classes) or classes.device != dev or classes.dim() != 2 or tuple(classes.shape) != (B, K):
+                raise ValueError('classes: a [B, %d] tensor on the device of the features' % K)
+            if classes.dtype not in (torch.int32, torch.int64, torch.float32):
+                raise ValueError('classes must be int32, int64 or float32')
+            classes = classes.detach()
+            if min(classes.stride()) < 0:
+                classes = classes.contiguous()
+            cls_ptr, cdt = classes.data_ptr(), {torch.int32: 0, torch.int64: 1, torch.float32: 2}[classes.dtype]
+            pitch, stride = classes.stride(0), classes.stride(1)
+        bank, norms, bcls, counters = self._setup()
+        ws = self._workspace(B * K, 0, 0, dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().effdet_feature_knn_append(st, dt, *table, self.F, self.C, self.A, B, K, ai_ptr, cls_ptr, cdt, pitch, stride,
+                                                         int(class_offset), cnt_ptr, cnt64, int(self.normalize), self.sample_every,
+                                                         self.capacity, bank.data_ptr(), norms.data_ptr(), bcls.data_ptr(),
+                                                         counters.data_ptr(), ws.data_ptr(), ws.numel()), 'effdet_feature_knn_append')
+        self.M = None
+
+    def add_detections(self, levels, det, anchor_index, count):
+        """Append the kept detections of a `DetBenchPredict` pass: det [B, max_det, 6] (class + 1 in det[..., 5]),
+        anchor_index = bench.last_ood['anchor_index'], count = bench.last_count."""
+        if not torch.is_tensor(det) or det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32:
+            raise ValueError('det must be a float32 [B, max_det, 6] tensor')
+        self.add(levels, det[..., 5] if self.C else None, anchor_index, count, class_offset=1)
+
+    def add_targets(self, levels, cls_targets):
+        """Append every anchor with a class >= 0 of the per-level [B, H, W, A] label maps of `AnchorLabeler` (the dense form; one
+        d0 batch of 64 has about 49 k of them: choose `sample_every`)."""
+        B = cls_targets[0].shape[0]
+        labels = torch.cat([t.reshape(B, -1) for t in cls_targets], 1)
+        if not self.C:
+            raise ValueError('add_targets selects rows by their class: construct with num_classes')
+        self.add(levels, labels)
+
+    def fit(self, k=None):
+        """Fix the bank size M and k for the scores (reads the three counters once: the only synchronisation).  Warns when rows
+        were lost to the capacity; ValueError when the bank is empty."""
+        if k is not None:
+            if not 1 <= int(k) <= self.MAX_K:
+                raise ValueError('k must lie in [1, %d], got %d' % (self.MAX_K, int(k)))
+            self.k = int(k)
+        size, seen, lost = self._counts()
+        if lost > 0:
+            import warnings
+            warnings.warn('KNNFeatureOOD: %d rows beyond the capacity of %d were dropped (raise capacity or sample_every)' % (lost, self.capacity))
+        if size < 1:
+            raise ValueError('KNNFeatureOOD.fit: no rows were added')
+        self.M = size
+        return self
+
+    # ---- score -----------------------------------------------------------------------------------------------------------
+    def _score(self, levels, anchor_index, count, A):
+        if self.M is None:
+            raise RuntimeError('KNNFeatureOOD: fit() comes before score()')
+        dt, B, P, table, keep = self._table(levels)
+        dev = keep[0].device
+        K, ai_ptr, cnt_ptr, cnt64, keep2 = self._rows(B, dev, anchor_index, count, A * P)
+        knn = torch.empty(B, K, dtype=torch.float32, device=dev)
+        idx = torch.empty(B, K, dtype=torch.int32, device=dev)
+        cls = torch.empty(B, K, dtype=torch.int32, device=dev)
+        bank, norms, bcls, _ = self._setup()
+        ws = self._workspace(B * K, self.k, self.splits, dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().effdet_feature_knn_score(st, dt, *table, self.F, A, B, K, ai_ptr, cnt_ptr, cnt64, int(self.normalize), self.k,
+                                                        self.splits, self.M, bank.data_ptr(), norms.data_ptr(), bcls.data_ptr(),
+                                                        knn.data_ptr(), idx.data_ptr(), cls.data_ptr(), ws.data_ptr(), ws.numel()),
+                   'effdet_feature_knn_score')
+        return {'knn': knn, 'knn_index': idx, 'knn_class': cls}
+
+    def score(self, levels, anchor_index, count=None):
+        """Scores of the rows anchor_index [B, K] (int64): dict(knn [B, K] float32 = minus the SQUARED distance to the k-th nearest
+        bank row, knn_index, knn_class [B, K] int32); rows at or beyond count[b] hold 0, -1, -1."""
+        if anchor_index is None:
+            raise ValueError('score() takes an anchor_index; score_cells() scores every cell')
+        return self._score(levels, anchor_index, count, self.A)
+
+    def score_cells(self, levels):
+        """The same keys for every cell of the pyramid, [B, P]."""
+        return self._score(levels, None, None, 1)
+
+    # ---- state -----------------------------------------------------------------------------------------------------------
+    def _geometry(self):
+        return {'num_features': self.F, 'num_anchors': self.A, 'num_classes': self.C or None, 'normalize': self.normalize}
+
+    def state_dict(self):
+        bank, norms, bcls, _ = self._setup()
+        size, seen, lost = self._counts()
+        d = dict(self._geometry(), rows=bank[:size, :self.F].cpu(), norms=norms[:size].cpu(), classes=bcls[:size].cpu(), size=size, seen=seen,
+                 lost=lost, sample_every=self.sample_every, k=self.k, fitted=self.M is not None)
+        return d
+
+    def _check_geometry(self, d, what):
+        for key, mine in self._geometry().items():
+            if d[key] != mine:
+                raise ValueError('%s: %s differs (%r, %r)' % (what, key, d[key], mine))
+
+    def _put(self, at, d):
+        """rows of a state dict -> bank rows [at, at + n); n is cut at the capacity; returns (stored, dropped)"""
+        bank, norms, bcls, _ = self._setup()
+        n = int(d['size'])
+        stored = max(min(n, self.capacity - at), 0)
+        bank[at:at + stored, :self.F] = torch.as_tensor(d['rows'])[:stored].to(device=self.device, dtype=torch.float32)
+        bank[at:at + stored, self.F:] = 0
+        norms[at:at + stored] = torch.as_tensor(d['norms'])[:stored].to(device=self.device, dtype=torch.float32)
+        bcls[at:at + stored] = torch.as_tensor(d['classes'])[:stored].to(device=self.device, dtype=torch.int32)
+        return stored, n - stored
+
+    def load_state_dict(self, d):
+        self._check_geometry(d, 'load_state_dict')
+        stored, dropped = self._put(0, d)
+        self.counters.copy_(torch.tensor([stored, int(d['seen']), int(d['lost']) + dropped], dtype=torch.int64))
+        self.k = int(d.get('k', self.k))
+        self.M = None
+        if d.get('fitted'):
+            self.fit()
+        return self
+
+    def merge_(self, other):
+        """Append the bank of another KNNFeatureOOD (or of its state dict) in its row order, e.g. another rank's; `seen` and
+        `lost` add up; fit() again afterwards.  Reads the counters (synchronises)."""
+        od = other.state_dict() if isinstance(other, KNNFeatureOOD) else other
+        self._check_geometry(od, 'merge_')
+        size, seen, lost = self._counts()
+        stored, dropped = self._put(size, od)
+        self.counters.copy_(torch.tensor([size + stored, seen + int(od['seen']), lost + int(od['lost']) + dropped], dtype=torch.int64))
+        self.M = None
         return self

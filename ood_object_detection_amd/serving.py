@@ -73,8 +73,8 @@ class PipelinedPredict(object):
                 # the graph's output tensors are overwritten by the slot's next replay: hand out copies of the small ones
                 ood = {'energy': outs[2]['energy'].clone(), 'max_logit': outs[2]['max_logit'].clone(),
                        'anchor_energy': outs[2]['anchor_energy'], 'anchor_max_logit': outs[2]['anchor_max_logit']}
-                for name in ('mahalanobis', 'relative_mahalanobis', 'nearest_class'):      # DetBenchPredict(feature_ood=...)
-                    if name in outs[2]:
+                for name in outs[2]:                                      # whatever DetBenchPredict(feature_ood=...) added
+                    if name not in ood and name != 'anchor_index':
                         ood[name] = outs[2][name].clone()
                 self._out[k] = (outs[0].clone(), outs[1].clone(), ood)
             else:

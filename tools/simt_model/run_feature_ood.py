@@ -30,7 +30,8 @@ GUARD = 64
 
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'feature_ood.hip')).read()
+    shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'feature_rows.h'), tmp)      # included by the unit
+    src =open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'feature_ood.hip')).read()
     with open(os.path.join(tmp, 'feature_ood.cpp'), 'w') as f:
         f.write(PRELUDE + src)
     out = os.path.join(tmp, 'libfeature_ood_model.so')
