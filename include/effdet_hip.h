@@ -816,6 +816,35 @@ int effdet_feature_knn_score(void* stream, int dtype, int num_levels, const void
                              int splits, long long M, const float* bank, const float* norms, const int* bank_classes,
                              float* knn, int* knn_index, int* knn_class, void* workspace, long long workspace_bytes);
 
+/* ---- subspace OOD scores (csrc/feature_subspace.hip): residual norm, partial Mahalanobis distance and ViM ----------------------
+ * Rows are addressed as above (level table, anchor_index, count, A).  With Fp = F rounded up to 16 and Rp = the number of
+ * residual directions rounded up to 16 (16 <= Rp <= Fp): Rt [Rp][Fp] row-major holds the directions as rows, inv_lambda [Rp] their
+ * weights and mu0 [Fp] the origin, all float32 and zero in the padding.  Per row, in float32: xc = f - mu0, y = Rt xc on the
+ * float32-input MFMA, r = sqrt(sum_i y_i^2), pm = sum_i inv_lambda_i * y_i^2 (each sum in one fixed order that depends on Rp
+ * alone), t = logit_score[b * ls_pitch + j * ls_stride] (elements), negated when negate != 0.  B * K <= 2^27.  Bad arguments
+ * return -22 before any launch.  No call synchronises with the host or allocates; no floating-point atomics; results are
+ * bit-identical from run to run and do not depend on how the rows are grouped into calls. */
+/* residual [B][K] = -r, partial [B][K] = -pm and, when vim is not NULL (logit_score must then be given), vim [B][K] =
+ * t - alpha * r (the product rounded, then the difference); a row that does not count holds 0 in each.  One launch. */
+int effdet_feature_subspace_score(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                                  const long long* level_batch_strides, const long long* level_cell_strides,
+                                  const long long* level_channel_strides, int F, int A, int B, long long K,
+                                  const long long* anchor_index, const void* count, int count_is_int64, const float* Rt,
+                                  const float* inv_lambda, const float* mu0, int Rp, const float* logit_score, long long ls_pitch,
+                                  long long ls_stride, int negate, float alpha, float* residual, float* partial, float* vim);
+/* Adds, over the rows that count: their number to counters[0] (int64), sum t to sums[0] and sum r to sums[1] (float64), r being
+ * bit-equal to the score's.  A workgroup adds its rows in (b, j) order to one partial in the workspace; one workgroup then adds
+ * the partials in workgroup order.  Two launches. */
+int effdet_feature_subspace_calibrate(void* stream, int dtype, int num_levels, const void* const* level_bases,
+                                      const long long* level_cells, const long long* level_batch_strides,
+                                      const long long* level_cell_strides, const long long* level_channel_strides, int F, int A, int B,
+                                      long long K, const long long* anchor_index, const void* count, int count_is_int64,
+                                      const float* Rt, const float* mu0, int Rp, const float* logit_score, long long ls_pitch,
+                                      long long ls_stride, int negate, long long* counters, double* sums, void* workspace,
+                                      long long workspace_bytes);
+/* bytes of the calibrate workspace for `rows` = B * K rows (pure host code; -22 for a bad argument) */
+long long effdet_feature_subspace_workspace_bytes(long long rows);
+
 /* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
 
 /* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at

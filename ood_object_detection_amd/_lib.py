@@ -94,6 +94,13 @@ SIGNATURES = {
     'effdet_feature_knn_score': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), c_int, c_int, c_int,
                                          c_ll, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_feature_subspace_score': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), c_int, c_int, c_int,
+                                              c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_ll, c_ll,
+                                              c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'effdet_feature_subspace_calibrate': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), c_int, c_int,
+                                                  c_int, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll, c_ll,
+                                                  c_int, c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_feature_subspace_workspace_bytes': (c_ll, [c_ll]),
     'effdet_sepconv_meta': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_sepconv_tiles': (c_int, [c_int, c_int, c_void_p, c_void_p]),

@@ -120,7 +120,9 @@ class DetBenchPredict(nn.Module):
     scored from its engine's pyramid through the gathered anchor index and `last_ood` gains `mahalanobis`,
     `relative_mahalanobis` and `nearest_class` [B, max_det] (0, 0, -1 beyond `last_count`).  An `ood_features.KNNFeatureOOD`
     adds `knn`, `knn_index` and `knn_class` the same way, and a list / tuple of scorers adds the keys of all of them (two scorers
-    with a common key are refused)."""
+    with a common key are refused).  A scorer that declares `WANTS_LOGIT_SCORE = True` (`ood_features.SubspaceFeatureOOD`) also
+    receives `logit_score=`, the gathered `energy` or `max_logit` [B, max_det] its `logit` names: it adds `residual` and
+    `partial_mahalanobis`, and `vim` once its alpha is set."""
 
     def __init__(self, model, streams=None, feature_ood=None):
         super().__init__()
@@ -166,7 +168,11 @@ class DetBenchPredict(nn.Module):
         if scorers:
             feat = {}
             for scorer in scorers:
-                feat.update(scorer.score(model._engine.pyramid_views(), anchor, count))
+                if getattr(scorer, 'WANTS_LOGIT_SCORE', False):
+                    logit = {'energy': energy, 'max_logit': maxlogit}[scorer.logit]
+                    feat.update(scorer.score(model._engine.pyramid_views(), anchor, count, logit_score=logit))
+                else:
+                    feat.update(scorer.score(model._engine.pyramid_views(), anchor, count))
         return det, count, energy, maxlogit, anchor, feat
 
     def _split_setup(self, x, n):

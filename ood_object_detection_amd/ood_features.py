@@ -17,7 +17,17 @@ distance to the k-th nearest of them ("deep nearest neighbours", Sun et al. 2022
     f = KNNFeatureOOD(config.fpn_channels, num_anchors, capacity=1 << 18, k=10, num_classes=config.num_classes)
     f.add_detections(levels, det, bench.last_ood['anchor_index'], bench.last_count)
     f.fit()
-    bench = DetBenchPredict(model, feature_ood=[maha, f])   # last_ood gains knn, knn_index, knn_class as well"""
+    bench = DetBenchPredict(model, feature_ood=[maha, f])   # last_ood gains knn, knn_index, knn_class as well
+
+`SubspaceFeatureOOD` (csrc/feature_subspace.hip) scores a row by its component outside the principal subspace of the
+in-distribution features: the norm of that component (`residual`), its Mahalanobis distance within the low-variance directions
+(`partial_mahalanobis`, Kamoi & Kobayashi 2020) and ViM (Wang et al. 2022), which takes the residual, scaled by alpha, off a logit
+score.  It needs no statistics beyond those `FeatureOOD.add*` accumulates, so it can share them, and its fit cannot fail:
+
+    sub = SubspaceFeatureOOD(config.fpn_channels, config.num_classes, num_anchors, statistics=maha)   # one add* pass fits both
+    sub.fit(explained=0.9)
+    sub.calibrate(levels, anchor_index, count, bench.last_ood['energy']); sub.finish_calibration()     # alpha, for vim
+    bench = DetBenchPredict(model, feature_ood=[maha, f, sub])   # last_ood gains residual, partial_mahalanobis, vim as well"""
 import ctypes
 
 import numpy as np
@@ -69,6 +79,43 @@ def finalize(n_c, s_c, S, shrinkage=0.0):
     M[~have] = 0.0
     m2 = np.where(have, (M * M).sum(1), np.inf)
     return {'mu': mu, 'mu0': mu0, 'cov': cov, 'cov0': cov0, 'W': W, 'W0': W0, 'M': M, 'm2': m2, 'n': n}
+
+
+def finalize_subspace(n_c, s_c, S, dim=None, explained=None, floor=1e-6):
+    """Statistics -> the residual subspace, float64 numpy (parameter-sized host glue, once per fit).
+    mu0 = sum_c s_c / n, cov0 = S / n - mu0 mu0^T (symmetrised) = U diag(lambda) U^T with lambda descending.  The principal
+    dimension D is `dim` (0 <= dim <= F - 1), or the smallest D whose leading eigenvalues sum to at least explained * trace
+    (0 < explained <= 1; capped at F - 1), or F // 2.  Returns dict(mu0 [F], R = U[:, D:] [F, F - D], lambda [F],
+    inv_lambda [F - D] = 1 / max(lambda_i, floor * trace / F) of the residual directions, dim, n)."""
+    n_c = np.asarray(n_c, np.int64)
+    s_c, S = np.asarray(s_c, np.float64), np.asarray(S, np.float64)
+    F = s_c.shape[1]
+    n = int(n_c.sum())
+    if n < 1:
+        raise ValueError('SubspaceFeatureOOD.fit: no rows were added')
+    if dim is not None and explained is not None:
+        raise ValueError('pass dim or explained, not both')
+    if not (float(floor) >= 0.0):
+        raise ValueError('floor must be >= 0')
+    mu0 = s_c.sum(0) / n
+    cov0 = S / n - np.outer(mu0, mu0)
+    lam, U = np.linalg.eigh(0.5 * (cov0 + cov0.T))
+    lam, U = lam[::-1].copy(), U[:, ::-1].copy()
+    trace = float(lam.sum())
+    if dim is not None:
+        D = int(dim)
+        if D != dim or not 0 <= D <= F - 1:
+            raise ValueError('dim must be an integer in [0, %d], got %r' % (F - 1, dim))
+    elif explained is not None:
+        if not 0.0 < float(explained) <= 1.0:
+            raise ValueError('explained must lie in (0, 1], got %r' % (explained,))
+        D = min(int(np.searchsorted(np.cumsum(lam), float(explained) * trace, side='left')) + 1, F - 1)
+    else:
+        D = F // 2
+    low = float(floor) * trace / F
+    with np.errstate(divide='ignore'):
+        inv = 1.0 / np.maximum(lam[D:], low)
+    return {'mu0': mu0, 'R': U[:, D:].copy(), 'lambda': lam, 'inv_lambda': inv, 'dim': D, 'n': n}
 
 
 def merged_state(a, b):
@@ -530,4 +577,210 @@ class KNNFeatureOOD(_PyramidRows):
         stored, dropped = self._put(size, od)
         self.counters.copy_(torch.tensor([size + stored, seen + int(od['seen']), lost + int(od['lost']) + dropped], dtype=torch.int64))
         self.M = None
+        return self
+
+
+class SubspaceFeatureOOD(_PyramidRows):
+    """Subspace scores of pyramid rows (csrc/feature_subspace.hip).  With mu0 and R [F, F - D] of
+    `finalize_subspace` (the eigenvectors of the pooled covariance beyond the D leading ones), per row in float32
+
+        y = R^T (f - mu0),   r = |y|,   residual = -r,   partial_mahalanobis = -sum_i inv_lambda_i y_i^2,   vim = t - alpha r
+
+    where t is a logit score of the row: -energy (the log-sum-exp) for logit='energy', max_logit for logit='max_logit'; `vim` is
+    minus the score of Wang et al. 2022, so that a higher value means more in-distribution like every other key.  The origin is
+    mu0 (the separable-conv class head has no `-(W^T)^+ b`).
+
+    statistics: a `FeatureOOD` of the same geometry whose n_c / s_c / S are shared - one `add*` pass then fits both scorers - or
+    None for statistics of this object's own; `add*` and `clear` go to it.  `fit` reads the statistics back (the one
+    synchronisation) and cannot fail for want of rows.  alpha is given to `fit`, or measured: `calibrate` adds n, sum t and sum r
+    over the valid rows of a call on the device (float64, one fixed order, no atomics, capturable in a graph) and
+    `finish_calibration` sets alpha = sum t / sum r, ViM's rule.  That rule needs a positive mean logit score: the sigmoid heads of
+    a detector can have a negative mean log-sum-exp over weak detections, and then `finish_calibration` refuses - calibrate on rows
+    above a detection-score threshold (through `count`), or pass alpha to `fit`.  This is a property of the method.
+    There is no CPU fallback."""
+    KEYS = ('residual', 'partial_mahalanobis', 'vim')
+    WANTS_LOGIT_SCORE = True                  # DetBenchPredict passes logit_score= (the gathered `logit` key) to score()
+    LOGITS = ('energy', 'max_logit')
+
+    def __init__(self, num_features, num_classes, num_anchors, statistics=None, logit='energy', device='cuda'):
+        if logit not in self.LOGITS:
+            raise ValueError('logit must be one of %r, got %r' % (self.LOGITS, logit))
+        if statistics is None:
+            statistics = FeatureOOD(num_features, num_classes, num_anchors, device=device)
+        elif not isinstance(statistics, FeatureOOD):
+            raise ValueError('statistics must be a FeatureOOD or None')
+        elif (statistics.F, statistics.C, statistics.A) != (int(num_features), int(num_classes), int(num_anchors)):
+            raise ValueError('statistics of another geometry')
+        self.statistics = statistics
+        self.F, self.C, self.A = statistics.F, statistics.C, statistics.A
+        self.device = statistics.device
+        self.logit = logit
+        self.dim = self.floor = self.alpha = None     # set by fit() (alpha also by finish_calibration())
+        self.params = None                            # float64 numpy results of the last fit (finalize_subspace())
+        self._dev = None                              # (Rt [Rp][Fp], inv_lambda [Rp], mu0 [Fp]) float32 uploads
+        self._cal = None
+
+    # ---- statistics ------------------------------------------------------------------------------------------------------
+    def add(self, *args, **kwargs):
+        """`FeatureOOD.add` of the statistics object."""
+        self.statistics.add(*args, **kwargs)
+
+    def add_detections(self, levels, det, anchor_index, count):
+        self.statistics.add_detections(levels, det, anchor_index, count)
+
+    def add_targets(self, levels, cls_targets):
+        self.statistics.add_targets(levels, cls_targets)
+
+    def clear(self):
+        """Forget every row (of the statistics object: a shared one is cleared for both scorers), the fit and the calibration."""
+        self.statistics.clear()
+        self.dim = self.floor = self.alpha = self.params = self._dev = None
+        self.reset_calibration()
+
+    # ---- fit -------------------------------------------------------------------------------------------------------------
+    def fit(self, dim=None, explained=None, floor=1e-6, alpha=None):
+        """Statistics -> residual directions (`finalize_subspace`; reads (C + F) * F + C numbers back, synchronises).  alpha: ViM's
+        scale when it is known; otherwise it stays unset until `finish_calibration`."""
+        st = self.statistics
+        p = finalize_subspace(st.n_c.cpu().numpy(), st.s_c.cpu().numpy(), st.S.cpu().numpy(), dim, explained, floor)
+        self._upload(p)
+        self.params, self.dim, self.floor = p, p['dim'], float(floor)
+        self.alpha = None if alpha is None else float(alpha)
+        return self
+
+    def _upload(self, p):
+        F, Rn = self.F, self.F - p['dim']
+        Fp, Rp = (F + 15) // 16 * 16, (Rn + 15) // 16 * 16
+        Rt, il, mu0 = np.zeros((Rp, Fp), np.float32), np.zeros(Rp, np.float32), np.zeros(Fp, np.float32)
+        Rt[:Rn, :F], il[:Rn], mu0[:F] = p['R'].T, p['inv_lambda'], p['mu0']
+        self._dev = tuple(torch.from_numpy(a).to(self.device) for a in (Rt, il, mu0))
+
+    # ---- calibration -----------------------------------------------------------------------------------------------------
+    def _counters(self):
+        if self._cal is None:
+            self._cal = (torch.zeros(1, dtype=torch.int64, device=self.device), torch.zeros(2, dtype=torch.float64, device=self.device))
+        return self._cal
+
+    def reset_calibration(self):
+        """Zero the three calibration counters (a device-side reset, no synchronisation)."""
+        for t in self._counters():
+            t.zero_()
+
+    def _logit(self, logit_score, B, K, dev):
+        if not torch.is_tensor(logit_score) or logit_score.device != dev or logit_score.dtype != torch.float32 or tuple(logit_score.shape) != (B, K):
+            raise ValueError('logit_score: a float32 [B, %d] tensor on the device of the features' % K)
+        logit_score = logit_score.detach()
+        if min(logit_score.stride()) < 0:
+            logit_score = logit_score.contiguous()
+        return logit_score
+
+    def calibrate(self, levels, anchor_index, count, logit_score):
+        """Add the valid rows (j < count[b]) of a call to n, sum t, sum r on the device; t from logit_score (float32 [B, K], the
+        `logit` key of `last_ood`; strided views are fine) by the sign rule, r under the current fit."""
+        if self._dev is None:
+            raise RuntimeError('SubspaceFeatureOOD: fit() comes before calibrate()')
+        if anchor_index is None:
+            raise ValueError('calibrate() takes an anchor_index')
+        dt, B, P, table, keep = self._table(levels)
+        dev = keep[0].device
+        K, ai_ptr, cnt_ptr, cnt64, keep2 = self._rows(B, dev, anchor_index, count, self.A * P)
+        ls = self._logit(logit_score, B, K, dev)
+        Rt, il, mu0 = self._dev
+        n, sums = self._counters()
+        lib = _lib.load()
+        need = lib.effdet_feature_subspace_workspace_bytes(B * K)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # per call: the caching allocator hands it out per stream
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.effdet_feature_subspace_calibrate(st, dt, *table, self.F, self.A, B, K, ai_ptr, cnt_ptr, cnt64, Rt.data_ptr(),
+                                                         mu0.data_ptr(), Rt.shape[0], ls.data_ptr(), ls.stride(0), ls.stride(1),
+                                                         int(self.logit == 'energy'), n.data_ptr(), sums.data_ptr(), ws.data_ptr(),
+                                                         ws.numel()), 'effdet_feature_subspace_calibrate')
+
+    def calibration(self):
+        """(n, sum t, sum r) so far (synchronises)."""
+        n, sums = self._counters()
+        s = sums.cpu()
+        return int(n.cpu()[0]), float(s[0]), float(s[1])
+
+    def finish_calibration(self):
+        """alpha = sum t / sum r over the calibrated rows (ViM's rule; reads three numbers, synchronises).  ValueError when no row
+        was calibrated or the ratio is not positive - the mean logit score of weak detections of a sigmoid head can be negative:
+        calibrate on rows above a detection-score threshold, or pass alpha to fit()."""
+        n, st, sr = self.calibration()
+        remedy = 'calibrate on rows above a detection-score threshold, or pass fit(alpha=...)'
+        if n == 0:
+            raise ValueError('SubspaceFeatureOOD.finish_calibration: no rows were calibrated: ' + remedy)
+        alpha = st / sr if sr > 0.0 else float('nan')
+        if not alpha > 0.0 or not np.isfinite(alpha):
+            raise ValueError('SubspaceFeatureOOD.finish_calibration: sum t = %g over sum r = %g of %d rows gives no positive alpha: %s'
+                             % (st, sr, n, remedy))
+        self.alpha = alpha
+        return self
+
+    # ---- score -----------------------------------------------------------------------------------------------------------
+    def _score(self, levels, anchor_index, count, A, logit_score):
+        if self._dev is None:
+            raise RuntimeError('SubspaceFeatureOOD: fit() comes before score()')
+        dt, B, P, table, keep = self._table(levels)
+        dev = keep[0].device
+        K, ai_ptr, cnt_ptr, cnt64, keep2 = self._rows(B, dev, anchor_index, count, A * P)
+        res = torch.empty(B, K, dtype=torch.float32, device=dev)
+        pm = torch.empty_like(res)
+        out = {'residual': res, 'partial_mahalanobis': pm}
+        ls_ptr, pitch, stride, vim_ptr, alpha = None, 0, 0, None, 0.0
+        if self.alpha is not None and logit_score is not None:
+            ls = self._logit(logit_score, B, K, dev)
+            out['vim'] = torch.empty_like(res)
+            ls_ptr, pitch, stride, vim_ptr, alpha = ls.data_ptr(), ls.stride(0), ls.stride(1), out['vim'].data_ptr(), self.alpha
+        Rt, il, mu0 = self._dev
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().effdet_feature_subspace_score(st, dt, *table, self.F, A, B, K, ai_ptr, cnt_ptr, cnt64, Rt.data_ptr(),
+                                                             il.data_ptr(), mu0.data_ptr(), Rt.shape[0], ls_ptr, pitch, stride,
+                                                             int(self.logit == 'energy'), alpha, res.data_ptr(), pm.data_ptr(), vim_ptr),
+                   'effdet_feature_subspace_score')
+        return out
+
+    def score(self, levels, anchor_index, count=None, logit_score=None):
+        """Scores of the rows anchor_index [B, K] (int64): dict(residual, partial_mahalanobis [B, K] float32) and, once alpha is set
+        and logit_score (float32 [B, K], the `logit` key of `last_ood`) is given, vim; rows at or beyond count[b] hold 0."""
+        if anchor_index is None:
+            raise ValueError('score() takes an anchor_index; score_cells() scores every cell')
+        return self._score(levels, anchor_index, count, self.A, logit_score)
+
+    def score_cells(self, levels):
+        """residual and partial_mahalanobis for every cell of the pyramid, [B, P] (a cell has no logit score)."""
+        return self._score(levels, None, None, 1, None)
+
+    # ---- state -----------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        d = {k: v for k, v in self.statistics.state_dict().items() if k != 'shrinkage'}
+        n, st, sr = self.calibration()
+        d.update(dim=self.dim, floor=self.floor, alpha=self.alpha, logit=self.logit, calibration=(n, st, sr))
+        return d
+
+    def load_state_dict(self, d):
+        """The statistics go to the statistics object (a shared `FeatureOOD` receives them too and loses its fit)."""
+        self.statistics.load_state_dict({k: d[k] for k in ('num_features', 'num_classes', 'num_anchors', 'n_c', 's_c', 'S')})
+        self.logit = d.get('logit', self.logit)
+        if self.logit not in self.LOGITS:
+            raise ValueError('logit must be one of %r, got %r' % (self.LOGITS, self.logit))
+        self.dim = self.floor = self.alpha = self.params = self._dev = None
+        n, sums = self._counters()
+        cal = d.get('calibration', (0, 0.0, 0.0))
+        n.copy_(torch.tensor([int(cal[0])], dtype=torch.int64))
+        sums.copy_(torch.tensor([float(cal[1]), float(cal[2])], dtype=torch.float64))
+        if d.get('dim') is not None:
+            self.fit(dim=d['dim'], floor=d['floor'], alpha=d.get('alpha'))
+        return self
+
+    def merge_(self, other):
+        """Add the statistics and the calibration counters of another SubspaceFeatureOOD (or of its state dict), e.g. another
+        rank's; fit() again afterwards."""
+        od = other.state_dict() if isinstance(other, SubspaceFeatureOOD) else other
+        self.statistics.merge_({k: od[k] for k in ('num_features', 'num_classes', 'num_anchors', 'n_c', 's_c', 'S')})
+        n, sums = self._counters()
+        cal = od.get('calibration', (0, 0.0, 0.0))
+        n.add_(torch.tensor([int(cal[0])], dtype=torch.int64, device=self.device))
+        sums.add_(torch.tensor([float(cal[1]), float(cal[2])], dtype=torch.float64, device=self.device))
+        self.dim = self.floor = self.alpha = self.params = self._dev = None
         return self
