@@ -701,6 +701,44 @@ int effdet_eval_ap_sorted(void* stream, const float* scores, const int* classes,
                           long long n, const unsigned int* state, int num_thresholds, int num_classes, const int* gt_count,
                           const int* gt_imgs, const int* correct_imgs, void* workspace, long long workspace_bytes, void* result);
 
+/* ---- open-set detection evaluation (csrc/eval_scale.hip): unknown recall, A-OSE, wilderness impact ----------------------------
+ * `num_classes` counts the unknown class here: the known classes are 1 .. num_classes - 1, the unknown class is U = num_classes,
+ * in the ground truth and in the detections; matching is effdet_eval_match_multi with these num_classes. */
+
+/* After effdet_eval_match_multi: open [B,max_det], bit t = the row is kept (no bit 31 in `flags`), its class is known and the
+ * largest IoU (the float32 expression of the matching, inter / (area_d + area_g - inter)) between its box and the image's
+ * ground-truth boxes of class U, difficult or not, is >= thresholds[t]; 0 for every other row.  One workgroup per image, the
+ * unknown boxes staged in static LDS 256 ground-truth rows at a time: any M > 0. */
+int effdet_eval_open_words(void* stream, const float* det, const unsigned int* flags, const float* gt_boxes, const long long* gt_cls,
+                           int B, int max_det, int M, int num_classes, const float* thresholds, int num_thresholds,
+                           unsigned int* open);
+/* effdet_eval_append that also appends the open words to out_open at the same positions (one cursor, one count of lost entries
+ * and of NaN scores). */
+int effdet_eval_append_open(void* stream, const float* det, const unsigned int* flags, const unsigned int* open, const int* kept,
+                            int B, int max_det, float* scores, int* classes, unsigned int* out_flags, unsigned int* out_open,
+                            long long capacity, unsigned int* state);
+/* pure host queries, as for effdet_eval_ap_sorted; which = 2: the sorted open words */
+long long effdet_eval_open_sorted_workspace_bytes(long long capacity, int num_classes);
+long long effdet_eval_open_sorted_offset(long long capacity, int num_classes, int which);
+long long effdet_eval_open_sorted_result_bytes(int num_thresholds, int num_classes);
+/* effdet_eval_ap_sorted (the same sort kernels with the open word as a second payload, the same AP kernel: the same bits) over
+ * num_classes classes, then one workgroup per (class, threshold) for the open-set counts.  result: the block of
+ * effdet_eval_ap_sorted, followed by seven int64 matrices [T][num_classes] over a class's kept entries in sorted order (positions
+ * from 0, ctp_p = true positives at positions <= p): n_det (not ignored), tp, open_total (open bit set, ignored or not), and, where
+ * the class has ground truth and an entry (otherwise 0, 0, -1, 0, 0): k_star = the cumulative count among those reachable
+ * whose recall k / gt_count is nearest recall_level in float64 (ties: the smaller), pos = the first position with ctp = k_star,
+ * rank_at / open_at = entries not ignored / with the open bit at positions <= pos.  0 < recall_level <= 1.  Capturable;
+ * bit-identical from run to run. */
+int effdet_eval_open_sorted(void* stream, const float* scores, const int* classes, const unsigned int* flags,
+                            const unsigned int* open, long long capacity, long long n, const unsigned int* state, int num_thresholds,
+                            int num_classes, const int* gt_count, const int* gt_imgs, const int* correct_imgs, double recall_level,
+                            void* workspace, long long workspace_bytes, void* result);
+/* det_out [B,max_det,6] = det_in with the class (column 5) of row (b, j) set to num_known + 1 where j < count[b], the class is in
+ * 1..num_known and !(score[b * pitch + j * stride] >= tau) (a NaN score becomes unknown); every other row is copied.  tau is read
+ * from tau_device on the device when that is not NULL.  det_out may be det_in.  One launch. */
+int effdet_relabel_unknown(void* stream, const float* det_in, const int* count, const float* score, long long pitch,
+                           long long stride, int B, int max_det, int num_known, float tau, const float* tau_device, float* det_out);
+
 /* ---- OOD evaluation helpers -------------------------------------------- */
 
 /* The fork's novelty score (infer.py:425-427, 465-471, 607-616), reported beside energy / max-logit:

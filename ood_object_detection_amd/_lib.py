@@ -163,6 +163,17 @@ SIGNATURES = {
     'effdet_eval_ap_sorted_result_bytes': (c_ll, [c_int, c_int]),
     'effdet_eval_ap_sorted': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'effdet_eval_open_words': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                       c_void_p]),
+    'effdet_eval_append_open': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_ll, c_void_p]),
+    'effdet_eval_open_sorted_workspace_bytes': (c_ll, [c_ll, c_int]),
+    'effdet_eval_open_sorted_offset': (c_ll, [c_ll, c_int, c_int]),
+    'effdet_eval_open_sorted_result_bytes': (c_ll, [c_int, c_int]),
+    'effdet_eval_open_sorted': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_ll, c_void_p]),
+    'effdet_relabel_unknown': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_int, c_int, c_int, c_float, c_void_p,
+                                       c_void_p]),
     'effdet_train_fold_bn': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_train_convbn_grads': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

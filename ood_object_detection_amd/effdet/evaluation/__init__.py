@@ -1,2 +1,3 @@
 from .detection_evaluator import ObjectDetectionEvaluator, PascalDetectionEvaluator  # noqa: F401
 from .dataset_evaluator import DatasetDetectionEvaluator  # noqa: F401
+from .open_set_evaluator import OpenSetDetectionEvaluator  # noqa: F401

@@ -7,7 +7,8 @@ per image, all thresholds), then the valid rows go to capacity-sized device buff
 `enqueue()` sorts (class, score descending, equal scores in arrival order) and computes AP per (threshold, class); `result()`
 is the one device-to-host copy.  Nothing before `result()` synchronises with the host, so `add_batch` and `enqueue` can be
 captured in a `torch.cuda.graph`; the same images give the same bits however they are split into `add_batch` calls.  No CPU
-fallback.  Not built (they raise): group-of boxes, masks, weighted mAP, precision / recall curves, recall bounds.
+fallback.  Not built (they raise): group-of boxes, masks, weighted mAP, full precision / recall curves, recall bounds.  The
+precision at ONE recall level, per-class recall / precision and the open-set metrics are in open_set_evaluator.py.
 """
 import ctypes
 
@@ -98,12 +99,15 @@ class DatasetDetectionEvaluator(SingleImageAPI):
             self._bufs = (torch.empty(self.capacity, dtype=torch.float32, device=dev),
                           torch.empty(self.capacity, dtype=torch.int32, device=dev),
                           torch.empty(self.capacity, dtype=torch.int32, device=dev))
-        self._ws = torch.empty(self.lib.effdet_eval_ap_sorted_workspace_bytes(self.capacity, C) // 8, dtype=torch.int64, device=dev)
-        self._result = torch.zeros(self.lib.effdet_eval_ap_sorted_result_bytes(T, C) // 8, dtype=torch.int64, device=dev)
+        self._alloc_blocks(T, C, dev)
         self._state = torch.zeros(4, dtype=torch.int32, device=dev)          # cursor, lost, NaN scores, 0
         self._counters = torch.zeros(2 * C + T * C, dtype=torch.int32, device=dev)
         self._gt_count, self._gt_imgs, self._correct = self._counters[:C], self._counters[C:2 * C], self._counters[2 * C:]
         self._reset_host()
+
+    def _alloc_blocks(self, T, C, dev):
+        self._ws = torch.empty(self.lib.effdet_eval_ap_sorted_workspace_bytes(self.capacity, C) // 8, dtype=torch.int64, device=dev)
+        self._result = torch.zeros(self.lib.effdet_eval_ap_sorted_result_bytes(T, C) // 8, dtype=torch.int64, device=dev)
 
     def _reset_host(self):
         self._pending_gt = {}
@@ -126,6 +130,15 @@ class DatasetDetectionEvaluator(SingleImageAPI):
         """det [B, max_det, 6] rows x1,y1,x2,y2,score,class (1-based) in descending score order, `count[b]` valid rows; gt_boxes
         [B, M, 4] yxyx, gt_cls [B, M] 1-based (<= 0: padding), gt_difficult [B, M] bool or None.  -> flag words [B, max_det] int32:
         bit t = true positive at threshold t, bit 16 + t = ignored there, bit 31 (negative) = dropped."""
+        det, flags, kept, _, _ = self._match(det, count, gt_boxes, gt_cls, gt_difficult)
+        B, max_det, _ = det.shape
+        _lib.check(self.lib.effdet_eval_append(self._st(), det.data_ptr(), flags.data_ptr(), kept.data_ptr(), B, max_det,
+                                               self._bufs[0].data_ptr(), self._bufs[1].data_ptr(), self._bufs[2].data_ptr(),
+                                               self.capacity, self._state.data_ptr()), 'effdet_eval_append')
+        return flags
+
+    def _match(self, det, count, gt_boxes, gt_cls, gt_difficult):
+        """the matching launch of `add_batch` -> (det, flags, kept [2 B], gt_boxes, gt_cls) as the device saw them"""
         dev = self.device
         det = det.to(device=dev, dtype=torch.float32).contiguous()
         count = count.to(device=dev, dtype=torch.int32).contiguous()
@@ -149,10 +162,7 @@ class DatasetDetectionEvaluator(SingleImageAPI):
                                                     self._num_classes, self._thr, len(self._thresholds), flags.data_ptr(),
                                                     kept.data_ptr(), self._gt_count.data_ptr(), self._gt_imgs.data_ptr(),
                                                     self._correct.data_ptr()), 'effdet_eval_match_multi')
-        _lib.check(self.lib.effdet_eval_append(st, det.data_ptr(), flags.data_ptr(), kept.data_ptr(), B, max_det,
-                                               self._bufs[0].data_ptr(), self._bufs[1].data_ptr(), self._bufs[2].data_ptr(),
-                                               self.capacity, self._state.data_ptr()), 'effdet_eval_append')
-        return flags
+        return det, flags, kept, gt_boxes, gt_cls
 
     def enqueue(self):
         """Sort + metrics into the result block on the device; no host synchronisation."""
@@ -171,20 +181,24 @@ class DatasetDetectionEvaluator(SingleImageAPI):
         r['block'] = block.numpy()
         return r
 
+    def _sorted_offsets(self):
+        return [self.lib.effdet_eval_ap_sorted_offset(self.capacity, self._num_classes, w) for w in (0, 1)]
+
     def sorted(self):
         """After `enqueue()`: (class [n] int64, score [n] float32, flag word [n] uint32) of the valid entries in the sorted order
         (debug / test accessor; synchronises)."""
         C = self._num_classes
         ws = self._ws.view(torch.uint8)
-        ko, fo = (self.lib.effdet_eval_ap_sorted_offset(self.capacity, C, w) for w in (0, 1))
+        offs = self._sorted_offsets()
+        ko = offs[0]
         n = min(int(self._state[0].item()), self.capacity)
         keys = ws[ko:ko + 8 * n].cpu().numpy().view(np.uint64)
-        flags = ws[fo:fo + 4 * n].cpu().numpy().view(np.uint32)
+        words = [ws[o:o + 4 * n].cpu().numpy().view(np.uint32) for o in offs[1:]]
         cls = (keys >> np.uint64(32)).astype(np.int64)
         k = ~(keys & np.uint64(0xFFFFFFFF)).astype(np.uint32)                 # the order-preserving map of the float32 bits
         bits = np.where(k & np.uint32(0x80000000), k ^ np.uint32(0x80000000), ~k)
         valid = cls < C
-        return cls[valid], bits.view(np.float32)[valid], flags[valid]
+        return (cls[valid], bits.view(np.float32)[valid]) + tuple(w[valid] for w in words)
 
     def evaluate(self, task_categories=None, batch_cats=None):
         """Metric dict with the reference's keys (detection_evaluator.py:268-305) at every threshold, and with more than one

@@ -211,6 +211,12 @@ class OODEvaluator:
         return {'auroc': (gt + 0.5 * eq) / (P * N), 'aupr_in': aupr_in, 'aupr_out': aupr_out, 'fpr_at_tpr': fp / N, 'tpr': tp / P,
                 'threshold': threshold, 'tp': tp, 'fp': fp, 'pairs_gt': gt, 'pairs_eq': eq, 'n_in': P, 'n_ood': N}
 
+    def threshold_tensor(self):
+        """The `threshold` of the last `enqueue` where it lies on the device: a 0-d float32 view of the result block (word 10, low
+        half), so `enqueue`, `relabel_unknown` and an evaluator's `add_batch` chain without a host read and capture together."""
+        self._setup()
+        return self._result.view(torch.float32)[20]
+
     def evaluate(self, recall_level=0.95):
         """Sort both sides and evaluate; the only call that synchronises.  Returns dict(auroc, aupr_in, aupr_out, fpr_at_tpr,
         tpr, threshold, tp, fp, pairs_gt, pairs_eq, n_in, n_ood): in-distribution is the positive class of auroc / aupr_in,
@@ -225,6 +231,47 @@ class OODEvaluator:
         if self._bufs is None or self._counts is None:
             raise RuntimeError('sorted_scores() follows evaluate()')
         return tuple(self._ws[off:off + 4 * n].view(torch.float32) for off, n in zip(self._sorted_off, self._counts))
+
+
+def relabel_unknown(det, count, scores, threshold, num_classes, out=None):
+    """Detections whose in-distribution score misses the threshold become the unknown class `num_classes + 1` (one launch):
+    det [B, max_det, 6] float32 rows x1,y1,x2,y2,score,class (1-based); row (b, j) gets class num_classes + 1 where j < count[b],
+    its class is in 1..num_classes and not scores[b, j] >= threshold (a NaN score becomes unknown); every other row is copied.
+    scores: [B, max_det] float32, any non-negative strides (a view of `DetBenchPredict.last_ood`, `-energy`, ...).  threshold: a
+    float, or a 0-d float32 GPU tensor read on the device (`OODEvaluator.threshold_tensor()`).  out: the tensor to write, `det`
+    itself for in-place use; None allocates one."""
+    for t, what in ((det, 'det'), (scores, 'scores')):
+        _check_scores(t, what)
+    if det.dim() != 3 or det.shape[2] != 6 or not det.is_contiguous():
+        raise ValueError('det must be a contiguous [B, max_det, 6] tensor')
+    B, max_det, _ = det.shape
+    if tuple(scores.shape) != (B, max_det) or scores.device != det.device:
+        raise ValueError('scores must be [B, max_det] on the device of det')
+    if not 1 <= int(num_classes) <= 65534:
+        raise ValueError('num_classes must lie in [1, 65534]')
+    if not torch.is_tensor(count) or count.device != det.device or count.numel() != B:
+        raise ValueError('count: a tensor of B entries on the device of det')
+    count = count.detach().reshape(B).to(torch.int32).contiguous()
+    scores = scores.detach()
+    if min(scores.stride()) < 0:
+        scores = scores.contiguous()
+    tau, tau_ptr = 0.0, None
+    if torch.is_tensor(threshold):
+        if threshold.device != det.device or threshold.dtype != torch.float32 or threshold.numel() != 1:
+            raise ValueError('threshold: a float or a 0-d float32 tensor on the device of det')
+        tau_ptr = threshold.data_ptr()
+    else:
+        tau = float(threshold)
+    if out is None:
+        out = torch.empty_like(det)
+    elif out.device != det.device or out.dtype != torch.float32 or out.shape != det.shape or not out.is_contiguous():
+        raise ValueError('out must be a contiguous float32 tensor like det')
+    if B * max_det:
+        st = torch.cuda.current_stream(det.device).cuda_stream
+        _lib.check(_lib.load().effdet_relabel_unknown(st, det.data_ptr(), count.data_ptr(), scores.data_ptr(), scores.stride(0),
+                                                      scores.stride(1), B, max_det, int(num_classes), tau, tau_ptr, out.data_ptr()),
+                   'effdet_relabel_unknown')
+    return out
 
 
 def detection_metrics(in_dist_scores: torch.Tensor, ood_scores: torch.Tensor, recall_level: float = 0.95):
