@@ -883,6 +883,40 @@ int effdet_feature_subspace_calibrate(void* stream, int dtype, int num_levels, c
 /* bytes of the calibrate workspace for `rows` = B * K rows (pure host code; -22 for a bad argument) */
 long long effdet_feature_subspace_workspace_bytes(long long rows);
 
+/* ---- logit-space OOD scores (csrc/logit_ood.hip): MSP, entropy, GEN, JointEnergy, KL matching, standardized max logit ----------
+ * Rows are the C class logits (float32 or bfloat16, dtype = EFFDET_F32 / EFFDET_BF16, class stride 1) of anchor n of image b at
+ * logits + b * image_stride + n * anchor_stride (elements, both >= 0), n < N <= 2^31.  Row (b, j), j < K, is anchor
+ * anchor_index[b * K + j] (int64; NULL: anchor j); it counts when j < count[b] (NULL: all K; int32, or int64 when count_is_int64)
+ * and the anchor lies in [0, N).  1 <= C <= 1024, B * K <= 2^27, temperature > 0.  Bad arguments return -22 before any launch.
+ * No call synchronises with the host or allocates; no floating-point atomics; results are bit-identical from run to run and a
+ * row's scores do not depend on how the rows are grouped into calls. */
+/* Per row in float32, with u = z / temperature, m = max u, k* the lowest argmax, e_k = exp(u_k - m), s = sum e, lse = m + log s,
+ * l_k = u_k - lse, p_k = exp(l_k):  msp = exp(m - lse);  neg_entropy = sum p_k l_k;  gen = -sum over the top_m largest u_k (equal
+ * values: the lower k first; top_m >= C: all) of exp(gamma * (l_k + q_k)), q_k = log1p(-p_k) for k != k* and
+ * log(sum_{k != k*} e_k) - log s for k*;  joint_energy = sum max(z_k, 0) + log1p(exp(-|z_k|));  predicted_class = k* (int64).
+ * With Cp = C rounded up to 16 and the fitted parameters log_d [Cp][Cp] (row c: log of template c; zero in the padding and in
+ * classes without rows), kl_inf [Cp] (0, or +inf for the padding and for classes without rows), mu [C], inv_sigma [C] - all
+ * NULL or all given, together with their three outputs:  kl_c = (neg_entropy - sum_k p_k log_d[c][k]) + kl_inf[c] with p and
+ * neg_entropy taken at temperature 1, the product on the float32-input MFMA;  kl_matching = -min_c kl_c;  kl_class = argmin
+ * (ties to the lower class);  standardized = (max z - mu[k*]) * inv_sigma[k*].  Outputs [B][K]; a row that does not count holds
+ * 0 in the float outputs and -1 in the class outputs.  One launch. */
+int effdet_logit_ood_score(void* stream, int dtype, const void* logits, long long image_stride, long long anchor_stride, int C, int B,
+                           long long N, long long K, const long long* anchor_index, const void* count, int count_is_int64,
+                           float temperature, float gamma, int top_m, const float* log_d, const float* kl_inf, const float* mu,
+                           const float* inv_sigma, float* msp, float* neg_entropy, float* gen, float* joint_energy,
+                           long long* predicted_class, float* kl_matching, long long* kl_class, float* standardized);
+/* Adds the rows that count (and, when use_min != 0, whose max z >= min_max_logit) to the running statistics of their predicted
+ * class c: n_c [C] int64, P_c [C][C] float64 (sum of p at temperature 1), a_c [C] and b_c [C] float64 (sum of max z and of its
+ * square).  The valid rows are compacted in (b, j) order; workgroup (c, s) adds the rows of class c of chunk s of that list in list
+ * order to a float64 partial, the chunks are added in chunk order and then to the statistics: the order depends on the number of
+ * valid rows and C alone.  Six launches. */
+int effdet_logit_ood_fit(void* stream, int dtype, const void* logits, long long image_stride, long long anchor_stride, int C, int B,
+                         long long N, long long K, const long long* anchor_index, const void* count, int count_is_int64,
+                         float temperature, int use_min, float min_max_logit, long long* n_c, double* P_c, double* a_c, double* b_c,
+                         void* workspace, long long workspace_bytes);
+/* bytes of the fit workspace for `rows` = B * K rows of C classes (pure host code; -22 for a bad argument) */
+long long effdet_logit_ood_workspace_bytes(long long rows, int C);
+
 /* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
 
 /* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at

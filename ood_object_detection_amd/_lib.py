@@ -101,6 +101,12 @@ SIGNATURES = {
                                                   c_int, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll, c_ll,
                                                   c_int, c_void_p, c_void_p, c_void_p, c_ll]),
     'effdet_feature_subspace_workspace_bytes': (c_ll, [c_ll]),
+    'effdet_logit_ood_score': (c_int, [c_void_p, c_int, c_void_p, c_ll, c_ll, c_int, c_int, c_ll, c_ll, c_void_p, c_void_p, c_int, c_float,
+                                       c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_logit_ood_fit': (c_int, [c_void_p, c_int, c_void_p, c_ll, c_ll, c_int, c_int, c_ll, c_ll, c_void_p, c_void_p, c_int, c_float,
+                                     c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_logit_ood_workspace_bytes': (c_ll, [c_ll, c_int]),
     'effdet_sepconv_meta': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_sepconv_tiles': (c_int, [c_int, c_int, c_void_p, c_void_p]),

@@ -122,7 +122,10 @@ class DetBenchPredict(nn.Module):
     adds `knn`, `knn_index` and `knn_class` the same way, and a list / tuple of scorers adds the keys of all of them (two scorers
     with a common key are refused).  A scorer that declares `WANTS_LOGIT_SCORE = True` (`ood_features.SubspaceFeatureOOD`) also
     receives `logit_score=`, the gathered `energy` or `max_logit` [B, max_det] its `logit` names: it adds `residual` and
-    `partial_mahalanobis`, and `vim` once its alpha is set."""
+    `partial_mahalanobis`, and `vim` once its alpha is set.  A scorer that declares `WANTS_CLASS_LOGITS = True`
+    (`ood_logits.LogitOOD`) is given the packed class logits [B, N, C] of the (sub-)batch instead of the pyramid (a view of the
+    engine's own buffer, no copy): it adds `msp`, `neg_entropy`, `gen`, `joint_energy`, `predicted_class` and, once fitted,
+    `kl_matching`, `kl_class` and `standardized_max_logit`."""
 
     def __init__(self, model, streams=None, feature_ood=None):
         super().__init__()
@@ -168,7 +171,9 @@ class DetBenchPredict(nn.Module):
         if scorers:
             feat = {}
             for scorer in scorers:
-                if getattr(scorer, 'WANTS_LOGIT_SCORE', False):
+                if getattr(scorer, 'WANTS_CLASS_LOGITS', False):
+                    feat.update(scorer.score(_packed(class_out, self.num_levels, self.num_classes), anchor, count))
+                elif getattr(scorer, 'WANTS_LOGIT_SCORE', False):
                     logit = {'energy': energy, 'max_logit': maxlogit}[scorer.logit]
                     feat.update(scorer.score(model._engine.pyramid_views(), anchor, count, logit_score=logit))
                 else:
