@@ -1,0 +1,102 @@
+// Workgroup reductions and the ordered compaction of the OOD units (feature_ood.hip, feature_knn.hip, logit_ood.hip, ood_eval.hip;
+// DESIGN.md §8): the kept entries of a [B, K] call get consecutive positions in (b, j) order by three launches - kept entries per
+// tile of 2048 (fo_count_kernel), the tiles' first positions in one workgroup (fo_base_kernel), then ballot ranks inside a tile
+// (fo_positions, called by the unit's own write kernel).  No atomic decides a position.  A unit describes its compaction by a struct
+// A with `unsigned* counts` ([nblocks]), `unsigned nblocks` and three overloads beside it:
+//   bool cp_keep(const A&, unsigned i)                          is entry i kept?  (false at i >= total)
+//   unsigned cp_begin(const A&)                                 the position of the first kept entry
+//   void cp_finish(const A&, unsigned begin, unsigned total)    thread 0 of the base workgroup: publish the number of kept entries
+#pragma once
+#include "common.h"
+
+namespace {
+
+constexpr int FO_THREADS = 256;
+constexpr int FO_ITEMS = 8;
+constexpr int FO_TILE = FO_THREADS * FO_ITEMS;                  // [B, K] entries of one compaction workgroup
+
+DEV unsigned fo_min(unsigned a, unsigned b) { return a < b ? a : b; }
+DEV unsigned fo_popc(unsigned long long m) { return (unsigned)__builtin_popcountll(m); }
+
+// All FO_THREADS threads call these; sh: [FO_THREADS] of T in LDS.  Fixed order, so a float64 sum has the same bits every run.
+template <typename T> DEV T fo_block_sum(T v, T* sh, int tid) {
+    sh[tid] = v;
+    __syncthreads();
+    for (int s = FO_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
+        __syncthreads();
+    }
+    const T r = sh[0];
+    __syncthreads();
+    return r;
+}
+DEV unsigned fo_block_excl_scan(unsigned v, unsigned* sh, int tid, unsigned* total) {
+    sh[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < FO_THREADS; off <<= 1) {
+        const unsigned t = tid >= off ? sh[tid - off] : 0u;
+        __syncthreads();
+        sh[tid] += t;
+        __syncthreads();
+    }
+    const unsigned incl = sh[tid];
+    *total = sh[FO_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+template <typename A> __global__ __launch_bounds__(256) void fo_count_kernel(A a) {
+    __shared__ unsigned sh[FO_THREADS];
+    const int tid = threadIdx.x;
+    const unsigned base = (unsigned)blockIdx.x * FO_TILE;
+    unsigned c = 0;
+    for (int r = 0; r < FO_ITEMS; ++r) c += cp_keep(a, base + r * FO_THREADS + tid) ? 1u : 0u;
+    const unsigned tot = fo_block_sum<unsigned>(c, sh, tid);
+    if (tid == 0) a.counts[blockIdx.x] = tot;
+}
+
+// one workgroup: counts -> first positions of the workgroups
+template <typename A> __global__ __launch_bounds__(256) void fo_base_kernel(A a) {
+    __shared__ unsigned sh[FO_THREADS];
+    const int tid = threadIdx.x;
+    const unsigned begin = cp_begin(a);
+    const unsigned chunk = (a.nblocks + FO_THREADS - 1) / FO_THREADS;
+    const unsigned lo = fo_min((unsigned)tid * chunk, a.nblocks), hi = fo_min(lo + chunk, a.nblocks);
+    unsigned sum = 0;
+    for (unsigned k = lo; k < hi; ++k) sum += a.counts[k];
+    unsigned total;
+    unsigned run = begin + fo_block_excl_scan(sum, sh, tid, &total);
+    for (unsigned k = lo; k < hi; ++k) { const unsigned c = a.counts[k]; a.counts[k] = run; run += c; }
+    if (tid == 0) cp_finish(a, begin, total);                   // the scan's barriers order what cp_begin read before what this writes
+}
+
+// entry r (< FO_ITEMS) of this lane in a write kernel: wave w of a workgroup owns entries [w * 512, (w + 1) * 512) of its tile, 64
+// consecutive ones per round, so positions follow (b, j)
+DEV unsigned fo_entry(int r) {
+    return (unsigned)blockIdx.x * FO_TILE + (threadIdx.x >> 6) * (64 * FO_ITEMS) + r * 64 + (threadIdx.x & 63);
+}
+// The write step, called by all FO_THREADS threads of workgroup blockIdx.x: bit r of the result says whether keep(r, fo_entry(r))
+// held, and pos[r] is then the entry's position (counts: the bases fo_base_kernel left).  The caller compares it with its capacity.
+template <typename Keep> DEV unsigned fo_positions(const unsigned* counts, unsigned (&pos)[FO_ITEMS], Keep keep) {
+    __shared__ unsigned wsum[FO_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned kept = 0, wtot = 0;
+#pragma unroll
+    for (int r = 0; r < FO_ITEMS; ++r) {
+        const bool k = keep(r, fo_entry(r));
+        const unsigned long long bal = __ballot(k);
+        pos[r] = wtot + fo_popc(bal & below);
+        wtot += fo_popc(bal);
+        kept |= (k ? 1u : 0u) << r;
+    }
+    if (lane == 0) wsum[wave] = wtot;
+    __syncthreads();
+    unsigned first = counts[blockIdx.x];
+    for (int w = 0; w < FO_THREADS / 64; ++w) first += w < wave ? wsum[w] : 0u;
+#pragma unroll
+    for (int r = 0; r < FO_ITEMS; ++r) pos[r] += first;
+    return kept;
+}
+
+}  // namespace

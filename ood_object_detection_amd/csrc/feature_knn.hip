@@ -1,9 +1,9 @@
 // Nearest-neighbour feature OOD score on the device: a bank of in-distribution pyramid rows and the squared distance of
 // a query row to its k-th nearest bank row ("deep nearest neighbours", Sun et al. 2022), with the nearest row and its class.
 //
-//   append  the valid rows of a [B, K] call -> the bank at a device cursor, in (b, j) order: block counts -> bases and the counter
-//           update in one workgroup -> the bank row of every entry (the compaction of feature_ood.hip's fit; no atomic decides a
-//           position) -> the rows themselves, four lanes a row.  The valid
+//   append  the valid rows of a [B, K] call -> the bank at a device cursor, in (b, j) order: the ordered compaction of compact.h
+//           (its base launch also moves the counters) gives every entry its bank row, then the rows themselves, four lanes a row.
+//           The valid
 //           row with global ordinal g (counted since the last clear, across calls) is kept when g % sample_every == 0 and lands on
 //           row size0 + g / s - ceil(seen0 / s): the bank does not depend on how the rows are split into calls.
 //   score   launch 1, grid (64-row block, bank split): a wave holds its 16 normalised query rows as the B operand in registers
@@ -46,14 +46,12 @@ DEV float fk_inv_norm(float n2) { return 1.0f / sqrtf(fmaxf(n2, 1e-24f)); }
 // ---- append ------------------------------------------------------------------------------------------------------------------
 struct FkAppend {
     FoLevels L;
-    int F, Fp, C, A;                                            // C = 0: no classes
-    unsigned K, total;
-    const long long* anchor;
-    const void* classes; int cdt; long long cpitch, cstride, coff;
-    const void* count; int count64;
+    FoSel sel;
+    FoClasses cls;                                              // C = 0: no classes
+    int F, Fp, A;
     int normalize;
     long long every, cap;
-    float* bank; float* norms; int* cls;                        // [cap][Fp], [cap], [cap]
+    float* bank; float* norms; int* bcls;                       // [cap][Fp], [cap], [cap]
     long long* counters;                                        // size, seen, lost
     long long* header;                                          // workspace: seen and size before this call
     unsigned* counts; unsigned nblocks;
@@ -62,99 +60,44 @@ struct FkAppend {
 
 // is entry i = b * K + j a valid row?
 DEV bool fk_keep(const FkAppend& a, unsigned i, const char** row, int* cls) {
-    if (i >= a.total) return false;
-    const unsigned b = i / a.K, j = i - b * a.K;
-    if (a.count && (long long)j >= fo_count(a.count, a.count64, b)) return false;
-    long long cl = -1;
-    if (a.C > 0) {
-        const long long at = (long long)b * a.cpitch + (long long)j * a.cstride;
-        if (a.cdt == 0) cl = reinterpret_cast<const int*>(a.classes)[at];
-        else if (a.cdt == 1) cl = reinterpret_cast<const long long*>(a.classes)[at];
-        else {
-            const float v = reinterpret_cast<const float*>(a.classes)[at];
-            if (!(v >= -2147483648.f && v < 2147483648.f)) return false;        // NaN, infinities
-            cl = (long long)v;
-        }
-        if (cl < a.coff) return false;
-        cl -= a.coff;
-        if (cl >= a.C) return false;
-    }
-    const long long an = a.anchor ? a.anchor[i] : (long long)j;
-    if (an < 0 || an >= (long long)a.A * a.L.P) return false;
+    unsigned b; long long an;
+    if (!fo_select(a.sel, i, &b, &an)) return false;
+    int cl = -1;
+    if (a.cls.C > 0 && (cl = fo_class(a.cls, b, i - b * a.sel.K)) < 0) return false;
     *row = fo_row(a.L, b, (unsigned)(an / a.A));
-    *cls = (int)cl;
+    *cls = cl;
     return true;
-}
-
-__global__ __launch_bounds__(256) void fk_append_count_kernel(FkAppend a) {
-    __shared__ unsigned sh[FO_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned base = (unsigned)blockIdx.x * FO_TILE;
-    unsigned c = 0;
-    for (int r = 0; r < FO_ITEMS; ++r) {
-        const char* row; int cl;
-        c += fk_keep(a, base + r * FO_THREADS + tid, &row, &cl) ? 1u : 0u;
-    }
-    const unsigned tot = fo_block_sum<unsigned>(c, sh, tid);
-    if (tid == 0) a.counts[blockIdx.x] = tot;
 }
 
 DEV long long fk_ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 
-// one workgroup: counts -> first ordinals of the workgroups; the counters move on, their old values stay in the header
-__global__ __launch_bounds__(256) void fk_append_base_kernel(FkAppend a) {
-    __shared__ unsigned sh[FO_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned chunk = (a.nblocks + FO_THREADS - 1) / FO_THREADS;
-    const unsigned lo = fo_min((unsigned)tid * chunk, a.nblocks), hi = fo_min(lo + chunk, a.nblocks);
-    unsigned sum = 0;
-    for (unsigned k = lo; k < hi; ++k) sum += a.counts[k];
-    unsigned total;
-    unsigned run = fo_block_excl_scan(sum, sh, tid, &total);
-    for (unsigned k = lo; k < hi; ++k) { const unsigned c = a.counts[k]; a.counts[k] = run; run += c; }
-    if (tid == 0) {
-        const long long size0 = a.counters[0], seen0 = a.counters[1];
-        a.header[0] = seen0; a.header[1] = size0;
-        const long long kept = fk_ceil_div(seen0 + total, a.every) - fk_ceil_div(seen0, a.every);
-        const long long room = a.cap > size0 ? a.cap - size0 : 0;
-        const long long stored = kept < room ? kept : room;
-        a.counters[0] = size0 + stored;
-        a.counters[1] = seen0 + total;
-        a.counters[2] += kept - stored;
-    }
+DEV bool cp_keep(const FkAppend& a, unsigned i) { const char* row; int cl; return fk_keep(a, i, &row, &cl); }
+DEV unsigned cp_begin(const FkAppend&) { return 0u; }
+// the counters move on, their old values stay in the header
+DEV void cp_finish(const FkAppend& a, unsigned, unsigned total) {
+    const long long size0 = a.counters[0], seen0 = a.counters[1];
+    a.header[0] = seen0; a.header[1] = size0;
+    const long long kept = fk_ceil_div(seen0 + total, a.every) - fk_ceil_div(seen0, a.every);
+    const long long room = a.cap > size0 ? a.cap - size0 : 0;
+    const long long stored = kept < room ? kept : room;
+    a.counters[0] = size0 + stored;
+    a.counters[1] = seen0 + total;
+    a.counters[2] += kept - stored;
 }
 
-// wave w of a workgroup owns entries [w * 512, (w + 1) * 512) of its tile, 64 consecutive ones per round: ordinals follow (b, j).
-// slots[i] = the bank row of entry i, or -1 when it is not stored
+// positions are ordinals here: slots[i] = the bank row of entry i, or -1 when it is not stored
 __global__ __launch_bounds__(256) void fk_append_write_kernel(FkAppend a) {
-    __shared__ unsigned wsum[FO_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned base = (unsigned)blockIdx.x * FO_TILE + (unsigned)wave * (64 * FO_ITEMS);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned rank[FO_ITEMS];
-    unsigned keep = 0, wtot = 0;
-#pragma unroll
-    for (int r = 0; r < FO_ITEMS; ++r) {
-        const char* row; int cl;
-        const bool k = fk_keep(a, base + r * 64 + lane, &row, &cl);
-        const unsigned long long bal = __ballot(k);
-        rank[r] = wtot + fo_popc(bal & below);
-        wtot += fo_popc(bal);
-        keep |= (k ? 1u : 0u) << r;
-    }
-    if (lane == 0) wsum[wave] = wtot;
-    __syncthreads();
-    unsigned first = a.counts[blockIdx.x];
-    for (int w = 0; w < FO_THREADS / 64; ++w) first += w < wave ? wsum[w] : 0u;
+    unsigned pos[FO_ITEMS];
+    const unsigned kept = fo_positions(a.counts, pos, [&](int, unsigned i) { return cp_keep(a, i); });
     const long long seen0 = a.header[0], size0 = a.header[1];
     const long long kept0 = fk_ceil_div(seen0, a.every);        // kept rows before this call, had none been lost
 #pragma unroll
     for (int r = 0; r < FO_ITEMS; ++r) {
-        const unsigned i = base + r * 64 + lane;
-        if (i < a.total) {
+        const unsigned i = fo_entry(r);
+        if (i < a.sel.total) {
             long long slot = -1;
-            if (keep & (1u << r)) {
-                const long long g = seen0 + first + rank[r];
+            if (kept & (1u << r)) {
+                const long long g = seen0 + pos[r];
                 const long long q = g / a.every;
                 if (g - q * a.every == 0) slot = size0 + (q - kept0);
             }
@@ -167,7 +110,7 @@ __global__ __launch_bounds__(256) void fk_append_write_kernel(FkAppend a) {
 __global__ __launch_bounds__(256) void fk_append_rows_kernel(FkAppend a) {
     const int tid = threadIdx.x, lane = tid & 63, r16 = lane & 15, g = lane >> 4;
     const unsigned i = ((unsigned)blockIdx.x * 4 + (unsigned)(tid >> 6)) * 16 + (unsigned)r16;
-    const int slot = i < a.total ? a.slots[i] : -1;
+    const int slot = i < a.sel.total ? a.slots[i] : -1;
     if (!__ballot(slot >= 0)) return;                           // the same for the whole wave
     const char* row = nullptr;
     int cl = -1;
@@ -200,31 +143,20 @@ __global__ __launch_bounds__(256) void fk_append_rows_kernel(FkAppend a) {
         if (on) *reinterpret_cast<f32x4*>(dst + c + 4 * g) = v;
     }
     const float n2 = fk_tree4x4(pp);
-    if (on && g == 0) { a.norms[slot] = n2; a.cls[slot] = cl; }
+    if (on && g == 0) { a.norms[slot] = n2; a.bcls[slot] = cl; }
 }
 
 // ---- score -------------------------------------------------------------------------------------------------------------------
 struct FkScore {
     FoLevels L;
+    FoSel sel;
     int F, A;
-    unsigned K, total;
-    const long long* anchor; const void* count; int count64;
     int normalize, k, splits;
     unsigned M, steps_per_split;
     const float* bank; const float* norms; const int* cls;
     float* lists; float* bestd; int* besti;                     // workspace: [total][splits][4][k], [total][splits][4] twice
     float* knn; int* index; int* kcls;
 };
-
-// the feature row of query i, or null when it does not count
-DEV const char* fk_query_row(const FkScore& a, unsigned i) {
-    if (i >= a.total) return nullptr;
-    const unsigned b = i / a.K, j = i - b * a.K;
-    if (a.count && (long long)j >= fo_count(a.count, a.count64, b)) return nullptr;
-    const long long an = a.anchor ? a.anchor[i] : (long long)j;
-    if (an < 0 || an >= (long long)a.A * a.L.P) return nullptr;
-    return fo_row(a.L, b, (unsigned)(an / a.A));
-}
 
 template <int NT> struct FkGeom {
     static constexpr int FP = 16 * NT, PITCH = FP + 4;
@@ -247,7 +179,7 @@ __global__ __launch_bounds__(256) void fk_score_kernel(FkScore a) {
     Frag<float> fq[NT];
     float qn;
     {
-        const char* p = fk_query_row(a, qi);
+        const char* p = fo_sel_row(a.L, a.sel, a.A, qi);       // null: the query does not count
         float pp[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kc = 0; kc < NT; ++kc)
@@ -347,7 +279,7 @@ __global__ __launch_bounds__(256) void fk_score_kernel(FkScore a) {
         if (st + 1 < s1) stash(buf ^ 1);
         __syncthreads();
     }
-    if (qi < a.total) {
+    if (qi < a.sel.total) {
         const long long at = ((long long)qi * a.splits + blockIdx.y) * 4 + g;
 #pragma unroll
         for (int j = 0; j < KL; ++j)
@@ -367,9 +299,9 @@ DEV float fk_wave_min(float v) {
 __global__ __launch_bounds__(256) void fk_merge_kernel(FkScore a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned i = (unsigned)blockIdx.x * 4 + (unsigned)wave;
-    if (i >= a.total) return;                                   // the same for the whole wave
+    if (i >= a.sel.total) return;                               // the same for the whole wave
     const int nl = 4 * a.splits;
-    const bool valid = fk_query_row(a, i) != nullptr;
+    const bool valid = fo_sel_row(a.L, a.sel, a.A, i) != nullptr;
     const float* mine = a.lists + (long long)i * nl * a.k;
     float cur[4];
     int ptr[4];
@@ -423,14 +355,9 @@ __global__ __launch_bounds__(256) void fk_merge_kernel(FkScore a) {
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 int fk_step_rows(int F) {
-    switch ((F + 15) / 16) {
-        case 4: return FkGeom<4>::TR;
-        case 6: return FkGeom<6>::TR;
-        case 7: return FkGeom<7>::TR;
-        case 10: return FkGeom<10>::TR;
-        case 14: return FkGeom<14>::TR;
-        default: return FkGeom<18>::TR;
-    }
+    int tr = 0;
+    fo_for_width(F, [&](auto nt) { tr = FkGeom<decltype(nt)::value>::TR; });
+    return tr;
 }
 
 // The split count the library chooses (steps = 0: the bank is not known yet, the most it may choose): one resident set of workgroups,
@@ -468,7 +395,7 @@ bool fk_layout(long long rows, int F, int k, int splits, FkLayout* L) {
 }
 
 template <int NT, int KL> void fk_score_launch(hipStream_t st, const FkScore& a) {
-    hipLaunchKernelGGL((fk_score_kernel<NT, KL>), dim3((a.total + FK_QROWS - 1) / FK_QROWS, a.splits), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((fk_score_kernel<NT, KL>), dim3((a.sel.total + FK_QROWS - 1) / FK_QROWS, a.splits), dim3(256), 0, st, a);
 }
 template <int NT> void fk_score_launch_k(hipStream_t st, const FkScore& a) {
     if (a.k == 1) fk_score_launch<NT, 1>(st, a);
@@ -493,31 +420,27 @@ extern "C" int effdet_feature_knn_append(void* stream, int dtype, int num_levels
                                          int* bank_classes, long long* counters, void* workspace, long long workspace_bytes) {
     FkAppend a;
     FkLayout lay;
-    if (!fo_width_ok(F) || C < 0 || A < 1 || B < 1 || K < 1 || (long long)B * K > FO_MAX_ROWS) return EFFDET_EINVAL;
-    if (sample_every < 1 || capacity < 1 || capacity > FK_MAX_CAPACITY) return EFFDET_EINVAL;
-    if (!fo_levels(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, B, &a.L))
+    if (C < 0 || sample_every < 1 || capacity < 1 || capacity > FK_MAX_CAPACITY) return EFFDET_EINVAL;
+    if (!fo_feature_rows(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, F, A, B,
+                         K, anchor_index, count, count_is_int64, &a.L, &a.sel))
         return EFFDET_EINVAL;
-    if (C > 0 && (!classes || class_dtype < 0 || class_dtype > 2 || class_pitch < 0 || class_stride < 0)) return EFFDET_EINVAL;
+    if (!fo_classes(classes, class_dtype, class_pitch, class_stride, class_offset, C, &a.cls) && C > 0) return EFFDET_EINVAL;
     if (!bank || !norms || !bank_classes || !counters || !workspace) return EFFDET_EINVAL;
     if (!fk_layout((long long)B * K, F, 0, 0, &lay) || workspace_bytes < lay.total) return EFFDET_EINVAL;
     EFFDET_ENTER();                                              // (the refusals above are pure host code)
     char* ws = reinterpret_cast<char*>(workspace);
-    a.F = F; a.Fp = (F + 15) & ~15; a.C = C; a.A = A;
-    a.K = (unsigned)K; a.total = (unsigned)((long long)B * K);
-    a.anchor = anchor_index;
-    a.classes = classes; a.cdt = class_dtype; a.cpitch = class_pitch; a.cstride = class_stride; a.coff = class_offset;
-    a.count = count; a.count64 = count_is_int64 ? 1 : 0;
+    a.F = F; a.Fp = (F + 15) & ~15; a.A = A;
     a.normalize = normalize ? 1 : 0; a.every = sample_every; a.cap = capacity;
-    a.bank = bank; a.norms = norms; a.cls = bank_classes; a.counters = counters;
+    a.bank = bank; a.norms = norms; a.bcls = bank_classes; a.counters = counters;
     a.header = reinterpret_cast<long long*>(ws + lay.header);
     a.counts = reinterpret_cast<unsigned*>(ws + lay.counts);
     a.slots = reinterpret_cast<int*>(ws + lay.slots);
-    a.nblocks = (a.total + FO_TILE - 1) / FO_TILE;
+    a.nblocks = (a.sel.total + FO_TILE - 1) / FO_TILE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(fk_append_count_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
-    hipLaunchKernelGGL(fk_append_base_kernel, dim3(1), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_count_kernel<FkAppend>, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_base_kernel<FkAppend>, dim3(1), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(fk_append_write_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
-    hipLaunchKernelGGL(fk_append_rows_kernel, dim3((a.total + 63) / 64), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(fk_append_rows_kernel, dim3((a.sel.total + 63) / 64), dim3(256), 0, st, a);
     return effdet_check_launch();
 }
 
@@ -529,9 +452,9 @@ extern "C" int effdet_feature_knn_score(void* stream, int dtype, int num_levels,
                                         float* knn, int* knn_index, int* knn_class, void* workspace, long long workspace_bytes) {
     FkScore a;
     FkLayout lay;
-    if (!fo_width_ok(F) || A < 1 || B < 1 || K < 1 || (long long)B * K > FO_MAX_ROWS) return EFFDET_EINVAL;
     if (k < 1 || k > FK_MAX_K || splits < 0 || splits > FK_MAX_SPLITS || M < 1 || M > FK_MAX_CAPACITY) return EFFDET_EINVAL;
-    if (!fo_levels(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, B, &a.L))
+    if (!fo_feature_rows(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, F, A, B,
+                         K, anchor_index, count, count_is_int64, &a.L, &a.sel))
         return EFFDET_EINVAL;
     if (!bank || !norms || !bank_classes || !knn || !knn_index || !knn_class || !workspace) return EFFDET_EINVAL;
     const long long rows = (long long)B * K, steps = (M + fk_step_rows(F) - 1) / fk_step_rows(F);
@@ -540,8 +463,6 @@ extern "C" int effdet_feature_knn_score(void* stream, int dtype, int num_levels,
     EFFDET_ENTER();
     char* ws = reinterpret_cast<char*>(workspace);
     a.F = F; a.A = A;
-    a.K = (unsigned)K; a.total = (unsigned)rows;
-    a.anchor = anchor_index; a.count = count; a.count64 = count_is_int64 ? 1 : 0;
     a.normalize = normalize ? 1 : 0; a.k = k; a.splits = splits;
     a.M = (unsigned)M; a.steps_per_split = (unsigned)((steps + splits - 1) / splits);
     a.bank = bank; a.norms = norms; a.cls = bank_classes;
@@ -550,14 +471,7 @@ extern "C" int effdet_feature_knn_score(void* stream, int dtype, int num_levels,
     a.besti = reinterpret_cast<int*>(ws + lay.besti);
     a.knn = knn; a.index = knn_index; a.kcls = knn_class;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch ((F + 15) / 16) {
-        case 4: fk_score_launch_k<4>(st, a); break;
-        case 6: fk_score_launch_k<6>(st, a); break;
-        case 7: fk_score_launch_k<7>(st, a); break;
-        case 10: fk_score_launch_k<10>(st, a); break;
-        case 14: fk_score_launch_k<14>(st, a); break;
-        default: fk_score_launch_k<18>(st, a); break;
-    }
-    hipLaunchKernelGGL(fk_merge_kernel, dim3((a.total + 3) / 4), dim3(256), 0, st, a);
+    fo_for_width(F, [&](auto nt) { fk_score_launch_k<decltype(nt)::value>(st, a); });
+    hipLaunchKernelGGL(fk_merge_kernel, dim3((a.sel.total + 3) / 4), dim3(256), 0, st, a);
     return effdet_check_launch();
 }

@@ -2,18 +2,17 @@
 // "relative" form over rows of the BiFPN pyramid.
 //
 //   fit     a batch's rows -> the running float64 statistics n_c (int64), s_c = sum f, S = sum f f^T:
-//           compaction of the valid rows in (b, j) order (block counts -> bases in one workgroup -> writes, the pattern of
-//           ood_eval.hip's append; no atomic decides a position), then S as per-workgroup partials over fixed row chunks that one
-//           launch adds in a fixed order to the running matrix, then s_c / n_c by one workgroup per class that walks the compacted
-//           rows in order.  Products of float32 values are exact in float64; only the order of the additions is a choice, and it
+//           compaction of the valid rows in (b, j) order (compact.h), then S as per-workgroup partials over fixed row chunks
+//           that one launch adds in a fixed order to the running matrix, then s_c / n_c by one workgroup per class that walks
+//           the compacted rows in order.  Products of float32 values are exact in float64; only the order of the additions is a choice, and it
 //           depends on nothing but the number of valid rows.
 //   score   64 (48 at F = 288) rows per workgroup, 16 per wave: xc = f - mu_0 staged in LDS, z0 = W_0 xc and z = W xc on the
 //           float32-input MFMA (16x16x4) with the factors read through L2 in K-chunks of 16, z written back over the wave's own
 //           LDS rows as the A operand of the F x C product with the whitened class means.
 //
-// Features are addressed through a level table (<= 8 entries: base, cells, batch stride, cell stride; channel stride 1).  Every
-// row index is compared with the table before a pointer is formed, every store index with its extent before the store; no call
-// synchronises with the host or allocates, so all of them can be captured in a graph.
+// Row selection, class labels, the level table of the features and the staging of xc are feature_rows.h's.  Every row index is
+// compared with the table before a pointer is formed, every store index with its extent before the store; no call synchronises
+// with the host or allocates, so all of them can be captured in a graph.
 #include "common.h"
 #include "feature_rows.h"
 
@@ -30,11 +29,9 @@ struct FoRec { unsigned rowcell; int cls; };                    // b * P + cell,
 
 struct FoFit {
     FoLevels L;
-    int F, C, A;
-    unsigned K, total;                                          // total = B * K
-    const long long* anchor;                                    // [B, K] or null (row j is anchor j)
-    const void* classes; int cdt; long long cpitch, cstride, coff;
-    const void* count; int count64;
+    FoSel sel;
+    FoClasses cls;
+    int F, A;
     unsigned* counts; unsigned nblocks;                         // kept entries per compaction workgroup, then bases
     unsigned* header;                                           // [0] = number of valid rows of this call
     FoRec* list; unsigned cap;
@@ -44,84 +41,28 @@ struct FoFit {
 
 // is entry i = b * K + j a valid row?
 DEV bool fo_keep(const FoFit& a, unsigned i, FoRec* rec) {
-    if (i >= a.total) return false;
-    const unsigned b = i / a.K, j = i - b * a.K;
-    if (a.count && (long long)j >= fo_count(a.count, a.count64, b)) return false;
-    const long long at = (long long)b * a.cpitch + (long long)j * a.cstride;
-    long long cl;
-    if (a.cdt == 0) cl = reinterpret_cast<const int*>(a.classes)[at];
-    else if (a.cdt == 1) cl = reinterpret_cast<const long long*>(a.classes)[at];
-    else {
-        const float v = reinterpret_cast<const float*>(a.classes)[at];
-        if (!(v >= -2147483648.f && v < 2147483648.f)) return false;        // NaN, infinities
-        cl = (long long)v;
-    }
-    if (cl < a.coff) return false;
-    cl -= a.coff;
-    if (cl >= a.C) return false;
-    const long long an = a.anchor ? a.anchor[i] : (long long)j;
-    if (an < 0 || an >= (long long)a.A * a.L.P) return false;
+    unsigned b; long long an;
+    if (!fo_select(a.sel, i, &b, &an)) return false;
+    const int cl = fo_class(a.cls, b, i - b * a.sel.K);
+    if (cl < 0) return false;
     rec->rowcell = b * a.L.P + (unsigned)(an / a.A);
-    rec->cls = (int)cl;
+    rec->cls = cl;
     return true;
 }
+DEV bool cp_keep(const FoFit& a, unsigned i) { FoRec rec; return fo_keep(a, i, &rec); }
+DEV unsigned cp_begin(const FoFit&) { return 0u; }
+DEV void cp_finish(const FoFit& a, unsigned, unsigned total) { a.header[0] = fo_min(total, a.cap); }
 
-__global__ __launch_bounds__(256) void fo_fit_count_kernel(FoFit a) {
-    __shared__ unsigned sh[FO_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned base = (unsigned)blockIdx.x * FO_TILE;
-    unsigned c = 0;
-    for (int r = 0; r < FO_ITEMS; ++r) {
-        FoRec rec;
-        c += fo_keep(a, base + r * FO_THREADS + tid, &rec) ? 1u : 0u;
-    }
-    const unsigned tot = fo_block_sum<unsigned>(c, sh, tid);
-    if (tid == 0) a.counts[blockIdx.x] = tot;
-}
-
-// one workgroup: counts -> first positions of the workgroups; header[0] = valid rows
-__global__ __launch_bounds__(256) void fo_fit_base_kernel(FoFit a) {
-    __shared__ unsigned sh[FO_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned chunk = (a.nblocks + FO_THREADS - 1) / FO_THREADS;
-    const unsigned lo = fo_min((unsigned)tid * chunk, a.nblocks), hi = fo_min(lo + chunk, a.nblocks);
-    unsigned sum = 0;
-    for (unsigned k = lo; k < hi; ++k) sum += a.counts[k];
-    unsigned total;
-    unsigned run = fo_block_excl_scan(sum, sh, tid, &total);
-    for (unsigned k = lo; k < hi; ++k) { const unsigned c = a.counts[k]; a.counts[k] = run; run += c; }
-    if (tid == 0) a.header[0] = fo_min(total, a.cap);
-}
-
-// wave w of a workgroup owns entries [w * 512, (w + 1) * 512) of its tile, 64 consecutive ones per round: positions follow (b, j)
 __global__ __launch_bounds__(256) void fo_fit_write_kernel(FoFit a) {
-    __shared__ unsigned wsum[FO_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned base = (unsigned)blockIdx.x * FO_TILE + (unsigned)wave * (64 * FO_ITEMS);
-    const unsigned long long below = (1ull << lane) - 1ull;
     FoRec rec[FO_ITEMS];
-    unsigned rank[FO_ITEMS];
-    unsigned keep = 0, wtot = 0;
-#pragma unroll
-    for (int r = 0; r < FO_ITEMS; ++r) {
+    unsigned pos[FO_ITEMS];
+    const unsigned kept = fo_positions(a.counts, pos, [&](int r, unsigned i) {
         rec[r].rowcell = 0; rec[r].cls = 0;
-        const bool k = fo_keep(a, base + r * 64 + lane, &rec[r]);
-        const unsigned long long bal = __ballot(k);
-        rank[r] = wtot + fo_popc(bal & below);
-        wtot += fo_popc(bal);
-        keep |= (k ? 1u : 0u) << r;
-    }
-    if (lane == 0) wsum[wave] = wtot;
-    __syncthreads();
-    unsigned first = a.counts[blockIdx.x];
-    for (int w = 0; w < FO_THREADS / 64; ++w) first += w < wave ? wsum[w] : 0u;
+        return fo_keep(a, i, &rec[r]);
+    });
 #pragma unroll
-    for (int r = 0; r < FO_ITEMS; ++r) {
-        if (keep & (1u << r)) {
-            const unsigned p = first + rank[r];
-            if (p < a.cap) a.list[p] = rec[r];
-        }
-    }
+    for (int r = 0; r < FO_ITEMS; ++r)
+        if ((kept & (1u << r)) && pos[r] < a.cap) a.list[pos[r]] = rec[r];
 }
 
 // blockIdx.x = S tile (ti, tj), blockIdx.y = row chunk: partial[chunk][i][j] = sum over the chunk's rows of f_i f_j, rows in order
@@ -217,22 +158,15 @@ __global__ __launch_bounds__(256) void fo_fit_class_kernel(FoFit a) {
 // ---- score -------------------------------------------------------------------------------------------------------------------
 struct FoScore {
     FoLevels L;
-    int F, C, Cp, A;                                            // Cp: C rounded up to 32
-    unsigned K, total;
-    const long long* anchor; const void* count; int count64;
+    FoSel sel;
+    int F, Cp, A;                                               // Cp: C rounded up to 32
     const float *W, *W0, *M, *m2, *mu0;                         // [Fp][Fp], [Fp][Fp], [Cp][Fp], [Cp], [Fp]; Fp = F rounded up to 16
     float* maha; float* rel; int* nearest;
 };
 
-template <int NT> struct FoGeom {
-    static constexpr int FP = 16 * NT, PITCH = FP + 4;
-    static constexpr int WAVES = 64 * PITCH * 4 <= 65536 ? 4 : 3;         // LDS of a workgroup stays within 64 KB at every width
-    static constexpr int ROWS = 16 * WAVES;
-};
-
 // acc[t] = the wave's 16 rows (xs, LDS) times rows [16 t, 16 t + 16) of Wm ([.][FP] in global memory), K = FP
 template <int NT> DEV void fo_gemm(const float* xs, const float* Wm, int lane, f32x4 (&acc)[NT]) {
-    constexpr int FP = FoGeom<NT>::FP, PITCH = FoGeom<NT>::PITCH;
+    constexpr int FP = FoRowGeom<NT>::FP, PITCH = FoRowGeom<NT>::PITCH;
     const int r16 = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -262,26 +196,13 @@ template <int NT> DEV void fo_row_sumsq(const f32x4 (&acc)[NT], float (&s)[4]) {
 }
 
 template <int NT>
-__global__ __launch_bounds__(FoGeom<NT>::WAVES * 64) void fo_score_kernel(FoScore a) {
-    constexpr int FP = FoGeom<NT>::FP, PITCH = FoGeom<NT>::PITCH, WAVES = FoGeom<NT>::WAVES;
+__global__ __launch_bounds__(FoRowGeom<NT>::WAVES * 64) void fo_score_kernel(FoScore a) {
+    constexpr int FP = FoRowGeom<NT>::FP, PITCH = FoRowGeom<NT>::PITCH, WAVES = FoRowGeom<NT>::WAVES;
     __shared__ __attribute__((aligned(16))) float sh[16 * WAVES * PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g = lane >> 4;
     const unsigned row0 = (unsigned)blockIdx.x * (16 * WAVES) + (unsigned)wave * 16;
     float* xs = sh + wave * 16 * PITCH;
-    unsigned valid = 0;
-    for (int rr = 0; rr < 16; ++rr) {
-        const unsigned i = row0 + rr;                           // the same for the whole wave
-        const char* p = nullptr;
-        if (i < a.total) {
-            const unsigned b = i / a.K, j = i - b * a.K;
-            if (!a.count || (long long)j < fo_count(a.count, a.count64, b)) {
-                const long long an = a.anchor ? a.anchor[i] : (long long)j;
-                if (an >= 0 && an < (long long)a.A * a.L.P) p = fo_row(a.L, b, (unsigned)(an / a.A));
-            }
-        }
-        if (p) valid |= 1u << rr;
-        for (int k = lane; k < FP; k += 64) xs[rr * PITCH + k] = (p && k < a.F) ? fo_ld(p, k, a.L.bf16) - a.mu0[k] : 0.f;
-    }
+    const unsigned valid = fo_stage_centered<NT>(a.L, a.sel, a.A, a.F, a.mu0, row0, xs, lane);
     __syncthreads();
     f32x4 acc[NT];
     float d0[4], q[4];
@@ -330,7 +251,7 @@ __global__ __launch_bounds__(FoGeom<NT>::WAVES * 64) void fo_score_kernel(FoScor
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const unsigned i = row0 + 4 * g + r;
-            if (i < a.total) {
+            if (i < a.sel.total) {
                 const bool v = (valid >> (4 * g + r)) & 1u;
                 a.maha[i] = v ? -best[r] : 0.f;
                 a.rel[i] = v ? -(best[r] - d0[r]) : 0.f;
@@ -355,11 +276,6 @@ bool fo_layout(long long rows, int F, FoLayout* L) {
     return true;
 }
 
-template <int NT> void fo_score_launch(hipStream_t st, const FoScore& a) {
-    constexpr int ROWS = FoGeom<NT>::ROWS;
-    hipLaunchKernelGGL(fo_score_kernel<NT>, dim3((a.total + ROWS - 1) / ROWS), dim3(FoGeom<NT>::WAVES * 64), 0, st, a);
-}
-
 }  // namespace
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------
@@ -376,29 +292,25 @@ extern "C" int effdet_feature_ood_fit(void* stream, int dtype, int num_levels, c
                                       long long* n_c, double* s_c, double* S, void* workspace, long long workspace_bytes) {
     FoFit a;
     FoLayout lay;
-    if (!fo_width_ok(F) || C < 1 || C > FO_MAX_CLASSES || A < 1 || B < 1 || K < 1 || (long long)B * K > FO_MAX_ROWS) return EFFDET_EINVAL;
-    if (!fo_levels(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, B, &a.L))
-        return EFFDET_EINVAL;
-    if (!classes || class_dtype < 0 || class_dtype > 2 || class_pitch < 0 || class_stride < 0 || !n_c || !s_c || !S || !workspace)
+    if (C < 1 || C > FO_MAX_CLASSES || !n_c || !s_c || !S || !workspace) return EFFDET_EINVAL;
+    if (!fo_feature_rows(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, F, A, B,
+                         K, anchor_index, count, count_is_int64, &a.L, &a.sel) ||
+        !fo_classes(classes, class_dtype, class_pitch, class_stride, class_offset, C, &a.cls))
         return EFFDET_EINVAL;
     if (!fo_layout((long long)B * K, F, &lay) || workspace_bytes < lay.total) return EFFDET_EINVAL;
     EFFDET_ENTER();                                              // (the refusals above are pure host code)
     char* ws = reinterpret_cast<char*>(workspace);
-    a.F = F; a.C = C; a.A = A;
-    a.K = (unsigned)K; a.total = (unsigned)((long long)B * K);
-    a.anchor = anchor_index;
-    a.classes = classes; a.cdt = class_dtype; a.cpitch = class_pitch; a.cstride = class_stride; a.coff = class_offset;
-    a.count = count; a.count64 = count_is_int64 ? 1 : 0;
+    a.F = F; a.A = A;
     a.header = reinterpret_cast<unsigned*>(ws + lay.header);
     a.counts = reinterpret_cast<unsigned*>(ws + lay.counts);
-    a.nblocks = (a.total + FO_TILE - 1) / FO_TILE;
-    a.list = reinterpret_cast<FoRec*>(ws + lay.list); a.cap = a.total;
+    a.nblocks = (a.sel.total + FO_TILE - 1) / FO_TILE;
+    a.list = reinterpret_cast<FoRec*>(ws + lay.list); a.cap = a.sel.total;
     a.partial = reinterpret_cast<double*>(ws + lay.partial);
     a.n_c = n_c; a.s_c = s_c; a.S = S;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int T = (F + FO_ST - 1) / FO_ST;
-    hipLaunchKernelGGL(fo_fit_count_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
-    hipLaunchKernelGGL(fo_fit_base_kernel, dim3(1), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_count_kernel<FoFit>, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_base_kernel<FoFit>, dim3(1), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(fo_fit_write_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(fo_fit_scatter_kernel, dim3(T * T, FO_CHUNKS), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(fo_fit_reduce_kernel, dim3((F * F + FO_THREADS - 1) / FO_THREADS), dim3(FO_THREADS), 0, st, a);
@@ -413,24 +325,19 @@ extern "C" int effdet_feature_ood_score(void* stream, int dtype, int num_levels,
                                         const float* W0, const float* M, const float* m2, const float* mu0, float* mahalanobis,
                                         float* relative, int* nearest) {
     FoScore a;
-    if (!fo_width_ok(F) || C < 1 || C > FO_MAX_CLASSES || A < 1 || B < 1 || K < 1 || (long long)B * K > FO_MAX_ROWS) return EFFDET_EINVAL;
-    if (!fo_levels(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, B, &a.L))
+    if (C < 1 || C > FO_MAX_CLASSES ||
+        !fo_feature_rows(dtype, num_levels, level_bases, level_cells, level_batch_strides, level_cell_strides, level_channel_strides, F, A, B,
+                         K, anchor_index, count, count_is_int64, &a.L, &a.sel))
         return EFFDET_EINVAL;
     if (!W || !W0 || !M || !m2 || !mu0 || !mahalanobis || !relative || !nearest) return EFFDET_EINVAL;
     EFFDET_ENTER();
-    a.F = F; a.C = C; a.Cp = (C + 31) & ~31; a.A = A;
-    a.K = (unsigned)K; a.total = (unsigned)((long long)B * K);
-    a.anchor = anchor_index; a.count = count; a.count64 = count_is_int64 ? 1 : 0;
+    a.F = F; a.Cp = (C + 31) & ~31; a.A = A;
     a.W = W; a.W0 = W0; a.M = M; a.m2 = m2; a.mu0 = mu0;
     a.maha = mahalanobis; a.rel = relative; a.nearest = nearest;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch ((F + 15) / 16) {
-        case 4: fo_score_launch<4>(st, a); break;
-        case 6: fo_score_launch<6>(st, a); break;
-        case 7: fo_score_launch<7>(st, a); break;
-        case 10: fo_score_launch<10>(st, a); break;
-        case 14: fo_score_launch<14>(st, a); break;
-        default: fo_score_launch<18>(st, a); break;
-    }
+    fo_for_width(F, [&](auto nt) {
+        using G = FoRowGeom<decltype(nt)::value>;
+        hipLaunchKernelGGL(fo_score_kernel<decltype(nt)::value>, dim3((a.sel.total + G::ROWS - 1) / G::ROWS), dim3(G::WAVES * 64), 0, st, a);
+    });
     return effdet_check_launch();
 }

@@ -1,16 +1,16 @@
-// Row addressing of the feature-space OOD units (feature_ood.hip, feature_knn.hip): rows are F-vectors of pyramid cells, read through
-// a level table (<= 8 entries: base, cells, batch stride, cell stride; channel stride 1), float32 or bfloat16; and the workgroup
-// reductions of their valid-row compaction (counts -> bases -> writes, 2048 [B, K] entries per workgroup of 256 threads).
+// What the OOD units that read rows of a [B, K] call share (feature_ood.hip, feature_knn.hip, feature_subspace.hip, logit_ood.hip;
+// DESIGN.md §8): which entries count (FoSel), the class label of an entry (FoClasses), the feature rows - F-vectors of pyramid cells
+// read through a level table (<= 8 entries: base, cells, batch stride, cell stride; channel stride 1), float32 or bfloat16 -, the
+// geometry and staging of the kernels that keep 16 centred rows per wave in LDS, the dispatch on the width, and the host checks of
+// these arguments.  The reductions and the ordered compaction are compact.h's.
 #pragma once
+#include <type_traits>
 #include "common.h"
+#include "compact.h"
 
 namespace {
 
-constexpr int FO_THREADS = 256;
-constexpr int FO_ITEMS = 8;
-constexpr int FO_TILE = FO_THREADS * FO_ITEMS;                  // [B, K] entries of one compaction workgroup
 constexpr long long FO_MAX_ROWS = 1ll << 27;                    // B * K of one call
-constexpr long long FO_MAX_BLOCKS = FO_MAX_ROWS / FO_TILE;
 constexpr int FO_MAX_LEVELS = 8;
 
 struct FoLevels {
@@ -35,41 +35,84 @@ DEV float fo_ld(const char* row, int k, int bf16) {
     return reinterpret_cast<const float*>(row)[k];
 }
 
-DEV unsigned fo_min(unsigned a, unsigned b) { return a < b ? a : b; }
-DEV unsigned fo_popc(unsigned long long m) { return (unsigned)__builtin_popcountll(m); }
-
-template <typename T> DEV T fo_block_sum(T v, T* sh, int tid) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int s = FO_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
-        __syncthreads();
+// Which entries of a [B, K] call count: entry i = b * K + j does when j < count[b] (null: all) and its anchor - anchor[i], or j
+// without an index - lies in [0, limit): limit = A * P for feature rows (the anchor sits on cell anchor / A), N for logits.
+struct FoSel {
+    unsigned K, total;                                          // total = B * K
+    const long long* anchor;                                    // [B, K] or null (row j is anchor j)
+    const void* count; int count64;
+    long long limit;
+};
+// does entry i count?  *b: its image, *an: its anchor; every index is compared before a pointer is formed
+DEV bool fo_select(const FoSel& s, unsigned i, unsigned* b, long long* an) {
+    if (i >= s.total) return false;
+    const unsigned bb = i / s.K, j = i - bb * s.K;
+    if (s.count) {
+        const long long c = s.count64 ? reinterpret_cast<const long long*>(s.count)[bb] : (long long)reinterpret_cast<const int*>(s.count)[bb];
+        if ((long long)j >= c) return false;
     }
-    const T r = sh[0];
-    __syncthreads();
-    return r;
+    const long long a = s.anchor ? s.anchor[i] : (long long)j;
+    if (a < 0 || a >= s.limit) return false;
+    *b = bb; *an = a;
+    return true;
 }
-DEV unsigned fo_block_excl_scan(unsigned v, unsigned* sh, int tid, unsigned* total) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < FO_THREADS; off <<= 1) {
-        const unsigned t = tid >= off ? sh[tid - off] : 0u;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const unsigned incl = sh[tid];
-    *total = sh[FO_THREADS - 1];
-    __syncthreads();
-    return incl - v;
+// the feature row of entry i with A anchors a cell, or null when the entry does not count
+DEV const char* fo_sel_row(const FoLevels& L, const FoSel& s, int A, unsigned i) {
+    unsigned b; long long an;
+    if (!fo_select(s, i, &b, &an)) return nullptr;
+    return fo_row(L, b, (unsigned)(an / A));
 }
 
-DEV long long fo_count(const void* count, int is64, unsigned b) {
-    return is64 ? reinterpret_cast<const long long*>(count)[b] : (long long)reinterpret_cast<const int*>(count)[b];
+// class labels [B, K] (int32, int64 or float32: dtype 0, 1, 2; strided)
+struct FoClasses { const void* ptr; int dtype; long long pitch, stride, offset; int C; };
+// the label of entry (b, j) less the offset, or -1 when that lies outside [0, C) (ignore labels, NaN, infinities)
+DEV int fo_class(const FoClasses& c, unsigned b, unsigned j) {
+    const long long at = (long long)b * c.pitch + (long long)j * c.stride;
+    long long cl;
+    if (c.dtype == 0) cl = reinterpret_cast<const int*>(c.ptr)[at];
+    else if (c.dtype == 1) cl = reinterpret_cast<const long long*>(c.ptr)[at];
+    else {
+        const float v = reinterpret_cast<const float*>(c.ptr)[at];
+        if (!(v >= -2147483648.f && v < 2147483648.f)) return -1;           // NaN, infinities
+        cl = (long long)v;
+    }
+    return (cl < c.offset || cl - c.offset >= c.C) ? -1 : (int)(cl - c.offset);
+}
+
+// 64 (48 at F = 288) rows per workgroup, 16 per wave, each wave's rows in its own LDS at pitch FP + 4
+template <int NT> struct FoRowGeom {
+    static constexpr int FP = 16 * NT, PITCH = FP + 4;
+    static constexpr int WAVES = 64 * PITCH * 4 <= 65536 ? 4 : 3;         // LDS of a workgroup stays within 64 KB at every width
+    static constexpr int ROWS = 16 * WAVES;
+};
+// xc = f - mu0 of the wave's 16 entries row0 .. row0 + 15 -> xs (its own LDS rows; zero beyond F and in rows that do not count);
+// bit rr of the result: entry row0 + rr counts
+template <int NT> DEV unsigned fo_stage_centered(const FoLevels& L, const FoSel& s, int A, int F, const float* mu0, unsigned row0,
+                                                 float* xs, int lane) {
+    constexpr int FP = FoRowGeom<NT>::FP, PITCH = FoRowGeom<NT>::PITCH;
+    unsigned valid = 0;
+    for (int rr = 0; rr < 16; ++rr) {
+        const char* p = fo_sel_row(L, s, A, row0 + rr);         // the same for the whole wave
+        if (p) valid |= 1u << rr;
+        for (int k = lane; k < FP; k += 64) xs[rr * PITCH + k] = (p && k < F) ? fo_ld(p, k, L.bf16) - mu0[k] : 0.f;
+    }
+    return valid;
 }
 
 // ---- host ----
 bool fo_width_ok(int F) { return F == 64 || F == 88 || F == 112 || F == 160 || F == 224 || F == 288; }
+
+// fn(std::integral_constant<int, NT>{}) for the NT = F / 16 (rounded up) of a supported width
+template <typename Fn> void fo_for_width(int F, Fn fn) {
+    switch ((F + 15) / 16) {
+        case 4: fn(std::integral_constant<int, 4>{}); break;
+        case 6: fn(std::integral_constant<int, 6>{}); break;
+        case 7: fn(std::integral_constant<int, 7>{}); break;
+        case 10: fn(std::integral_constant<int, 10>{}); break;
+        case 14: fn(std::integral_constant<int, 14>{}); break;
+        default: fn(std::integral_constant<int, 18>{}); break;
+    }
+}
 
 // the table of the ABI -> the kernels' copy; false: a bad table
 bool fo_levels(int dtype, int num_levels, const void* const* bases, const long long* cells, const long long* batch_strides,
@@ -88,6 +131,25 @@ bool fo_levels(int dtype, int num_levels, const void* const* bases, const long l
     for (int l = num_levels; l <= FO_MAX_LEVELS; ++l) L->start[l] = (unsigned)P;
     L->n = num_levels; L->bf16 = dtype == EFFDET_BF16; L->P = (unsigned)P;
     return true;
+}
+
+// the [B, K] arguments of the ABI -> the kernels' copy; false: refuse (limit < 1 covers A < 1 and N < 1)
+bool fo_sel(int B, long long K, const long long* anchor_index, const void* count, int count_is_int64, long long limit, FoSel* s) {
+    if (B < 1 || K < 1 || (long long)B * K > FO_MAX_ROWS || limit < 1) return false;
+    *s = FoSel{(unsigned)K, (unsigned)((long long)B * K), anchor_index, count, count_is_int64 ? 1 : 0, limit};
+    return true;
+}
+// the width, the level table and the rows of a feature unit's call
+bool fo_feature_rows(int dtype, int num_levels, const void* const* bases, const long long* cells, const long long* batch_strides,
+                     const long long* cell_strides, const long long* channel_strides, int F, int A, int B, long long K,
+                     const long long* anchor_index, const void* count, int count_is_int64, FoLevels* L, FoSel* s) {
+    return fo_width_ok(F) && A >= 1 && fo_levels(dtype, num_levels, bases, cells, batch_strides, cell_strides, channel_strides, B, L) &&
+           fo_sel(B, K, anchor_index, count, count_is_int64, (long long)A * L->P, s);
+}
+// the class arguments of the ABI -> the kernels' copy; false: refuse
+bool fo_classes(const void* classes, int dtype, long long pitch, long long stride, long long offset, int C, FoClasses* c) {
+    *c = FoClasses{classes, dtype, pitch, stride, offset, C};
+    return classes && dtype >= 0 && dtype <= 2 && pitch >= 0 && stride >= 0;
 }
 
 }  // namespace

@@ -6,9 +6,9 @@
 //                      r2 = sum_i y_i^2,  pm = sum_i inv_lambda_i * y_i^2,  r = sqrt(r2),  t = negate ? -logit_score : logit_score
 //                      residual = -r,  partial = -pm,  vim = t - alpha * r   (product, then difference: two roundings)
 //
-//   score      64 (48 at F = 288) rows per workgroup, 16 per wave (the geometry of feature_ood.hip's score kernel): xc staged in the
-//              wave's LDS rows at pitch Fp + 4, the product K-chunked by 16 with all Rp / 16 accumulator tiles live, Rt read as
-//              16-byte loads through L2.  With few residual directions a y_i stands alone in the sums, and the rounding of one
+//   score      64 (48 at F = 288) rows per workgroup, 16 per wave, xc staged in the wave's LDS rows at pitch Fp + 4 (the geometry and
+//              staging of feature_rows.h, shared with feature_ood.hip's score kernel), the product K-chunked by 16 with all
+//              Rp / 16 accumulator tiles live, Rt read as 16-byte loads through L2.  With few residual directions a y_i stands alone in the sums, and the rounding of one
 //              chain of Fp / 4 accumulations is all of the score's error; the accumulator registers that few tiles leave free then
 //              hold S = 4 (Rp / 16 <= NT / 4) or 2 (<= NT / 2) independent chains over the K-chunks kc = s mod S, added as
 //              (c0 + c1) + (c2 + c3) at the end - no more registers than S = 1 with all tiles, half the rounding error at S = 4.
@@ -29,9 +29,8 @@ namespace {
 
 struct FsArgs {
     FoLevels L;
+    FoSel sel;
     int F, A, RT;                                               // RT = Rp / 16 tiles of residual directions
-    unsigned K, total;                                          // total = B * K
-    const long long* anchor; const void* count; int count64;
     const float *Rt, *inv_lambda, *mu0;                         // [Rp][Fp], [Rp], [Fp]; zero in the padding
     const float* ls; long long ls_pitch, ls_stride; int negate; // the logit score [B, K] (strided) or null
     float alpha;
@@ -40,39 +39,14 @@ struct FsArgs {
     long long* counters; double* sums;                          // calibrate: the running n and {sum t, sum r}
 };
 
-template <int NT> struct FsGeom {
-    static constexpr int FP = 16 * NT, PITCH = FP + 4;
-    static constexpr int WAVES = 64 * PITCH * 4 <= 65536 ? 4 : 3;         // LDS of a workgroup stays within 64 KB at every width
-    static constexpr int ROWS = 16 * WAVES;
-};
 constexpr int FS_MIN_ROWS = 48;                                 // the fewest rows of a workgroup at any width
-
-// xc of the wave's 16 rows -> xs (its own LDS rows); bit rr of the result: row row0 + rr counts
-template <int NT> DEV unsigned fs_stage(const FsArgs& a, unsigned row0, float* xs, int lane) {
-    constexpr int FP = FsGeom<NT>::FP, PITCH = FsGeom<NT>::PITCH;
-    unsigned valid = 0;
-    for (int rr = 0; rr < 16; ++rr) {
-        const unsigned i = row0 + rr;                           // the same for the whole wave
-        const char* p = nullptr;
-        if (i < a.total) {
-            const unsigned b = i / a.K, j = i - b * a.K;
-            if (!a.count || (long long)j < fo_count(a.count, a.count64, b)) {
-                const long long an = a.anchor ? a.anchor[i] : (long long)j;
-                if (an >= 0 && an < (long long)a.A * a.L.P) p = fo_row(a.L, b, (unsigned)(an / a.A));
-            }
-        }
-        if (p) valid |= 1u << rr;
-        for (int k = lane; k < FP; k += 64) xs[rr * PITCH + k] = (p && k < a.F) ? fo_ld(p, k, a.L.bf16) - a.mu0[k] : 0.f;
-    }
-    return valid;
-}
 
 // K-chains of the product for RT tiles of residual directions at NT tiles of width: as many as the accumulators of NT tiles hold
 constexpr int fs_chains(int NT, int RT) { return 4 * RT <= NT ? 4 : (2 * RT <= NT ? 2 : 1); }
 
 // r[q], pm[q] of row 4 * (lane >> 4) + q of the wave's 16 staged rows, in every lane of the row; RT <= NT / S
 template <int NT, int S> DEV void fs_rows(const FsArgs& a, const float* xs, int lane, float (&r)[4], float (&pm)[4]) {
-    constexpr int FP = FsGeom<NT>::FP, PITCH = FsGeom<NT>::PITCH, TM = NT / S;
+    constexpr int FP = FoRowGeom<NT>::FP, PITCH = FoRowGeom<NT>::PITCH, TM = NT / S;
     const int r16 = lane & 15, g = lane >> 4;
     const int RT = a.RT;                                        // uniform: the tile tests below are scalar branches
     f32x4 ch[S][TM];
@@ -134,19 +108,19 @@ template <int NT, int S> DEV void fs_rows(const FsArgs& a, const float* xs, int 
 
 // the logit score of entry i after the sign rule
 DEV float fs_logit(const FsArgs& a, unsigned i) {
-    const unsigned b = i / a.K, j = i - b * a.K;
+    const unsigned b = i / a.sel.K, j = i - b * a.sel.K;
     const float v = a.ls[(long long)b * a.ls_pitch + (long long)j * a.ls_stride];
     return a.negate ? -v : v;
 }
 
 template <int NT, int S>
-__global__ __launch_bounds__(FsGeom<NT>::WAVES * 64) void fs_score_kernel(FsArgs a) {
-    constexpr int PITCH = FsGeom<NT>::PITCH, WAVES = FsGeom<NT>::WAVES;
+__global__ __launch_bounds__(FoRowGeom<NT>::WAVES * 64) void fs_score_kernel(FsArgs a) {
+    constexpr int PITCH = FoRowGeom<NT>::PITCH, WAVES = FoRowGeom<NT>::WAVES;
     __shared__ __attribute__((aligned(16))) float sh[16 * WAVES * PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g = lane >> 4;
     const unsigned row0 = (unsigned)blockIdx.x * (16 * WAVES) + (unsigned)wave * 16;
     float* xs = sh + wave * 16 * PITCH;
-    const unsigned valid = fs_stage<NT>(a, row0, xs, lane);
+    const unsigned valid = fo_stage_centered<NT>(a.L, a.sel, a.A, a.F, a.mu0, row0, xs, lane);
     __syncthreads();
     float r[4], pm[4];
     fs_rows<NT, S>(a, xs, lane, r, pm);
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(FsGeom<NT>::WAVES * 64) void fs_score_kernel(FsArgs
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const unsigned i = row0 + 4 * g + q;
-            if (i < a.total) {
+            if (i < a.sel.total) {
                 const bool v = (valid >> (4 * g + q)) & 1u;
                 a.residual[i] = v ? -r[q] : 0.f;
                 a.partial[i] = v ? -pm[q] : 0.f;
@@ -173,15 +147,15 @@ __global__ __launch_bounds__(FsGeom<NT>::WAVES * 64) void fs_score_kernel(FsArgs
 
 // part[workgroup] = {n, sum t, sum r} over the workgroup's valid rows in (b, j) order
 template <int NT, int S>
-__global__ __launch_bounds__(FsGeom<NT>::WAVES * 64) void fs_calib_kernel(FsArgs a) {
-    constexpr int PITCH = FsGeom<NT>::PITCH, WAVES = FsGeom<NT>::WAVES, ROWS = FsGeom<NT>::ROWS;
+__global__ __launch_bounds__(FoRowGeom<NT>::WAVES * 64) void fs_calib_kernel(FsArgs a) {
+    constexpr int PITCH = FoRowGeom<NT>::PITCH, WAVES = FoRowGeom<NT>::WAVES, ROWS = FoRowGeom<NT>::ROWS;
     __shared__ __attribute__((aligned(16))) float sh[16 * WAVES * PITCH];
     __shared__ float rt[ROWS], rr[ROWS];
     __shared__ unsigned rv[ROWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g = lane >> 4;
     const unsigned row0 = (unsigned)blockIdx.x * ROWS + (unsigned)wave * 16;
     float* xs = sh + wave * 16 * PITCH;
-    const unsigned valid = fs_stage<NT>(a, row0, xs, lane);
+    const unsigned valid = fo_stage_centered<NT>(a.L, a.sel, a.A, a.F, a.mu0, row0, xs, lane);
     __syncthreads();
     float r[4], pm[4];
     fs_rows<NT, S>(a, xs, lane, r, pm);
@@ -227,27 +201,21 @@ long long fs_workspace(long long rows) {
     return (((rows + FS_MIN_ROWS - 1) / FS_MIN_ROWS) * 24 + 255) & ~255ll;
 }
 
-template <int NT, int S> void fs_score_launch_s(hipStream_t st, const FsArgs& a) {
-    constexpr int ROWS = FsGeom<NT>::ROWS;
-    hipLaunchKernelGGL((fs_score_kernel<NT, S>), dim3((a.total + ROWS - 1) / ROWS), dim3(FsGeom<NT>::WAVES * 64), 0, st, a);
-}
 template <int NT> void fs_score_launch(hipStream_t st, const FsArgs& a) {
+    const dim3 grid((a.sel.total + FoRowGeom<NT>::ROWS - 1) / FoRowGeom<NT>::ROWS), block(FoRowGeom<NT>::WAVES * 64);
     switch (fs_chains(NT, a.RT)) {
-        case 4: fs_score_launch_s<NT, 4>(st, a); break;
-        case 2: fs_score_launch_s<NT, 2>(st, a); break;
-        default: fs_score_launch_s<NT, 1>(st, a); break;
+        case 4: hipLaunchKernelGGL((fs_score_kernel<NT, 4>), grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL((fs_score_kernel<NT, 2>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((fs_score_kernel<NT, 1>), grid, block, 0, st, a); break;
     }
 }
-template <int NT, int S> void fs_calib_launch_s(hipStream_t st, const FsArgs& a) {
-    hipLaunchKernelGGL((fs_calib_kernel<NT, S>), dim3(a.nblocks), dim3(FsGeom<NT>::WAVES * 64), 0, st, a);
-}
 template <int NT> void fs_calib_launch(hipStream_t st, FsArgs& a) {
-    constexpr int ROWS = FsGeom<NT>::ROWS;
-    a.nblocks = (a.total + ROWS - 1) / ROWS;
+    a.nblocks = (a.sel.total + FoRowGeom<NT>::ROWS - 1) / FoRowGeom<NT>::ROWS;
+    const dim3 grid(a.nblocks), block(FoRowGeom<NT>::WAVES * 64);
     switch (fs_chains(NT, a.RT)) {                              // the chains of the score: r agrees bit for bit
-        case 4: fs_calib_launch_s<NT, 4>(st, a); break;
-        case 2: fs_calib_launch_s<NT, 2>(st, a); break;
-        default: fs_calib_launch_s<NT, 1>(st, a); break;
+        case 4: hipLaunchKernelGGL((fs_calib_kernel<NT, 4>), grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL((fs_calib_kernel<NT, 2>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((fs_calib_kernel<NT, 1>), grid, block, 0, st, a); break;
     }
     hipLaunchKernelGGL(fs_calib_reduce_kernel, dim3(1), dim3(FO_THREADS), 0, st, a);
 }
@@ -257,13 +225,12 @@ bool fs_args(int dtype, int num_levels, const void* const* bases, const long lon
              const long long* cell_strides, const long long* channel_strides, int F, int A, int B, long long K,
              const long long* anchor_index, const void* count, int count_is_int64, const float* Rt, const float* mu0, int Rp,
              const float* logit_score, long long ls_pitch, long long ls_stride, int negate, FsArgs* a) {
-    if (!fo_width_ok(F) || A < 1 || B < 1 || K < 1 || (long long)B * K > FO_MAX_ROWS) return false;
-    if (!fo_levels(dtype, num_levels, bases, cells, batch_strides, cell_strides, channel_strides, B, &a->L)) return false;
+    if (!fo_feature_rows(dtype, num_levels, bases, cells, batch_strides, cell_strides, channel_strides, F, A, B, K, anchor_index, count,
+                         count_is_int64, &a->L, &a->sel))
+        return false;
     if (!Rt || !mu0 || Rp < 16 || Rp % 16 != 0 || Rp > (F + 15) / 16 * 16) return false;
     if (logit_score && (ls_pitch < 0 || ls_stride < 0)) return false;
     a->F = F; a->A = A; a->RT = Rp / 16;
-    a->K = (unsigned)K; a->total = (unsigned)((long long)B * K);
-    a->anchor = anchor_index; a->count = count; a->count64 = count_is_int64 ? 1 : 0;
     a->Rt = Rt; a->inv_lambda = nullptr; a->mu0 = mu0;
     a->ls = logit_score; a->ls_pitch = ls_pitch; a->ls_stride = ls_stride; a->negate = negate ? 1 : 0;
     a->alpha = 0.f;
@@ -293,14 +260,7 @@ extern "C" int effdet_feature_subspace_score(void* stream, int dtype, int num_le
     a.inv_lambda = inv_lambda; a.alpha = alpha;
     a.residual = residual; a.partial = partial; a.vim = vim;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch ((F + 15) / 16) {
-        case 4: fs_score_launch<4>(st, a); break;
-        case 6: fs_score_launch<6>(st, a); break;
-        case 7: fs_score_launch<7>(st, a); break;
-        case 10: fs_score_launch<10>(st, a); break;
-        case 14: fs_score_launch<14>(st, a); break;
-        default: fs_score_launch<18>(st, a); break;
-    }
+    fo_for_width(F, [&](auto nt) { fs_score_launch<decltype(nt)::value>(st, a); });
     return effdet_check_launch();
 }
 
@@ -319,13 +279,6 @@ extern "C" int effdet_feature_subspace_calibrate(void* stream, int dtype, int nu
     EFFDET_ENTER();
     a.part = reinterpret_cast<double*>(workspace); a.counters = counters; a.sums = sums;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch ((F + 15) / 16) {
-        case 4: fs_calib_launch<4>(st, a); break;
-        case 6: fs_calib_launch<6>(st, a); break;
-        case 7: fs_calib_launch<7>(st, a); break;
-        case 10: fs_calib_launch<10>(st, a); break;
-        case 14: fs_calib_launch<14>(st, a); break;
-        default: fs_calib_launch<18>(st, a); break;
-    }
+    fo_for_width(F, [&](auto nt) { fs_calib_launch<decltype(nt)::value>(st, a); });
     return effdet_check_launch();
 }

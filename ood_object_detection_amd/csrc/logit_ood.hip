@@ -18,10 +18,9 @@
 //           the float32-input MFMA (16x16x4), wave w taking the class tiles w, w + 4, ...; beyond 512 classes p passes through
 //           LDS in two K-chunks of 512, the second one recomputed from a second read of the row.  A row's bits depend on nothing
 //           but the row and Cp.
-//   fit     per entry the predicted class, max z and lse (T = 1); the valid entries compacted in (b, j) order (counts -> bases ->
-//           writes, the pattern of feature_rows.h); workgroup (c, s) adds p, max z and (max z)^2 of the rows of class c in chunk s
-//           of the compacted list, in list order, to float64 partials; the chunks are added in chunk order and then to the running
-//           statistics.  The chunk bounds follow from the number of valid rows and C alone.  No floating-point atomics.
+//   fit     per entry the predicted class, max z and lse (T = 1); the valid entries compacted in (b, j) order (compact.h);
+//           workgroup (c, s) adds p, max z and (max z)^2 of the rows of class c in chunk s of the compacted list, in list order,
+//           to float64 partials; the chunks are added in chunk order and then to the running statistics.  The chunk bounds follow from the number of valid rows and C alone.  No floating-point atomics.
 //
 // Every row index is compared with its extent before a pointer is formed, every store index before the store; no call
 // synchronises with the host or allocates, so all of them can be captured in a graph.
@@ -39,9 +38,8 @@ constexpr int LO_NONE = 0x7FFFFFFF;
 
 struct LoArgs {
     const void* z; int bf16; long long bstride, astride;        // the logits: row (b, n) at b * bstride + n * astride (elements)
-    int C, Cp; long long N;
-    unsigned K, total;                                          // total = B * K
-    const long long* anchor; const void* count; int count64;
+    int C, Cp;
+    FoSel sel;                                                  // limit = N
     float T, gamma; int top_m;
     const float *logD, *kl_inf, *mu, *inv_sigma;                // [Cp][Cp], [Cp], [C], [C]; all null before a fit
     float *msp, *neg_entropy, *gen, *joint; long long* pred;
@@ -54,11 +52,8 @@ struct LoArgs {
 
 // first logit of entry i = b * K + j, or null when the entry does not count
 DEV const char* lo_rowp(const LoArgs& a, unsigned i) {
-    if (i >= a.total) return nullptr;
-    const unsigned b = i / a.K, j = i - b * a.K;
-    if (a.count && (long long)j >= fo_count(a.count, a.count64, b)) return nullptr;
-    const long long an = a.anchor ? a.anchor[i] : (long long)j;
-    if (an < 0 || an >= a.N) return nullptr;
+    unsigned b; long long an;
+    if (!fo_select(a.sel, i, &b, &an)) return nullptr;
     return reinterpret_cast<const char*>(a.z) + ((long long)b * a.bstride + an * a.astride) * (a.bf16 ? 2 : 4);
 }
 
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_score_kernel(LoArgs a) {
                 for (int k = lane; k < KC; k += 64) ps[r * PITCH + k] = 0.f;
             if (lane == 0) {
                 ne1s[r] = 0.f; lse1s[r] = 0.f; rv[r] = 0;
-                if (i < a.total) {
+                if (i < a.sel.total) {
                     a.msp[i] = 0.f; a.neg_entropy[i] = 0.f; a.gen[i] = 0.f; a.joint[i] = 0.f; a.pred[i] = -1;
                     if (fitted) { a.kl[i] = 0.f; a.sml[i] = 0.f; a.kl_class[i] = -1; }
                 }
@@ -310,7 +305,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_score_kernel(LoArgs a) {
     __syncthreads();
     if (tid < LO_ROWS) {
         const unsigned i = row0 + tid;
-        if (i < a.total && rv[tid]) {
+        if (i < a.sel.total && rv[tid]) {
             float v = bestv[0][tid]; int c = bestc[0][tid];
             for (int w = 1; w < LO_WAVES; ++w)
                 if (lo_less(bestv[w][tid], bestc[w][tid], v, c)) { v = bestv[w][tid]; c = bestc[w][tid]; }
@@ -329,7 +324,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_fit_rows_kernel(LoArgs a) {
 #pragma unroll 1
     for (int rr = 0; rr < 4; ++rr) {
         const unsigned i = (unsigned)blockIdx.x * LO_ROWS + wave * 4 + rr;
-        if (i >= a.total) continue;
+        if (i >= a.sel.total) continue;
         const char* p = lo_rowp(a, i);
         int cls = -1; float mz = 0.f, lse = 0.f;
         if (p) {
@@ -356,59 +351,16 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_fit_rows_kernel(LoArgs a) {
     }
 }
 
-DEV bool lo_keep(const LoArgs& a, unsigned i) { return i < a.total && a.cls[i] >= 0; }
+DEV bool cp_keep(const LoArgs& a, unsigned i) { return i < a.sel.total && a.cls[i] >= 0; }
+DEV unsigned cp_begin(const LoArgs&) { return 0u; }
+DEV void cp_finish(const LoArgs& a, unsigned, unsigned total) { a.header[0] = fo_min(total, a.sel.total); }
 
-__global__ __launch_bounds__(256) void lo_fit_count_kernel(LoArgs a) {
-    __shared__ unsigned sh[FO_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned base = (unsigned)blockIdx.x * FO_TILE;
-    unsigned c = 0;
-    for (int r = 0; r < FO_ITEMS; ++r) c += lo_keep(a, base + r * FO_THREADS + tid) ? 1u : 0u;
-    const unsigned tot = fo_block_sum<unsigned>(c, sh, tid);
-    if (tid == 0) a.counts[blockIdx.x] = tot;
-}
-
-// one workgroup: counts -> first positions of the workgroups; header[0] = valid rows
-__global__ __launch_bounds__(256) void lo_fit_base_kernel(LoArgs a) {
-    __shared__ unsigned sh[FO_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned chunk = (a.nblocks + FO_THREADS - 1) / FO_THREADS;
-    const unsigned lo = fo_min((unsigned)tid * chunk, a.nblocks), hi = fo_min(lo + chunk, a.nblocks);
-    unsigned sum = 0;
-    for (unsigned k = lo; k < hi; ++k) sum += a.counts[k];
-    unsigned total;
-    unsigned run = fo_block_excl_scan(sum, sh, tid, &total);
-    for (unsigned k = lo; k < hi; ++k) { const unsigned c = a.counts[k]; a.counts[k] = run; run += c; }
-    if (tid == 0) a.header[0] = fo_min(total, a.total);
-}
-
-// wave w of a workgroup owns entries [w * 512, (w + 1) * 512) of its tile, 64 consecutive ones per round: positions follow (b, j)
 __global__ __launch_bounds__(256) void lo_fit_write_kernel(LoArgs a) {
-    __shared__ unsigned wsum[FO_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned base = (unsigned)blockIdx.x * FO_TILE + (unsigned)wave * (64 * FO_ITEMS);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned rank[FO_ITEMS];
-    unsigned keep = 0, wtot = 0;
+    unsigned pos[FO_ITEMS];
+    const unsigned kept = fo_positions(a.counts, pos, [&](int, unsigned i) { return cp_keep(a, i); });
 #pragma unroll
-    for (int r = 0; r < FO_ITEMS; ++r) {
-        const bool k = lo_keep(a, base + r * 64 + lane);
-        const unsigned long long bal = __ballot(k);
-        rank[r] = wtot + fo_popc(bal & below);
-        wtot += fo_popc(bal);
-        keep |= (k ? 1u : 0u) << r;
-    }
-    if (lane == 0) wsum[wave] = wtot;
-    __syncthreads();
-    unsigned first = a.counts[blockIdx.x];
-    for (int w = 0; w < FO_THREADS / 64; ++w) first += w < wave ? wsum[w] : 0u;
-#pragma unroll
-    for (int r = 0; r < FO_ITEMS; ++r) {
-        if (keep & (1u << r)) {
-            const unsigned p = first + rank[r];
-            if (p < a.total) a.list[p] = base + r * 64 + lane;
-        }
-    }
+    for (int r = 0; r < FO_ITEMS; ++r)
+        if ((kept & (1u << r)) && pos[r] < a.sel.total) a.list[pos[r]] = fo_entry(r);
 }
 
 // blockIdx.x = class c, blockIdx.y = chunk s of the compacted list: partial[s][c] = {sum p [C], sum max z, sum (max z)^2, n} over
@@ -417,7 +369,7 @@ __global__ __launch_bounds__(256) void lo_fit_sum_kernel(LoArgs a) {
     __shared__ int match[FO_THREADS];
     const int tid = threadIdx.x, C = a.C;
     const int c = blockIdx.x, s = blockIdx.y;
-    const unsigned V = fo_min(a.header[0], a.total);
+    const unsigned V = fo_min(a.header[0], a.sel.total);
     const unsigned len = (V + (unsigned)a.S - 1) / (unsigned)a.S;
     const unsigned lo = fo_min((unsigned)s * len, V), hi = fo_min(lo + len, V);
     double acc[LO_MAX_CLASSES / FO_THREADS];
@@ -429,7 +381,7 @@ __global__ __launch_bounds__(256) void lo_fit_sum_kernel(LoArgs a) {
         int e = -1;
         if (v < hi) {
             const unsigned i = a.list[v];
-            if (i < a.total && a.cls[i] == c) e = (int)i;
+            if (i < a.sel.total && a.cls[i] == c) e = (int)i;
         }
         match[tid] = e;
         __syncthreads();
@@ -500,13 +452,11 @@ bool lo_layout(long long rows, int C, LoLayout* L) {
 bool lo_args(int dtype, const void* logits, long long image_stride, long long anchor_stride, int C, int B, long long N, long long K,
              const long long* anchor_index, const void* count, int count_is_int64, float temperature, LoArgs* a) {
     if ((dtype != EFFDET_F32 && dtype != EFFDET_BF16) || !logits || image_stride < 0 || anchor_stride < 0) return false;
-    if (C < 1 || C > LO_MAX_CLASSES || B < 1 || N < 1 || N > (1ll << 31) || K < 1 || (long long)B * K > FO_MAX_ROWS) return false;
-    if (!(temperature > 0.f) || !(temperature < __builtin_inff())) return false;
+    if (C < 1 || C > LO_MAX_CLASSES || N > (1ll << 31) || !(temperature > 0.f) || !(temperature < __builtin_inff())) return false;
     *a = LoArgs{};
+    if (!fo_sel(B, K, anchor_index, count, count_is_int64, N, &a->sel)) return false;
     a->z = logits; a->bf16 = dtype == EFFDET_BF16; a->bstride = image_stride; a->astride = anchor_stride;
-    a->C = C; a->Cp = (C + 15) / 16 * 16; a->N = N;
-    a->K = (unsigned)K; a->total = (unsigned)((long long)B * K);
-    a->anchor = anchor_index; a->count = count; a->count64 = count_is_int64 ? 1 : 0;
+    a->C = C; a->Cp = (C + 15) / 16 * 16;
     a->T = temperature;
     return true;
 }
@@ -539,7 +489,7 @@ extern "C" int effdet_logit_ood_score(void* stream, int dtype, const void* logit
     a.msp = msp; a.neg_entropy = neg_entropy; a.gen = gen; a.joint = joint_energy; a.pred = predicted_class;
     a.kl = kl_matching; a.kl_class = kl_class; a.sml = standardized;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((a.total + LO_ROWS - 1) / LO_ROWS), block(LO_WAVES * 64);
+    const dim3 grid((a.sel.total + LO_ROWS - 1) / LO_ROWS), block(LO_WAVES * 64);
     if (a.Cp <= 128) hipLaunchKernelGGL((lo_score_kernel<2, 128, 2>), grid, block, 0, st, a);
     else if (a.Cp <= 256) hipLaunchKernelGGL((lo_score_kernel<4, 256, 4>), grid, block, 0, st, a);
     else if (a.Cp <= 512) hipLaunchKernelGGL((lo_score_kernel<8, 512, 8>), grid, block, 0, st, a);
@@ -567,13 +517,13 @@ extern "C" int effdet_logit_ood_fit(void* stream, int dtype, const void* logits,
     a.partial = reinterpret_cast<double*>(ws + L.partial); a.S = L.S;
     a.n_c = n_c; a.P_c = P_c; a.a_c = a_c; a.b_c = b_c;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((a.total + LO_ROWS - 1) / LO_ROWS), block(LO_WAVES * 64);
+    const dim3 grid((a.sel.total + LO_ROWS - 1) / LO_ROWS), block(LO_WAVES * 64);
     if (a.Cp <= 128) hipLaunchKernelGGL(lo_fit_rows_kernel<2>, grid, block, 0, st, a);
     else if (a.Cp <= 256) hipLaunchKernelGGL(lo_fit_rows_kernel<4>, grid, block, 0, st, a);
     else if (a.Cp <= 512) hipLaunchKernelGGL(lo_fit_rows_kernel<8>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(lo_fit_rows_kernel<16>, grid, block, 0, st, a);
-    hipLaunchKernelGGL(lo_fit_count_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
-    hipLaunchKernelGGL(lo_fit_base_kernel, dim3(1), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_count_kernel<LoArgs>, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_base_kernel<LoArgs>, dim3(1), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(lo_fit_write_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(lo_fit_sum_kernel, dim3(C, a.S), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(lo_fit_reduce_kernel, dim3(C), dim3(FO_THREADS), 0, st, a);

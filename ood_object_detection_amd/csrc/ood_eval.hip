@@ -1,8 +1,8 @@
 // Detection-level OOD evaluation on the device: AUROC pair counts, AUPR (in / out) and FPR at a TPR level over two multisets of
 // float32 scores, `pos` (in-distribution, P values) and `neg` (OOD, N values); a higher score means more in-distribution.
 //
-//   append   [B, K] score matrix -> one side's flat buffer, in (b, j) order from a cursor that lives on the device:
-//            block counts -> bases (one workgroup, also moves the cursor) -> writes.  No atomic decides a position.
+//   append   [B, K] score matrix -> one side's flat buffer, in (b, j) order from a cursor that lives on the device: the ordered
+//            compaction of compact.h, whose base launch also moves the cursor.  No atomic decides a position.
 //   sort     both sides through the same launches (a two-entry problem table, blockIdx.y = side): LSD radix sort of the 32-bit
 //            order-preserving keys, 8 bits a pass, every pass = histogram launch, scan launch, stable scatter launch.
 //   metrics  everything follows from the two sorted arrays by binary search: one launch of per-workgroup partials (uint64 pair
@@ -12,6 +12,7 @@
 // scatter index is compared with the segment length before the store, and the element counts are read from the device cursors
 // (grids are sized by the capacities; workgroups beyond the live count exit), so the host never reads anything back.
 #include "common.h"
+#include "compact.h"
 
 // all lanes of a wave have issued the LDS accesses before this point (the CPU model of tools/simt_model defines its own)
 #ifndef OE_WAVE_SYNC
@@ -23,14 +24,13 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int OE_THREADS = 256;
+static_assert(OE_THREADS == FO_THREADS, "the reductions and the compaction of compact.h are written for this workgroup size");
 constexpr int OE_SORT_ITEMS = 16;
 constexpr int OE_SORT_TILE = OE_THREADS * OE_SORT_ITEMS;          // keys of one workgroup per pass
-constexpr int OE_APPEND_ITEMS = 8;
-constexpr int OE_APPEND_TILE = OE_THREADS * OE_APPEND_ITEMS;      // matrix entries of one workgroup
 constexpr int OE_MET_ITEMS = 8;
 constexpr int OE_MET_TILE = OE_THREADS * OE_MET_ITEMS;            // sorted scores of one workgroup
 constexpr long long OE_MAX_SCORES = 1ll << 27;                    // per side, and per append call
-constexpr long long OE_APPEND_MAX_BLOCKS = OE_MAX_SCORES / OE_APPEND_TILE;
+constexpr long long OE_APPEND_MAX_BLOCKS = OE_MAX_SCORES / FO_TILE;   // FO_TILE matrix entries per append workgroup
 
 // flag bits of a side's state word 1, and of the result block
 constexpr unsigned OE_SIDE_NAN = 1u, OE_SIDE_OVERFLOW = 2u;
@@ -69,8 +69,6 @@ bool oe_layout(long long cap_pos, long long cap_neg, OeLayout* L) {
 }
 
 // ---- small device helpers ----------------------------------------------------------------------------------------------------
-DEV unsigned oe_min(unsigned a, unsigned b) { return a < b ? a : b; }
-DEV unsigned oe_popc(u64 m) { return (unsigned)__builtin_popcountll(m); }
 // float32 bits -> key whose unsigned order is the order of the floats, and back
 DEV unsigned oe_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : (bits ^ 0x80000000u); }
 DEV unsigned oe_unkey(unsigned key) { return (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key; }
@@ -91,33 +89,6 @@ DEV unsigned oe_bound(const unsigned* a, unsigned n, unsigned k, int upper) {
         }
     }
     return lo;
-}
-
-// All OE_THREADS threads call these; sh: [OE_THREADS] of T in LDS.  Fixed order, so a float64 sum has the same bits every run.
-template <typename T> DEV T oe_block_sum(T v, T* sh, int tid) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int s = OE_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] = sh[tid] + sh[tid + s];
-        __syncthreads();
-    }
-    const T r = sh[0];
-    __syncthreads();
-    return r;
-}
-DEV unsigned oe_block_excl_scan(unsigned v, unsigned* sh, int tid, unsigned* total) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < OE_THREADS; off <<= 1) {
-        const unsigned t = tid >= off ? sh[tid - off] : 0u;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const unsigned incl = sh[tid];
-    *total = sh[OE_THREADS - 1];
-    __syncthreads();
-    return incl - v;
 }
 
 // ---- append ------------------------------------------------------------------------------------------------------------------
@@ -145,70 +116,33 @@ DEV bool oe_keep(const OeAppend& a, unsigned i, long long* src) {
     return true;
 }
 
-__global__ __launch_bounds__(256) void oe_append_count_kernel(OeAppend a) {
-    __shared__ unsigned sh[OE_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned base = (unsigned)blockIdx.x * OE_APPEND_TILE;
-    unsigned c = 0;
-    for (int r = 0; r < OE_APPEND_ITEMS; ++r) {
-        long long src;
-        c += oe_keep(a, base + r * OE_THREADS + tid, &src) ? 1u : 0u;
-    }
-    const unsigned tot = oe_block_sum<unsigned>(c, sh, tid);
-    if (tid == 0) a.counts[blockIdx.x] = tot;
+DEV bool cp_keep(const OeAppend& a, unsigned i) { long long src; return oe_keep(a, i, &src); }
+// positions start at the cursor (clamped to the capacity).  fo_base_kernel reads it here, before the barriers of its scan, and
+// calls cp_finish after them: the barriers order the read of the cursor before its write
+DEV unsigned cp_begin(const OeAppend& a) { return fo_min(a.state[0], a.capacity); }
+// the cursor moves (clamped to the capacity, overflow flagged)
+DEV void cp_finish(const OeAppend& a, unsigned c0, unsigned total) {
+    const u64 end = (u64)c0 + total;
+    if (end > a.capacity) a.state[1] |= OE_SIDE_OVERFLOW;
+    a.state[0] = end > a.capacity ? a.capacity : (unsigned)end;
 }
 
-// one workgroup: counts -> first positions of the workgroups, and the cursor moves (clamped to the capacity, overflow flagged)
-__global__ __launch_bounds__(256) void oe_append_base_kernel(OeAppend a) {
-    __shared__ unsigned sh[OE_THREADS];
-    const int tid = threadIdx.x;
-    const unsigned c0 = oe_min(a.state[0], a.capacity);
-    const unsigned chunk = (a.nblocks + OE_THREADS - 1) / OE_THREADS;
-    const unsigned lo = oe_min((unsigned)tid * chunk, a.nblocks), hi = oe_min(lo + chunk, a.nblocks);
-    unsigned sum = 0;
-    for (unsigned k = lo; k < hi; ++k) sum += a.counts[k];
-    unsigned total;
-    unsigned run = c0 + oe_block_excl_scan(sum, sh, tid, &total);        // the scan's barriers order the read of the cursor before its write
-    for (unsigned k = lo; k < hi; ++k) { const unsigned c = a.counts[k]; a.counts[k] = run; run += c; }
-    if (tid == 0) {
-        const u64 end = (u64)c0 + total;
-        if (end > a.capacity) a.state[1] |= OE_SIDE_OVERFLOW;
-        a.state[0] = end > a.capacity ? a.capacity : (unsigned)end;
-    }
-}
-
-// wave w of a workgroup owns entries [w * 512, (w + 1) * 512) of its tile, 64 consecutive ones per round: positions follow (b, j)
 __global__ __launch_bounds__(256) void oe_append_write_kernel(OeAppend a) {
-    __shared__ unsigned wsum[OE_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned base = (unsigned)blockIdx.x * OE_APPEND_TILE + (unsigned)wave * (64 * OE_APPEND_ITEMS);
-    const u64 below = (1ull << lane) - 1ull;
-    long long src[OE_APPEND_ITEMS];
-    unsigned rank[OE_APPEND_ITEMS];
-    unsigned keep = 0, wtot = 0;
-#pragma unroll
-    for (int r = 0; r < OE_APPEND_ITEMS; ++r) {
+    long long src[FO_ITEMS];
+    unsigned pos[FO_ITEMS];
+    const unsigned kept = fo_positions(a.counts, pos, [&](int r, unsigned i) {
         src[r] = 0;
-        const bool k = oe_keep(a, base + r * 64 + lane, &src[r]);
-        const u64 bal = __ballot(k);
-        rank[r] = wtot + oe_popc(bal & below);
-        wtot += oe_popc(bal);
-        keep |= (k ? 1u : 0u) << r;
-    }
-    if (lane == 0) wsum[wave] = wtot;
-    __syncthreads();
-    unsigned first = a.counts[blockIdx.x];
-    for (int w = 0; w < OE_THREADS / 64; ++w) first += w < wave ? wsum[w] : 0u;
+        return oe_keep(a, i, &src[r]);
+    });
     bool nan = false;
 #pragma unroll
-    for (int r = 0; r < OE_APPEND_ITEMS; ++r) {
-        if (keep & (1u << r)) {
+    for (int r = 0; r < FO_ITEMS; ++r) {
+        if (kept & (1u << r)) {
             float v = a.scores[src[r]];
             if (a.negate) v = -v;
             if (v != v) nan = true;
             if (v == 0.f) v = 0.f;                                      // -0.0 is stored as +0.0: the two tie
-            const unsigned p = first + rank[r];
-            if (p < a.capacity) a.buffer[p] = v;                        // beyond the capacity: dropped (the base launch set the flag)
+            if (pos[r] < a.capacity) a.buffer[pos[r]] = v;              // beyond the capacity: dropped (the base launch set the flag)
         }
     }
     if (nan) atomicOr(&a.state[1], OE_SIDE_NAN);                        // an OR of a flag bit: no order to depend on
@@ -232,7 +166,7 @@ __global__ __launch_bounds__(256) void oe_sort_hist_kernel(OeSortTable t) {
     __shared__ unsigned h[256];
     const OeSortSide S = t.s[blockIdx.y];
     const int tid = threadIdx.x;
-    const unsigned n = oe_min(S.cursor[0], S.capacity), tile = blockIdx.x;
+    const unsigned n = fo_min(S.cursor[0], S.capacity), tile = blockIdx.x;
     if (tile >= (n + OE_SORT_TILE - 1) / OE_SORT_TILE) return;          // the same for the whole workgroup
     h[tid] = 0;
     __syncthreads();
@@ -249,14 +183,14 @@ __global__ __launch_bounds__(256) void oe_sort_scan_kernel(OeSortTable t) {
     __shared__ unsigned sh[OE_THREADS];
     const OeSortSide S = t.s[blockIdx.y];
     const int tid = threadIdx.x;
-    const unsigned n = oe_min(S.cursor[0], S.capacity), ntiles = (n + OE_SORT_TILE - 1) / OE_SORT_TILE;
+    const unsigned n = fo_min(S.cursor[0], S.capacity), ntiles = (n + OE_SORT_TILE - 1) / OE_SORT_TILE;
     unsigned* row = S.hist + (unsigned)blockIdx.x * S.tiles;
     const unsigned chunk = (ntiles + OE_THREADS - 1) / OE_THREADS;
-    const unsigned lo = oe_min((unsigned)tid * chunk, ntiles), hi = oe_min(lo + chunk, ntiles);
+    const unsigned lo = fo_min((unsigned)tid * chunk, ntiles), hi = fo_min(lo + chunk, ntiles);
     unsigned sum = 0;
     for (unsigned k = lo; k < hi; ++k) sum += row[k];
     unsigned total;
-    unsigned run = oe_block_excl_scan(sum, sh, tid, &total);
+    unsigned run = fo_block_excl_scan(sum, sh, tid, &total);
     for (unsigned k = lo; k < hi; ++k) { const unsigned c = row[k]; row[k] = run; run += c; }
     if (tid == 0) S.totals[blockIdx.x] = total;
 }
@@ -269,11 +203,11 @@ __global__ __launch_bounds__(256) void oe_sort_scatter_kernel(OeSortTable t) {
     __shared__ unsigned sh[OE_THREADS];
     const OeSortSide S = t.s[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned n = oe_min(S.cursor[0], S.capacity), tile = blockIdx.x;
+    const unsigned n = fo_min(S.cursor[0], S.capacity), tile = blockIdx.x;
     if (tile >= (n + OE_SORT_TILE - 1) / OE_SORT_TILE) return;
     for (int w = 0; w < OE_THREADS / 64; ++w) wcnt[w][tid] = 0;
     unsigned total;
-    const unsigned digit_first = oe_block_excl_scan(S.totals[tid], sh, tid, &total) + S.hist[(unsigned)tid * S.tiles + tile];
+    const unsigned digit_first = fo_block_excl_scan(S.totals[tid], sh, tid, &total) + S.hist[(unsigned)tid * S.tiles + tile];
     // (the scan's barriers also publish the zeroed counters)
     const u64 below = (1ull << lane) - 1ull;
     const unsigned seg = tile * OE_SORT_TILE + (unsigned)wave * (64 * OE_SORT_ITEMS);
@@ -291,10 +225,10 @@ __global__ __launch_bounds__(256) void oe_sort_scatter_kernel(OeSortTable t) {
             const u64 bal = __ballot(bit);
             same &= bit ? bal : ~bal;
         }
-        const unsigned lower = oe_popc(same & below);
+        const unsigned lower = fo_popc(same & below);
         const unsigned prev = valid ? wcnt[wave][d] : 0u;
         OE_WAVE_SYNC();
-        if (valid && lower == 0) wcnt[wave][d] = prev + oe_popc(same);     // one lane per digit present in the round
+        if (valid && lower == 0) wcnt[wave][d] = prev + fo_popc(same);     // one lane per digit present in the round
         OE_WAVE_SYNC();
         key[r] = k;
         rank[r] = prev + lower;
@@ -330,7 +264,7 @@ __global__ __launch_bounds__(256) void oe_metrics_part_kernel(OeMetrics m) {
     __shared__ u64 shu[OE_THREADS];
     __shared__ double shd[OE_THREADS];
     const int tid = threadIdx.x, side = blockIdx.y;
-    const unsigned P = oe_min(m.state[0], m.capacity[0]), N = oe_min(m.state[2], m.capacity[1]);
+    const unsigned P = fo_min(m.state[0], m.capacity[0]), N = fo_min(m.state[2], m.capacity[1]);
     const unsigned n_own = side == 0 ? P : N, n_other = side == 0 ? N : P;
     if (P == 0 || N == 0 || (unsigned)blockIdx.x * OE_MET_TILE >= n_own) return;
     const unsigned* own = m.sorted[side];
@@ -357,9 +291,9 @@ __global__ __launch_bounds__(256) void oe_metrics_part_kernel(OeMetrics m) {
             }
         }
     }
-    gt = oe_block_sum<u64>(gt, shu, tid);
-    eq = oe_block_sum<u64>(eq, shu, tid);
-    ap = oe_block_sum<double>(ap, shd, tid);
+    gt = fo_block_sum<u64>(gt, shu, tid);
+    eq = fo_block_sum<u64>(eq, shu, tid);
+    ap = fo_block_sum<double>(ap, shd, tid);
     if (tid == 0) { m.part_gt[side][blockIdx.x] = gt; m.part_eq[side][blockIdx.x] = eq; m.part_ap[side][blockIdx.x] = ap; }
 }
 
@@ -368,17 +302,17 @@ __global__ __launch_bounds__(256) void oe_metrics_final_kernel(OeMetrics m) {
     __shared__ u64 shu[OE_THREADS];
     __shared__ double shd[OE_THREADS];
     const int tid = threadIdx.x;
-    const unsigned P = oe_min(m.state[0], m.capacity[0]), N = oe_min(m.state[2], m.capacity[1]);
+    const unsigned P = fo_min(m.state[0], m.capacity[0]), N = fo_min(m.state[2], m.capacity[1]);
     const bool empty = P == 0 || N == 0;
     const unsigned nb0 = empty ? 0u : (P + OE_MET_TILE - 1) / OE_MET_TILE, nb1 = empty ? 0u : (N + OE_MET_TILE - 1) / OE_MET_TILE;
     u64 gt = 0, eq = 0;
     double ap_in = 0.0, ap_out = 0.0;
     for (unsigned k = tid; k < nb0; k += OE_THREADS) { gt += m.part_gt[0][k]; eq += m.part_eq[0][k]; ap_in += m.part_ap[0][k]; }
     for (unsigned k = tid; k < nb1; k += OE_THREADS) ap_out += m.part_ap[1][k];
-    gt = oe_block_sum<u64>(gt, shu, tid);
-    eq = oe_block_sum<u64>(eq, shu, tid);
-    ap_in = oe_block_sum<double>(ap_in, shd, tid);
-    ap_out = oe_block_sum<double>(ap_out, shd, tid);
+    gt = fo_block_sum<u64>(gt, shu, tid);
+    eq = fo_block_sum<u64>(eq, shu, tid);
+    ap_in = fo_block_sum<double>(ap_in, shd, tid);
+    ap_out = fo_block_sum<double>(ap_out, shd, tid);
     if (tid != 0) return;
     u64 flags = (u64)(m.state[1] & 3u) | ((u64)(m.state[3] & 3u) << 2);
     if (P == 0) flags |= OE_RES_EMPTY_IN;
@@ -441,10 +375,10 @@ extern "C" int effdet_ood_eval_append(void* stream, const float* scores, long lo
     a.buffer = buffer; a.capacity = (unsigned)capacity;
     a.state = side_state;
     a.counts = reinterpret_cast<unsigned*>(workspace);                  // OeLayout::append_counts is the head of the workspace
-    a.nblocks = (a.total + OE_APPEND_TILE - 1) / OE_APPEND_TILE;
+    a.nblocks = (a.total + FO_TILE - 1) / FO_TILE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(oe_append_count_kernel, dim3(a.nblocks), dim3(OE_THREADS), 0, st, a);
-    hipLaunchKernelGGL(oe_append_base_kernel, dim3(1), dim3(OE_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_count_kernel<OeAppend>, dim3(a.nblocks), dim3(OE_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_base_kernel<OeAppend>, dim3(1), dim3(OE_THREADS), 0, st, a);
     hipLaunchKernelGGL(oe_append_write_kernel, dim3(a.nblocks), dim3(OE_THREADS), 0, st, a);
     return effdet_check_launch();
 }

@@ -202,6 +202,36 @@ class _PyramidRows:
             raise ValueError('between 1 and 2^27 rows per call')
         return K, ai_ptr, cnt_ptr, cnt64, keep
 
+    def _classes(self, classes, B, K, dev):
+        """classes [B, K] -> (pointer, dtype code, image stride, entry stride, tensor to keep alive)"""
+        if not torch.is_tensor(classes) or classes.device != dev or classes.dim() != 2 or classes.shape[0] != B:
+            raise ValueError('classes: a [B, K] tensor on the device of the features')
+        if classes.dtype not in (torch.int32, torch.int64, torch.float32):
+            raise ValueError('classes must be int32, int64 or float32')
+        if classes.shape[1] != K:
+            raise ValueError('classes must be [B, %d] like the rows' % K)
+        classes = classes.detach()
+        if min(classes.stride()) < 0:
+            classes = classes.contiguous()
+        return classes.data_ptr(), {torch.int32: 0, torch.int64: 1, torch.float32: 2}[classes.dtype], classes.stride(0), classes.stride(1), classes
+
+    @staticmethod
+    def _det_classes(det):
+        """det [B, max_det, 6] of a `DetBenchPredict` pass -> its class column (class + 1)"""
+        if not torch.is_tensor(det) or det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32:
+            raise ValueError('det must be a float32 [B, max_det, 6] tensor')
+        return det[..., 5]
+
+    @staticmethod
+    def _stream_ws(dev, need=None, rows=0):
+        """(the current stream of dev, a workspace of `need` bytes of this call's own or None): the caching allocator hands it out
+        per stream, so the sub-batch streams of a `DetBenchPredict` do not share one; inside a graph capture it comes from the
+        graph's pool"""
+        if need is not None and need <= 0:
+            raise ValueError('between 1 and 2^27 rows per call, got %d' % rows)
+        ws = None if need is None else torch.empty(need, dtype=torch.uint8, device=dev)
+        return torch.cuda.current_stream(dev).cuda_stream, ws
+
 
 class FeatureOOD(_PyramidRows):
     """Running class statistics of pyramid features and the two scores that follow from them (module docstring).
@@ -261,32 +291,19 @@ class FeatureOOD(_PyramidRows):
         (None: all) and the class lies in [0, num_classes) - so -1 / ignore labels pass through."""
         dt, B, P, table, keep = self._table(levels)
         dev = keep[0].device
-        if not torch.is_tensor(classes) or classes.device != dev or classes.dim() != 2 or classes.shape[0] != B:
-            raise ValueError('classes: a [B, K] tensor on the device of the features')
-        if classes.dtype not in (torch.int32, torch.int64, torch.float32):
-            raise ValueError('classes must be int32, int64 or float32')
         K, ai_ptr, cnt_ptr, cnt64, keep2 = self._rows(B, dev, anchor_index, count, self.A * P)
-        if classes.shape[1] != K:
-            raise ValueError('classes must be [B, %d] like the rows' % K)
-        classes = classes.detach()
-        if min(classes.stride()) < 0:
-            classes = classes.contiguous()
-        cdt = {torch.int32: 0, torch.int64: 1, torch.float32: 2}[classes.dtype]
+        cls_ptr, cdt, pitch, stride, classes = self._classes(classes, B, K, dev)
         n_c, s_c, S = self._setup()
         ws = self._workspace(B * K)
-        lib = _lib.load()
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.effdet_feature_ood_fit(st, dt, *table, self.F, self.C, self.A, B, K, ai_ptr, classes.data_ptr(), cdt,
-                                              classes.stride(0), classes.stride(1), int(class_offset), cnt_ptr, cnt64,
-                                              n_c.data_ptr(), s_c.data_ptr(), S.data_ptr(), ws.data_ptr(), ws.numel()),
-                   'effdet_feature_ood_fit')
+        st, _ = self._stream_ws(dev)
+        _lib.check(_lib.load().effdet_feature_ood_fit(st, dt, *table, self.F, self.C, self.A, B, K, ai_ptr, cls_ptr, cdt, pitch, stride,
+                                                      int(class_offset), cnt_ptr, cnt64, n_c.data_ptr(), s_c.data_ptr(), S.data_ptr(),
+                                                      ws.data_ptr(), ws.numel()), 'effdet_feature_ood_fit')
 
     def add_detections(self, levels, det, anchor_index, count):
         """Add the kept detections of a `DetBenchPredict` pass: det [B, max_det, 6] (class + 1 in det[..., 5]),
         anchor_index = bench.last_ood['anchor_index'], count = bench.last_count."""
-        if not torch.is_tensor(det) or det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32:
-            raise ValueError('det must be a float32 [B, max_det, 6] tensor')
-        self.add(levels, det[..., 5], anchor_index, count, class_offset=1)
+        self.add(levels, self._det_classes(det), anchor_index, count, class_offset=1)
 
     def add_targets(self, levels, cls_targets):
         """Add every anchor with a class >= 0 of the per-level [B, H, W, A] label maps of `AnchorLabeler` (the dense form)."""
@@ -317,11 +334,10 @@ class FeatureOOD(_PyramidRows):
         maha = torch.empty(B, K, dtype=torch.float32, device=dev)
         rel = torch.empty_like(maha)
         near = torch.empty(B, K, dtype=torch.int32, device=dev)
-        lib = _lib.load()
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.effdet_feature_ood_score(st, dt, *table, self.F, self.C, A, B, K, ai_ptr, cnt_ptr, cnt64,
-                                                *[t.data_ptr() for t in self._dev], maha.data_ptr(), rel.data_ptr(), near.data_ptr()),
-                   'effdet_feature_ood_score')
+        st, _ = self._stream_ws(dev)
+        _lib.check(_lib.load().effdet_feature_ood_score(st, dt, *table, self.F, self.C, A, B, K, ai_ptr, cnt_ptr, cnt64,
+                                                        *[t.data_ptr() for t in self._dev], maha.data_ptr(), rel.data_ptr(),
+                                                        near.data_ptr()), 'effdet_feature_ood_score')
         return {'mahalanobis': maha, 'relative_mahalanobis': rel, 'nearest_class': near}
 
     def score(self, levels, anchor_index, count=None):
@@ -430,12 +446,8 @@ class KNNFeatureOOD(_PyramidRows):
     lost = property(lambda self: self._counts()[2])
 
     def _workspace(self, rows, k, splits, dev):
-        """A workspace of this call's own (the caching allocator hands it out per stream, so the sub-batch streams of a
-        `DetBenchPredict` do not share one; inside a graph capture it comes from the graph's pool)."""
-        need = _lib.load().effdet_feature_knn_workspace_bytes(rows, self.F, k, splits)
-        if need <= 0:
-            raise ValueError('between 1 and 2^27 rows per call, got %d' % rows)
-        return torch.empty(need, dtype=torch.uint8, device=dev)
+        """(stream, workspace) of a call: k = 0 for an append"""
+        return self._stream_ws(dev, _lib.load().effdet_feature_knn_workspace_bytes(rows, self.F, k, splits), rows)
 
     # ---- bank ------------------------------------------------------------------------------------------------------------
     def clear(self):
@@ -451,18 +463,9 @@ class KNNFeatureOOD(_PyramidRows):
         K, ai_ptr, cnt_ptr, cnt64, keep2 = self._rows(B, dev, anchor_index, count, self.A * P)
         cls_ptr, cdt, pitch, stride = None, 0, 0, 0
         if self.C:
-            if not torch.is_tensor(classes) or classes.device != dev or classes.dim() != 2 or tuple(classes.shape) != (B, K):
-                raise ValueError('classes: a [B, %d] tensor on the device of the features' % K)
-            if classes.dtype not in (torch.int32, torch.int64, torch.float32):
-                raise ValueError('classes must be int32, int64 or float32')
-            classes = classes.detach()
-            if min(classes.stride()) < 0:
-                classes = classes.contiguous()
-            cls_ptr, cdt = classes.data_ptr(), {torch.int32: 0, torch.int64: 1, torch.float32: 2}[classes.dtype]
-            pitch, stride = classes.stride(0), classes.stride(1)
+            cls_ptr, cdt, pitch, stride, classes = self._classes(classes, B, K, dev)
         bank, norms, bcls, counters = self._setup()
-        ws = self._workspace(B * K, 0, 0, dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st, ws = self._workspace(B * K, 0, 0, dev)
         _lib.check(_lib.load().effdet_feature_knn_append(st, dt, *table, self.F, self.C, self.A, B, K, ai_ptr, cls_ptr, cdt, pitch, stride,
                                                          int(class_offset), cnt_ptr, cnt64, int(self.normalize), self.sample_every,
                                                          self.capacity, bank.data_ptr(), norms.data_ptr(), bcls.data_ptr(),
@@ -472,9 +475,8 @@ class KNNFeatureOOD(_PyramidRows):
     def add_detections(self, levels, det, anchor_index, count):
         """Append the kept detections of a `DetBenchPredict` pass: det [B, max_det, 6] (class + 1 in det[..., 5]),
         anchor_index = bench.last_ood['anchor_index'], count = bench.last_count."""
-        if not torch.is_tensor(det) or det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32:
-            raise ValueError('det must be a float32 [B, max_det, 6] tensor')
-        self.add(levels, det[..., 5] if self.C else None, anchor_index, count, class_offset=1)
+        labels = self._det_classes(det)
+        self.add(levels, labels if self.C else None, anchor_index, count, class_offset=1)
 
     def add_targets(self, levels, cls_targets):
         """Append every anchor with a class >= 0 of the per-level [B, H, W, A] label maps of `AnchorLabeler` (the dense form; one
@@ -512,8 +514,7 @@ class KNNFeatureOOD(_PyramidRows):
         idx = torch.empty(B, K, dtype=torch.int32, device=dev)
         cls = torch.empty(B, K, dtype=torch.int32, device=dev)
         bank, norms, bcls, _ = self._setup()
-        ws = self._workspace(B * K, self.k, self.splits, dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st, ws = self._workspace(B * K, self.k, self.splits, dev)
         _lib.check(_lib.load().effdet_feature_knn_score(st, dt, *table, self.F, A, B, K, ai_ptr, cnt_ptr, cnt64, int(self.normalize), self.k,
                                                         self.splits, self.M, bank.data_ptr(), norms.data_ptr(), bcls.data_ptr(),
                                                         knn.data_ptr(), idx.data_ptr(), cls.data_ptr(), ws.data_ptr(), ws.numel()),
@@ -688,9 +689,7 @@ class SubspaceFeatureOOD(_PyramidRows):
         Rt, il, mu0 = self._dev
         n, sums = self._counters()
         lib = _lib.load()
-        need = lib.effdet_feature_subspace_workspace_bytes(B * K)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # per call: the caching allocator hands it out per stream
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st, ws = self._stream_ws(dev, lib.effdet_feature_subspace_workspace_bytes(B * K), B * K)
         _lib.check(lib.effdet_feature_subspace_calibrate(st, dt, *table, self.F, self.A, B, K, ai_ptr, cnt_ptr, cnt64, Rt.data_ptr(),
                                                          mu0.data_ptr(), Rt.shape[0], ls.data_ptr(), ls.stride(0), ls.stride(1),
                                                          int(self.logit == 'energy'), n.data_ptr(), sums.data_ptr(), ws.data_ptr(),
@@ -733,7 +732,7 @@ class SubspaceFeatureOOD(_PyramidRows):
             out['vim'] = torch.empty_like(res)
             ls_ptr, pitch, stride, vim_ptr, alpha = ls.data_ptr(), ls.stride(0), ls.stride(1), out['vim'].data_ptr(), self.alpha
         Rt, il, mu0 = self._dev
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st, _ = self._stream_ws(dev)
         _lib.check(_lib.load().effdet_feature_subspace_score(st, dt, *table, self.F, A, B, K, ai_ptr, cnt_ptr, cnt64, Rt.data_ptr(),
                                                              il.data_ptr(), mu0.data_ptr(), Rt.shape[0], ls_ptr, pitch, stride,
                                                              int(self.logit == 'energy'), alpha, res.data_ptr(), pm.data_ptr(), vim_ptr),

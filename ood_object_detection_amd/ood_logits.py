@@ -146,12 +146,8 @@ class LogitOOD(_PyramidRows):
         if min_max_logit is not None and not np.isfinite(float(min_max_logit)):
             raise ValueError('min_max_logit must be finite or None')
         lib = _lib.load()
-        need = lib.effdet_logit_ood_workspace_bytes(B * K, self.C)
-        if need <= 0:
-            raise ValueError('between 1 and 2^27 rows per call, got %d' % (B * K))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # per call: the caching allocator hands it out per stream
+        st, ws = self._stream_ws(dev, lib.effdet_logit_ood_workspace_bytes(B * K, self.C), B * K)
         n_c, P_c, a_c, b_c = self._setup()
-        st = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(lib.effdet_logit_ood_fit(st, *self._head(logits), K, ai_ptr, cnt_ptr, cnt64, self.temperature,
                                             int(min_max_logit is not None), float(min_max_logit or 0.0), n_c.data_ptr(), P_c.data_ptr(),
                                             a_c.data_ptr(), b_c.data_ptr(), ws.data_ptr(), ws.numel()), 'effdet_logit_ood_fit')
@@ -185,7 +181,7 @@ class LogitOOD(_PyramidRows):
                for k in self.KEYS if self._dev is not None or k not in self.FITTED_KEYS}
         fitted = [None] * 4 if self._dev is None else [t.data_ptr() for t in self._dev]
         ptr = lambda k: out[k].data_ptr() if k in out else None
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st, _ = self._stream_ws(dev)
         _lib.check(_lib.load().effdet_logit_ood_score(st, *self._head(logits), K, ai_ptr, cnt_ptr, cnt64, self.temperature, self.gamma,
                                                       self.top_m, *fitted, ptr('msp'), ptr('neg_entropy'), ptr('gen'), ptr('joint_energy'),
                                                       ptr('predicted_class'), ptr('kl_matching'), ptr('kl_class'),

@@ -34,6 +34,14 @@ def test_entry_points_declared_bound_and_exported():
     for unit in ('feature_ood.hip', 'feature_knn.hip'):
         src = open(os.path.join(csrc, unit)).read()
         assert '#include "feature_rows.h"' in src and 'fo_row(const FoLevels' not in src, unit
+    # so are the ordered compaction and the reductions, in compact.h: no unit defines a count or a base kernel of its own
+    assert re.search(r'build/feature_ood\.o build/feature_knn\.o:\s*feature_rows\.h compact\.h', mk)
+    assert re.search(r'build/ood_eval\.o:\s*compact\.h', mk)
+    assert '#include "compact.h"' in open(os.path.join(csrc, 'feature_rows.h')).read()
+    for unit in ('feature_ood.hip', 'feature_knn.hip', 'feature_subspace.hip', 'logit_ood.hip', 'ood_eval.hip'):
+        src = open(os.path.join(csrc, unit)).read()
+        assert not re.search(r'void \w+_(count|base)_kernel\(', src) and 'block_sum(T v' not in src and 'oe_block_sum' not in src, unit
+    assert '#include "compact.h"' in open(os.path.join(csrc, 'ood_eval.hip')).read()
 
 
 def _table(n=1, cells=(100,), channel=1, F=64):

@@ -151,6 +151,8 @@ def test_entry_points_declared_bound_and_exported():
     assert re.search(r'build/feature_subspace\.o:\s*feature_rows\.h', mk)
     src = open(os.path.join(_lib.CSRC, 'feature_subspace.hip')).read()
     assert '#include "feature_rows.h"' in src and 'fo_row(const FoLevels' not in src      # the row addressing is stated once
+    assert re.search(r'build/feature_subspace\.o:\s*feature_rows\.h compact\.h', mk)
+    assert 'fo_stage_centered<NT>(' in src and 'struct FsGeom' not in src and 'fs_stage' not in src     # ... and so are geometry and staging
     assert 'atomicAdd' not in src and 'mfma_f32_16x16x32_bf16' not in src                 # no atomics, no bf16 product
 
 

@@ -135,6 +135,8 @@ def test_entry_points_declared_bound_and_exported():
     assert re.search(r'build/logit_ood\.o:\s*feature_rows\.h', mk)
     src = open(os.path.join(_lib.CSRC, 'logit_ood.hip')).read()
     assert '#include "feature_rows.h"' in src and 'fo_block_excl_scan(unsigned' not in src      # the compaction helpers are stated once
+    assert re.search(r'build/logit_ood\.o:\s*feature_rows\.h compact\.h', mk)
+    assert not re.search(r'void \w+_(count|base)_kernel\(', src) and 'fo_count_kernel<LoArgs>' in src      # ... and so are its launches
     assert 'atomicAdd' not in src and 'mfma_f32_16x16x32_bf16' not in src                       # no atomics, no bf16 product
     assert 'mma_chunk(' in src                                                                   # the float32-input MFMA of common.h
 

@@ -32,6 +32,7 @@ CSRC = os.path.join(ROOT, 'ood_object_detection_amd', 'csrc')
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
     shutil.copy(os.path.join(CSRC, 'feature_rows.h'), tmp)
+    shutil.copy(os.path.join(CSRC, 'compact.h'), tmp)
     src = open(os.path.join(CSRC, 'feature_knn.hip')).read()
     with open(os.path.join(tmp, 'feature_knn.cpp'), 'w') as f:
         f.write(PRELUDE + src)

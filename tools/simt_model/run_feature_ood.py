@@ -31,6 +31,7 @@ GUARD = 64
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
     shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'feature_rows.h'), tmp)      # included by the unit
+    shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'compact.h'), tmp)
     src =open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'feature_ood.hip')).read()
     with open(os.path.join(tmp, 'feature_ood.cpp'), 'w') as f:
         f.write(PRELUDE + src)

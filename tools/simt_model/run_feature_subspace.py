@@ -33,6 +33,7 @@ A = 3
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
     shutil.copy(os.path.join(CSRC, 'feature_rows.h'), tmp)       # included by the unit
+    shutil.copy(os.path.join(CSRC, 'compact.h'), tmp)
     src = open(os.path.join(CSRC, 'feature_subspace.hip')).read()
     with open(os.path.join(tmp, 'feature_subspace.cpp'), 'w') as f:
         f.write(PRELUDE + src)

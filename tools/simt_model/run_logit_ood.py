@@ -33,6 +33,7 @@ FILL = -12345.5
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
     shutil.copy(os.path.join(CSRC, 'feature_rows.h'), tmp)       # included by the unit
+    shutil.copy(os.path.join(CSRC, 'compact.h'), tmp)
     src = open(os.path.join(CSRC, 'logit_ood.hip')).read()
     with open(os.path.join(tmp, 'logit_ood.cpp'), 'w') as f:
         f.write(PRELUDE + src)

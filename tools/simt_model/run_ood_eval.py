@@ -33,6 +33,7 @@ SENTINEL = np.float32(-12345.5)
 
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
+    shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'compact.h'), tmp)       # included by the unit
     src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'ood_eval.hip')).read()
     with open(os.path.join(tmp, 'ood_eval.cpp'), 'w') as f:
         f.write(PRELUDE + src)
