@@ -917,6 +917,31 @@ int effdet_logit_ood_fit(void* stream, int dtype, const void* logits, long long 
 /* bytes of the fit workspace for `rows` = B * K rows of C classes (pure host code; -22 for a bad argument) */
 long long effdet_logit_ood_workspace_bytes(long long rows, int C);
 
+/* ---- energy-margin OOD training losses (csrc/energy_reg.hip): energy-bounded hinge and logistic uncertainty loss, with gradients --
+ * Rows are the C class logits (float32 or bfloat16, dtype = EFFDET_F32 / EFFDET_BF16) of a contiguous [B][N][C] tensor, role [B][N]
+ * int8: 1 = in-distribution, 0 = outlier, anything else = the row does not count and is not read.  1 <= C <= 1024, B * N <= 2^27.
+ * energy_kind 0 (logsumexp): mz = max z, m = mz / temperature, s = sum_k exp(z_k / temperature - m), E = -(temperature * (m + log s));
+ * energy_kind 1 (joint, temperature must be 1): E = -sum_k (max(z_k, 0) + log1p(exp(-|z_k|))).  With use_min != 0 an outlier row
+ * counts only when mz >= min_max_logit (a row that holds a NaN does not pass).
+ * form 0 (hinge): l_in = max(0, E - margin_in)^2, l_out = max(0, margin_out - E)^2;  form 1 (logistic, phi = (w, b) on the device):
+ * sv = w * (-E) + b, l_in = softplus(-sv), l_out = softplus(sv).  E, its derivative and grad_logits are float32 in that order; the
+ * terms of the sums over rows are evaluated in float64 - the hinge's l from the float32 max(0, .), the logistic l and dl/dsv from
+ * the float32 m and s of the log-sum-exp (E once more as -(temperature * (m + log s)) in float64) or from the float32 joint energy -
+ * and added in float64 in an order that follows from B * N alone (no floating-point atomics).
+ *   loss [1] float32 = c_in * sum_in l + c_out * sum_out l,  c_side = weight_side / max(n_side, 1);
+ *   stats [8] float64 = n_in, n_out, mean l in / out, mean E in / out, rows with a positive hinge in / out (0 for form 1);
+ *   energy [B][N] float32 or NULL: E, 0 where the row does not count;
+ *   grad_logits [B][N][C] in the logits' dtype or NULL: d loss / d z, zero in every row that does not count;
+ *   grad_phi [2] float32: d loss / d (w, b) (0 for form 0).
+ * Bad arguments return -22 before any launch.  No call synchronises with the host or allocates; three launches, four with
+ * grad_logits; results are bit-identical from run to run. */
+int effdet_energy_reg(void* stream, int dtype, const void* logits, const signed char* role, int B, long long N, int C, int form,
+                      int energy_kind, float temperature, float margin_in, float margin_out, float weight_in, float weight_out,
+                      int use_min, float min_max_logit, const float* phi, float* loss, double* stats, float* energy,
+                      void* grad_logits, float* grad_phi, void* workspace, long long workspace_bytes);
+/* bytes of the workspace for `rows` = B * N rows (pure host code; -22 for a bad argument) */
+long long effdet_energy_reg_workspace_bytes(long long rows);
+
 /* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
 
 /* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at

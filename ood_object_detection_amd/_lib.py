@@ -107,6 +107,10 @@ SIGNATURES = {
     'effdet_logit_ood_fit': (c_int, [c_void_p, c_int, c_void_p, c_ll, c_ll, c_int, c_int, c_ll, c_ll, c_void_p, c_void_p, c_int, c_float,
                                      c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
     'effdet_logit_ood_workspace_bytes': (c_ll, [c_ll, c_int]),
+    'effdet_energy_reg': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_ll, c_int, c_int, c_int, c_float, c_float, c_float,
+                                  c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_ll]),
+    'effdet_energy_reg_workspace_bytes': (c_ll, [c_ll]),
     'effdet_sepconv_meta': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_sepconv_tiles': (c_int, [c_int, c_int, c_void_p, c_void_p]),

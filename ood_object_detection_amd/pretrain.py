@@ -28,13 +28,17 @@ def set_bn_eval(module):
 
 class PretrainStep(object):
     def __init__(self, model, lr=1e-3, max_grad_norm=10.0, alpha=0.15, box_loss_weight=50.0, freeze_bn=False,
-                 labeler=True, graph=False, graph_warmup=2, optimizer=None):
+                 labeler=True, graph=False, graph_warmup=2, optimizer=None, ood_regularizer=None, ood_background='none'):
         """graph=True: after `graph_warmup` eager iterations the whole iteration (zero_grad, forward, loss, backward and -
         single GPU - clip + Adam) is captured into one hipGraph and replayed; the ~5 000 launches of a step then cost one
         submission.  Shapes must stay fixed; labels are assigned eagerly and copied into the graph's static buffers.
         optimizer: an `optim.GroupedOptimizer` over (some of) the model's parameters, used in place of the FlatAdam that is
         otherwise built from `lr` / `max_grad_norm` (parameter groups, clip domains, Nesterov SGD: optim.script_param_groups);
-        'grad_norm' is then its 1-d tensor of per-domain norms."""
+        'grad_norm' is then its 1-d tensor of per-domain norms.
+        ood_regularizer: an `ood_train.EnergyRegularizer`; target['outlier'] ([B] bool) then names the outlier-exposure images, the
+        roles of the anchors are formed next to the labels (`ood_train.anchor_roles`, background=ood_background), the loss is the
+        detection loss plus the regulariser's, and the returned dict gains 'ood_loss' and the regulariser's statistics.  The default
+        FlatAdam then covers the model's parameters followed by the regulariser's; a caller's optimizer covers them or not."""
         from .effdet.anchors import Anchors, AnchorLabeler
         from .effdet.config import set_config_writeable
         from .effdet.loss import DetectionLoss
@@ -49,7 +53,13 @@ class PretrainStep(object):
         cfg.alpha, cfg.box_loss_weight = alpha, box_loss_weight
         self.loss_fn = DetectionLoss(cfg)
         self._grouped = optimizer is not None
-        self.opt = optimizer if self._grouped else FlatAdam(model.parameters(), lr=lr, max_grad_norm=max_grad_norm)
+        self.ood, self.ood_background = ood_regularizer, ood_background
+        if self._grouped:
+            self.opt = optimizer
+        elif self.ood is None:
+            self.opt = FlatAdam(model.parameters(), lr=lr, max_grad_norm=max_grad_norm)
+        else:
+            self.opt = FlatAdam(list(model.parameters()) + list(self.ood.parameters()), lr=lr, max_grad_norm=max_grad_norm)
         self.anchors = Anchors.from_config(cfg).to(model.backbone.conv_stem.weight.device)
         self.labeler = AnchorLabeler(self.anchors, cfg.num_classes, match_threshold=0.5) if labeler else None
         self.num_levels = cfg.num_levels
@@ -65,6 +75,7 @@ class PretrainStep(object):
         self._calls = 0
         self._cap = None                        # (graph, optimizer graph or None, static inputs, static outputs)
         self._static_base = None
+        self._cap_ood = None                    # with a regulariser: (static roles, its captured loss and statistics)
 
     def targets(self, target):
         """target: {'bbox': [per-image [M,4] yxyx], 'cls': [per-image [M]]} (labelled on the GPU, effdet/anchors.py:384-438)
@@ -75,6 +86,15 @@ class PretrainStep(object):
         if self.labeler is None:
             raise ValueError('pre-labelled targets or labeler=True needed')
         return self.labeler.batch_label_anchors(target['bbox'], target['cls'])
+
+    def roles(self, target, cls_t):
+        """with a regulariser: the int8 [B, N] role of every anchor from the labels and target['outlier'], else None"""
+        if self.ood is None:
+            return None
+        if 'outlier' not in target:
+            raise ValueError("an ood_regularizer needs target['outlier'], a [B] bool tensor")
+        from .ood_train import anchor_roles
+        return anchor_roles(cls_t, target['outlier'].to(cls_t[0].device), self.ood_background)
 
     def detections(self, class_out, box_out):
         """pretrain.py:238-245: _post_process + generate_detections(hard NMS, no clipping) for the whole batch.
@@ -107,7 +127,7 @@ class PretrainStep(object):
         return det, count
 
     # ---- captured iteration ---------------------------------------------------------------------------------
-    def _capture(self, x, cls_t, box_t, npos):
+    def _capture(self, x, cls_t, box_t, npos, roles=None):
         model, opt = self.model, self.opt
         from .effdet.loss import _pack_targets
         sx = x.clone()
@@ -121,6 +141,7 @@ class PretrainStep(object):
             s_cls = [t.clone() for t in cls_t]
             s_box = [t.clone() for t in box_t]
         s_np = npos.clone()
+        s_roles = None if roles is None else roles.clone()
         torch.cuda.synchronize()
         g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1):
@@ -128,6 +149,11 @@ class PretrainStep(object):
             feats = model(sx, mode='bb')
             class_out, box_out = model(feats, mode='fpn_and_head')
             loss, class_loss, box_loss = self.loss_fn(class_out, box_out, s_cls, s_box, s_np)
+            ood = None
+            if s_roles is not None:
+                ood_loss, ood_stats = self.ood(class_out, s_roles)
+                loss = loss + ood_loss
+                ood = dict(ood_stats, ood_loss=ood_loss.detach())
             loss.backward()
             # a GroupedOptimizer's step() records only its launches under capture: its step counts live on the device
             step_captured = opt.step if self._grouped else opt.step_captured
@@ -140,8 +166,9 @@ class PretrainStep(object):
                 outs[3] = step_captured()
         del feats, class_out, box_out, loss
         self._cap = (g1, g2, (sx, s_cls, s_box, s_np), outs)
+        self._cap_ood = (s_roles, ood)
 
-    def _replay(self, x, cls_t, box_t, npos, time_allreduce):
+    def _replay(self, x, cls_t, box_t, npos, time_allreduce, roles=None):
         g1, g2, (sx, s_cls, s_box, s_np), outs = self._cap
         if tuple(x.shape) != tuple(sx.shape) or x.dtype != sx.dtype:
             raise ValueError('graph mode: input shape / dtype changed (%s %s, captured %s %s)' % (tuple(x.shape), x.dtype, tuple(sx.shape), sx.dtype))
@@ -162,6 +189,8 @@ class PretrainStep(object):
             for d, t in zip(s_box, box_t):
                 d.copy_(t)
         s_np.copy_(npos)
+        if roles is not None:
+            self._cap_ood[0].copy_(roles)
         if self._grouped:
             self.opt.refresh()                  # learning rates edited since the last replay reach the device tables
         else:
@@ -171,8 +200,11 @@ class PretrainStep(object):
             self._allreduce(time_allreduce)
             g2.replay()
         self.model.invalidate()
-        return {'loss': outs[0].clone(), 'class_loss': outs[1].clone(), 'box_loss': outs[2].clone(),
-                'grad_norm': None if outs[3] is None else outs[3].clone()}
+        res = {'loss': outs[0].clone(), 'class_loss': outs[1].clone(), 'box_loss': outs[2].clone(),
+               'grad_norm': None if outs[3] is None else outs[3].clone()}
+        if roles is not None:
+            res.update({k: v.clone() for k, v in self._cap_ood[1].items()})
+        return res
 
     def _allreduce(self, time_allreduce):
         import torch.distributed as dist
@@ -208,14 +240,21 @@ class PretrainStep(object):
         self._engine_flags()
         if self.graph and evaluator is None and self._calls > self._graph_warmup:
             cls_t, box_t, npos = self.targets(target)
+            roles = self.roles(target, cls_t)
             if self._cap is None:
-                self._capture(x, cls_t, box_t, npos)
-            return self._replay(x, cls_t, box_t, npos, time_allreduce)
+                self._capture(x, cls_t, box_t, npos, roles)
+            return self._replay(x, cls_t, box_t, npos, time_allreduce, roles)
         opt.zero_grad()
         cls_t, box_t, npos = self.targets(target)
+        roles = self.roles(target, cls_t)
         feats = model(x, mode='bb')
         class_out, box_out = model(feats, mode='fpn_and_head')
         loss, class_loss, box_loss = self.loss_fn(class_out, box_out, cls_t, box_t, npos)
+        ood = None
+        if roles is not None:
+            ood_loss, ood_stats = self.ood(class_out, roles)
+            loss = loss + ood_loss
+            ood = dict(ood_stats, ood_loss=ood_loss.detach())
         loss.backward()
         if evaluator is not None:
             self.evaluate(class_out, box_out, target, evaluator)
@@ -223,4 +262,7 @@ class PretrainStep(object):
             self._allreduce(time_allreduce)
         norm = opt.step()
         model.invalidate()                      # the inference engine's packed weights are stale now
-        return {'loss': loss.detach(), 'class_loss': class_loss, 'box_loss': box_loss, 'grad_norm': norm}
+        res = {'loss': loss.detach(), 'class_loss': class_loss, 'box_loss': box_loss, 'grad_norm': norm}
+        if ood is not None:
+            res.update(ood)
+        return res
