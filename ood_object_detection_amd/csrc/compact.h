@@ -1,7 +1,8 @@
-// Workgroup reductions and the ordered compaction of the OOD units (feature_ood.hip, feature_knn.hip, logit_ood.hip, ood_eval.hip;
-// DESIGN.md §8): the kept entries of a [B, K] call get consecutive positions in (b, j) order by three launches - kept entries per
-// tile of 2048 (fo_count_kernel), the tiles' first positions in one workgroup (fo_base_kernel), then ballot ranks inside a tile
-// (fo_positions, called by the unit's own write kernel).  No atomic decides a position.  A unit describes its compaction by a struct
+// Workgroup reductions, integer helpers and the ordered compaction that the OOD and the evaluation units share (feature_ood.hip,
+// feature_knn.hip, logit_ood.hip, ood_eval.hip, eval_scale.hip).  The compaction: the kept entries of a [B, K] call
+// get consecutive positions in (b, j) order by three launches - kept entries per tile of 2048 (fo_count_kernel), the tiles' first
+// positions in one workgroup (fo_base_kernel), then ballot ranks inside a tile (fo_positions, called by the unit's own write
+// kernel).  No atomic decides a position.  A unit describes its compaction by a struct
 // A with `unsigned* counts` ([nblocks]), `unsigned nblocks` and three overloads beside it:
 //   bool cp_keep(const A&, unsigned i)                          is entry i kept?  (false at i >= total)
 //   unsigned cp_begin(const A&)                                 the position of the first kept entry
@@ -12,13 +13,32 @@
 namespace {
 
 constexpr int FO_THREADS = 256;
+constexpr int FO_WAVES = FO_THREADS / 64;
 constexpr int FO_ITEMS = 8;
 constexpr int FO_TILE = FO_THREADS * FO_ITEMS;                  // [B, K] entries of one compaction workgroup
 
 DEV unsigned fo_min(unsigned a, unsigned b) { return a < b ? a : b; }
 DEV unsigned fo_popc(unsigned long long m) { return (unsigned)__builtin_popcountll(m); }
+// float32 bits -> key whose unsigned order is the order of the floats, and back
+DEV unsigned fo_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : (bits ^ 0x80000000u); }
+DEV unsigned fo_unkey(unsigned key) { return (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key; }
+// largest power of two <= n (0 for 0)
+DEV unsigned fo_floor_pow2(unsigned n) {
+    n |= n >> 1; n |= n >> 2; n |= n >> 4; n |= n >> 8; n |= n >> 16;
+    return n - (n >> 1);
+}
+// a[0 .. n) is ordered so that the entries for which `before` holds come first: their number.  Branch-free binary search: the trip
+// count follows from n alone, and every read is at an index < n.
+template <typename T, typename Before> DEV unsigned fo_partition_point(const T* a, unsigned n, Before before) {
+    unsigned lo = 0;
+    for (unsigned step = fo_floor_pow2(n); step > 0; step >>= 1) {
+        const unsigned nxt = lo + step;
+        if (nxt <= n && before(a[nxt - 1])) lo = nxt;
+    }
+    return lo;
+}
 
-// All FO_THREADS threads call these; sh: [FO_THREADS] of T in LDS.  Fixed order, so a float64 sum has the same bits every run.
+// All FO_THREADS threads call it; sh: [FO_THREADS] of T in LDS.  Fixed order (a tree), so a float64 sum has the same bits every run.
 template <typename T> DEV T fo_block_sum(T v, T* sh, int tid) {
     sh[tid] = v;
     __syncthreads();
@@ -30,19 +50,24 @@ template <typename T> DEV T fo_block_sum(T v, T* sh, int tid) {
     __syncthreads();
     return r;
 }
+// Exclusive prefix of v over the threads, *total: the sum over all.  All FO_THREADS threads call it; sh: [FO_WAVES] in LDS, free again
+// when the call returns.  Shuffles inside a wave, then the waves in order: two barriers.  Integers only, so any order gives the same.
 DEV unsigned fo_block_excl_scan(unsigned v, unsigned* sh, int tid, unsigned* total) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < FO_THREADS; off <<= 1) {
-        const unsigned t = tid >= off ? sh[tid - off] : 0u;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    unsigned incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
     }
-    const unsigned incl = sh[tid];
-    *total = sh[FO_THREADS - 1];
+    if (lane == 63) sh[wave] = incl;
     __syncthreads();
-    return incl - v;
+    unsigned before = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < FO_WAVES; ++w) { const unsigned s = sh[w]; before += w < wave ? s : 0u; tot += s; }
+    __syncthreads();
+    *total = tot;
+    return before + incl - v;
 }
 
 template <typename A> __global__ __launch_bounds__(256) void fo_count_kernel(A a) {
@@ -57,7 +82,7 @@ template <typename A> __global__ __launch_bounds__(256) void fo_count_kernel(A a
 
 // one workgroup: counts -> first positions of the workgroups
 template <typename A> __global__ __launch_bounds__(256) void fo_base_kernel(A a) {
-    __shared__ unsigned sh[FO_THREADS];
+    __shared__ unsigned sh[FO_WAVES];
     const int tid = threadIdx.x;
     const unsigned begin = cp_begin(a);
     const unsigned chunk = (a.nblocks + FO_THREADS - 1) / FO_THREADS;

@@ -1,0 +1,81 @@
+// What the two greedy matchers (evaluation.hip: one threshold, a `tp` label per slot; eval_scale.hip: up to 16 thresholds, a flag
+// word per slot) and the open words of eval_scale.hip state once: the float32 IoU, the staging of an image's
+// ground truth with its per-class counters, and the search for a detection's candidate box.  One workgroup of EM_THREADS threads
+// per image.  What thread 0 does with the candidate differs between the two kernels and stays there.
+//
+// Both units are compiled with -ffp-contract=off: the IoU must round like the reference's separate float32 numpy operations
+// (effdet/evaluation/np_box_ops.py), so its operations stay in this order, one rounding each.
+#pragma once
+#include "common.h"
+
+namespace {
+
+constexpr int EM_THREADS = 256;
+constexpr int EM_NO_BOX = 0x7fffffff;                           // the candidate index of a detection whose class has no box
+
+struct EmDet { float x1, y1, x2, y2, area; };
+DEV EmDet em_det(float x1, float y1, float x2, float y2) { return EmDet{x1, y1, x2, y2, (y2 - y1) * (x2 - x1)}; }
+
+// IoU of a detection and the ground-truth box (g0, g1, g2, g3) = (ymin, xmin, ymax, xmax)
+DEV float em_iou(const EmDet& d, float g0, float g1, float g2, float g3) {
+    const float ih = fmaxf(0.f, fminf(d.y2, g2) - fmaxf(d.y1, g0));
+    const float iw = fmaxf(0.f, fminf(d.x2, g3) - fmaxf(d.x1, g1));
+    const float inter = ih * iw;
+    const float area_g = (g2 - g0) * (g3 - g1);
+    return inter / (d.area + area_g - inter);
+}
+
+// All threads call it, once, before the first search.  LDS: seen[C] = 0 (class already had its top-scoring detection), taken[M] = 0,
+// gcls[M] = the 0-based class of box j of image b or -1, and, when gdif is given, gdif[M] = the box is `difficult` (gt_difficult
+// may be null: none is).  Then the counters, by integer atomics (order independent): gt_count[c] += boxes of class c - with gdif,
+// those that are not difficult (object_detection_evaluation.py:132-139) - and gt_imgs[c] += 1 when class c occurs in the image at all.
+DEV void em_stage_gt(const long long* gt_cls, const unsigned char* gt_difficult, int b, int M, int C, int* seen, int* taken, int* gcls,
+                     int* gdif, int* gt_count, int* gt_imgs) {
+    const int tid = threadIdx.x;
+    for (int c = tid; c < C; c += EM_THREADS) seen[c] = 0;
+    for (int j = tid; j < M; j += EM_THREADS) {
+        const long long c1 = gt_cls[(long long)b * M + j];
+        gcls[j] = (c1 >= 1 && c1 <= C) ? (int)(c1 - 1) : -1;
+        if (gdif) gdif[j] = (gt_difficult && gt_difficult[(long long)b * M + j]) ? 1 : 0;
+        taken[j] = 0;
+    }
+    __syncthreads();
+    for (int j = tid; j < M; j += EM_THREADS) {
+        const int c = gcls[j];
+        if (c < 0) continue;
+        if (!gdif || !gdif[j]) atomicAdd(gt_count + c, 1);
+        bool first = true;
+        for (int q = 0; q < j; ++q) first = first && gcls[q] != c;
+        if (first) atomicAdd(gt_imgs + c, 1);
+    }
+}
+
+// All threads call it, with the same detection.  Among the boxes of image b whose class is c: the one with the largest IoU, the
+// lowest index on ties.  The result is valid on thread 0 only: the index (EM_NO_BOX: no box of class c) and *iou (-1 then).
+// red_v, red_i: [EM_THREADS / 64] in LDS.  It contains barriers; the caller's barrier at the end of its round frees red_v / red_i.
+DEV int em_best_box(const EmDet& d, int c, const float* gt_boxes, const int* gcls, int b, int M, float* red_v, int* red_i, float* iou) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float best = -1.f; int bj = EM_NO_BOX;
+    for (int j = tid; j < M; j += EM_THREADS) {
+        if (gcls[j] != c) continue;
+        const float* g = gt_boxes + ((long long)b * M + j) * 4;                 // yxyx
+        const float v = em_iou(d, g[0], g[1], g[2], g[3]);
+        if (v > best) { best = v; bj = j; }                                     // ascending j: first maximum kept
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oj = __shfl_xor(bj, o, 64);
+        if (ov > best || (ov == best && oj < bj)) { best = ov; bj = oj; }
+    }
+    __syncthreads();
+    if (lane == 0) { red_v[wave] = best; red_i[wave] = bj; }
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < EM_THREADS / 64; ++w)
+            if (red_v[w] > best || (red_v[w] == best && red_i[w] < bj)) { best = red_v[w]; bj = red_i[w]; }
+    *iou = best;
+    return bj;
+}
+
+}  // namespace

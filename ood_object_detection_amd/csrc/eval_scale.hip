@@ -9,9 +9,9 @@
 //   append   (score, class, flag word) of the valid slots -> capacity-sized buffers at a cursor that lives on the device, in (image,
 //            slot) order: the images' kept counts come from the match launch, a workgroup adds up the counts of the images before
 //            its own, a one-workgroup launch moves the cursor.  No atomic decides a position.
-//   sort     stable LSD radix sort of 48-bit keys (class, then score descending) with the flag word as payload, 8 bits a pass, every
-//            pass = histogram launch, scan launch, stable scatter launch (the structure of ood_eval.hip).  Equal scores keep their
-//            arrival order; every class is one contiguous segment; invalid entries sort behind the last class.
+//   sort     the stable LSD radix sort of radix_sort.h over 48-bit keys (class, then score descending) with the flag word as payload,
+//            five passes, six beyond 255 classes.  Equal scores keep their arrival order; every class is one contiguous segment;
+//            invalid entries sort behind the last class.
 //   AP       one workgroup per (class, threshold) over its segment: the totals first, then the 2048-entry chunks from the last to the
 //            first: rank and cumulative TP by an integer scan, precision = ctp / rank in float64, the VOC envelope by a reverse
 //            max-scan carried from chunk to chunk (a maximum: exact), AP = sum over the true positives of (recall step) * envelope
@@ -26,6 +26,9 @@
 // index is compared with the live count before the store; the live count is read from the device cursor (grids are sized by the
 // capacity; workgroups beyond the live count exit), so the host never reads anything back.
 #include "common.h"
+#include "compact.h"
+#include "radix_sort.h"
+#include "eval_match.h"
 
 namespace {
 
@@ -33,8 +36,7 @@ typedef unsigned long long u64;
 
 constexpr int ES_THREADS = 256;
 constexpr int ES_WAVES = ES_THREADS / 64;
-constexpr int ES_SORT_ITEMS = 16;
-constexpr int ES_SORT_TILE = ES_THREADS * ES_SORT_ITEMS;          // keys of one workgroup per pass
+static_assert(ES_THREADS == FO_THREADS && ES_THREADS == EM_THREADS, "the shared headers are written for this workgroup size");
 constexpr int ES_AP_ITEMS = 8;
 constexpr int ES_AP_CHUNK = ES_THREADS * ES_AP_ITEMS;             // segment entries of one AP step (counts fit 16 bits)
 constexpr long long ES_MAX_N = 1ll << 24;
@@ -42,42 +44,15 @@ constexpr int ES_MAX_T = 16, ES_MAX_C = 65535;
 constexpr unsigned ES_INVALID = 0x80000000u;
 constexpr int ES_RESULT_HEAD = 8;                                 // 8-byte words before the AP matrix
 
-DEV unsigned es_min(unsigned a, unsigned b) { return a < b ? a : b; }
-DEV unsigned es_popc(u64 m) { return (unsigned)__builtin_popcountll(m); }
-// float32 bits -> key whose unsigned order is the order of the floats
-DEV unsigned es_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : (bits ^ 0x80000000u); }
-DEV unsigned es_floor_pow2(unsigned n) {
-    n |= n >> 1; n |= n >> 2; n |= n >> 4; n |= n >> 8; n |= n >> 16;
-    return n - (n >> 1);
-}
-// a[0 .. n) ascending: the number of entries < k.  The trip count follows from n alone, every read is at an index < n.
-DEV unsigned es_lower_bound(const u64* a, unsigned n, u64 k) {
-    unsigned lo = 0;
-    for (unsigned step = es_floor_pow2(n); step > 0; step >>= 1) {
-        const unsigned nxt = lo + step;
-        if (nxt <= n && a[nxt - 1] < k) lo = nxt;
-    }
-    return lo;
+// keys[0 .. n) sorted: the first entry of class c (the search of compact.h: the trip count follows from n alone, every read is at
+// an index < n).  Class c is the segment [es_class_begin(c), es_class_begin(c + 1)).
+DEV unsigned es_class_begin(const u64* keys, unsigned n, int c) {
+    const u64 k = (u64)c << 32;
+    return fo_partition_point(keys, n, [=](u64 v) { return v < k; });
 }
 
-// ---- workgroup scans: all ES_THREADS threads call them; sh: [ES_WAVES] in LDS, free again when the call returns -----------------
-DEV unsigned es_block_excl_scan(unsigned v, unsigned* sh, int tid, unsigned* total) {
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) sh[wave] = incl;
-    __syncthreads();
-    unsigned before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < ES_WAVES; ++w) { const unsigned s = sh[w]; before += w < wave ? s : 0u; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return before + incl - v;
-}
+// ---- workgroup reductions in float64 order: all ES_THREADS threads call them; sh: [ES_WAVES] in LDS, free again when the call
+// returns.  (The integer scan is fo_block_excl_scan of compact.h.) ------------------------------------------------------------------
 // sum in a fixed order (butterfly inside a wave, then the waves in order): the same bits every run
 template <typename V> DEV V es_block_sum(V v, V* sh, int tid) {
 #pragma unroll
@@ -126,24 +101,8 @@ __global__ __launch_bounds__(ES_THREADS) void es_match_kernel(EsMatch p) {
     int* gdif = gcls + p.M;                          // [M]
     float* red_v = reinterpret_cast<float*>(gdif + p.M);    // [4]
     int* red_i = reinterpret_cast<int*>(red_v + 4);          // [4]
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int c = tid; c < p.C; c += ES_THREADS) seen[c] = 0;
-    for (int j = tid; j < p.M; j += ES_THREADS) {
-        const long long c1 = p.gt_cls[(long long)b * p.M + j];
-        gcls[j] = (c1 >= 1 && c1 <= p.C) ? (int)(c1 - 1) : -1;
-        gdif[j] = (p.gt_difficult && p.gt_difficult[(long long)b * p.M + j]) ? 1 : 0;
-        taken[j] = 0;
-    }
-    __syncthreads();
-    // ground truth: instances that are not difficult; images in which the class occurs at all (object_detection_evaluation.py:132-139)
-    for (int j = tid; j < p.M; j += ES_THREADS) {
-        const int c = gcls[j];
-        if (c < 0) continue;
-        if (!gdif[j]) atomicAdd(p.gt_count + c, 1);
-        bool first = true;
-        for (int q = 0; q < j; ++q) first = first && gcls[q] != c;
-        if (first) atomicAdd(p.gt_imgs + c, 1);
-    }
+    const int b = blockIdx.x, tid = threadIdx.x;
+    em_stage_gt(p.gt_cls, p.gt_difficult, b, p.M, p.C, seen, taken, gcls, gdif, p.gt_count, p.gt_imgs);      // difficult boxes: not in gt_count
     const int n = min(p.det_count[b], p.max_det);
     int kept = 0, nans = 0;                          // thread 0's
     for (int i = 0; i < p.max_det; ++i) {
@@ -154,31 +113,10 @@ __global__ __launch_bounds__(ES_THREADS) void es_match_kernel(EsMatch p) {
         const int c = (int)d[5] - 1;
         if (score != score) ++nans;
         if (!(y1 < y2 && x1 < x2) || c < 0 || c >= p.C || score != score) { if (tid == 0) *out = ES_INVALID; continue; }     // uniform
-        const float area_d = (y2 - y1) * (x2 - x1);
-        float best = -1.f; int bj = 0x7fffffff;
-        for (int j = tid; j < p.M; j += ES_THREADS) {
-            if (gcls[j] != c) continue;
-            const float* g = p.gt_boxes + ((long long)b * p.M + j) * 4;             // yxyx
-            const float ih = fmaxf(0.f, fminf(y2, g[2]) - fmaxf(y1, g[0]));
-            const float iw = fmaxf(0.f, fminf(x2, g[3]) - fmaxf(x1, g[1]));
-            const float inter = ih * iw;
-            const float area_g = (g[2] - g[0]) * (g[3] - g[1]);
-            const float iou = inter / (area_d + area_g - inter);
-            if (iou > best) { best = iou; bj = j; }                                 // ascending j: first maximum kept
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o, 64);
-            const int oj = __shfl_xor(bj, o, 64);
-            if (ov > best || (ov == best && oj < bj)) { best = ov; bj = oj; }
-        }
-        __syncthreads();
-        if (lane == 0) { red_v[wave] = best; red_i[wave] = bj; }
-        __syncthreads();
+        float best;
+        const int bj = em_best_box(em_det(x1, y1, x2, y2), c, p.gt_boxes, gcls, b, p.M, red_v, red_i, &best);
         if (tid == 0) {
-            for (int w = 1; w < ES_WAVES; ++w)
-                if (red_v[w] > best || (red_v[w] == best && red_i[w] < bj)) { best = red_v[w]; bj = red_i[w]; }
-            const bool has_gt = bj != 0x7fffffff;
+            const bool has_gt = bj != EM_NO_BOX;
             unsigned word = 0, reach = 0;            // reach: thresholds the candidate's IoU reaches
             if (has_gt) {
                 for (int t = 0; t < p.T; ++t) reach |= (best >= p.thr[t] ? 1u : 0u) << t;
@@ -215,14 +153,14 @@ __global__ __launch_bounds__(ES_THREADS) void es_append_write_kernel(EsAppend a)
     const int b = blockIdx.x, tid = threadIdx.x;
     unsigned before = 0;
     for (int k = tid; k < b; k += ES_THREADS) before += (unsigned)a.kept[k];
-    unsigned pos = es_min(a.state[0], a.capacity) + es_block_sum<unsigned>(before, shu, tid);
+    unsigned pos = fo_min(a.state[0], a.capacity) + es_block_sum<unsigned>(before, shu, tid);
     for (int i0 = 0; i0 < a.max_det; i0 += ES_THREADS) {
         const int i = i0 + tid;
         const long long slot = (long long)b * a.max_det + i;
         const unsigned f = i < a.max_det ? a.flags[slot] : ES_INVALID;
         const bool keep = !(f & ES_INVALID);
         unsigned total;
-        const unsigned p = pos + es_block_excl_scan(keep ? 1u : 0u, shu, tid, &total);
+        const unsigned p = pos + fo_block_excl_scan(keep ? 1u : 0u, shu, tid, &total);
         if (keep && p < a.capacity) {                                     // beyond the capacity: counted by the cursor launch
             float v = a.det[slot * 6 + 4];
             if (v == 0.f) v = 0.f;                                        // -0.0 is stored as +0.0: the two tie
@@ -244,7 +182,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_append_cursor_kernel(EsAppend a
     kept = es_block_sum<unsigned>(kept, shu, tid);
     nans = es_block_sum<unsigned>(nans, shu, tid);
     if (tid == 0) {
-        const u64 end = (u64)es_min(a.state[0], a.capacity) + kept;
+        const u64 end = (u64)fo_min(a.state[0], a.capacity) + kept;
         if (end > a.capacity) {
             const u64 lost = (u64)a.state[1] + (end - a.capacity);
             a.state[1] = lost > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)lost;
@@ -255,11 +193,15 @@ __global__ __launch_bounds__(ES_THREADS) void es_append_cursor_kernel(EsAppend a
     }
 }
 
-// ---- sort ------------------------------------------------------------------------------------------------------------------------
-struct EsSort {
+// ---- sort: the pass descriptor of radix_sort.h (one problem; W2: a second payload word, the open word) -----------------------------
+template <bool W2> struct EsItem { u64 key; unsigned val; };
+template <> struct EsItem<true> { u64 key; unsigned val, open; };
+template <bool W2> struct EsSort {
+    typedef u64 Key;
+    typedef EsItem<W2> Item;
     const float* scores; const int* classes; const unsigned* flags;      // the first pass reads these
     const u64* src_k; const unsigned* src_v; u64* dst_k; unsigned* dst_v;
-    const unsigned* open; const unsigned* src_w; unsigned* dst_w;         // a second payload word (the W2 scatter only)
+    const unsigned* open; const unsigned* src_w; unsigned* dst_w;         // W2 only
     const unsigned* cursor; long long n_host;                             // live count: n_host, or min(*cursor, capacity) when n_host < 0
     unsigned* hist; unsigned* totals;
     unsigned capacity, tiles;                                             // tiles by capacity: the row pitch of hist
@@ -267,113 +209,32 @@ struct EsSort {
 };
 
 DEV unsigned es_live(const unsigned* cursor, long long n_host, unsigned capacity) {
-    return n_host >= 0 ? (unsigned)n_host : es_min(cursor[0], capacity);
+    return n_host >= 0 ? (unsigned)n_host : fo_min(cursor[0], capacity);
+}
+template <bool W2> DEV RsProblem rs_problem(const EsSort<W2>& s, unsigned) {
+    return RsProblem{es_live(s.cursor, s.n_host, s.capacity), s.hist, s.totals, s.tiles};
 }
 // (class << 32) | ~key(score): ascending = class, then score descending.  Invalid entries (flag bit 31, class outside 0..C-1, NaN
 // score) get class C: behind every class.
-DEV void es_sort_load(const EsSort& s, unsigned i, u64* key, unsigned* val) {
-    if (!s.first) { *key = s.src_k[i]; *val = s.src_v[i]; return; }
+template <bool W2> DEV u64 rs_key(const EsSort<W2>& s, unsigned, unsigned i) {
+    if (!s.first) return s.src_k[i];
     const unsigned f = s.flags[i];
     const int c = s.classes[i];
     float v = s.scores[i];
     const bool ok = !(f & ES_INVALID) && c >= 0 && c < s.C && v == v;
     if (v == 0.f) v = 0.f;
-    *key = ((u64)(ok ? (unsigned)c : (unsigned)s.C) << 32) | (u64)(~es_key(__float_as_uint(v)));
-    *val = f;
+    return ((u64)(ok ? (unsigned)c : (unsigned)s.C) << 32) | (u64)(~fo_key(__float_as_uint(v)));
 }
-
-__global__ __launch_bounds__(ES_THREADS) void es_sort_hist_kernel(EsSort s) {
-    __shared__ unsigned h[256];
-    const int tid = threadIdx.x;
-    const unsigned n = es_live(s.cursor, s.n_host, s.capacity), tile = blockIdx.x;
-    if (tile >= (n + ES_SORT_TILE - 1) / ES_SORT_TILE) return;          // the same for the whole workgroup
-    h[tid] = 0;
-    __syncthreads();
-    for (int r = 0; r < ES_SORT_ITEMS; ++r) {
-        const unsigned i = tile * ES_SORT_TILE + r * ES_THREADS + tid;
-        if (i < n) {
-            u64 k; unsigned v;
-            es_sort_load(s, i, &k, &v);
-            atomicAdd(&h[(unsigned)(k >> s.shift) & 255u], 1u);          // integer counts in LDS: order independent
-        }
-    }
-    __syncthreads();
-    s.hist[(unsigned)tid * s.tiles + tile] = h[tid];
+template <bool W2> DEV EsItem<W2> rs_load(const EsSort<W2>& s, unsigned, unsigned i) {
+    EsItem<W2> e;
+    e.key = rs_key(s, 0, i);
+    e.val = s.first ? s.flags[i] : s.src_v[i];
+    if constexpr (W2) e.open = s.first ? s.open[i] : s.src_w[i];
+    return e;
 }
-
-// workgroup d: exclusive prefix of digit d's counts over the live tiles (in place), and the digit's total
-__global__ __launch_bounds__(ES_THREADS) void es_sort_scan_kernel(EsSort s) {
-    __shared__ unsigned sh[ES_WAVES];
-    const int tid = threadIdx.x;
-    const unsigned n = es_live(s.cursor, s.n_host, s.capacity), ntiles = (n + ES_SORT_TILE - 1) / ES_SORT_TILE;
-    unsigned* row = s.hist + (unsigned)blockIdx.x * s.tiles;
-    const unsigned chunk = (ntiles + ES_THREADS - 1) / ES_THREADS;
-    const unsigned lo = es_min((unsigned)tid * chunk, ntiles), hi = es_min(lo + chunk, ntiles);
-    unsigned sum = 0;
-    for (unsigned k = lo; k < hi; ++k) sum += row[k];
-    unsigned total;
-    unsigned run = es_block_excl_scan(sum, sh, tid, &total);
-    for (unsigned k = lo; k < hi; ++k) { const unsigned c = row[k]; row[k] = run; run += c; }
-    if (tid == 0) s.totals[blockIdx.x] = total;
-}
-
-// Stable scatter of one tile.  Wave w owns entries [w * 1024, (w + 1) * 1024) of the tile, 64 consecutive ones per round.  An entry's
-// rank among the equal digits of its wave = the wave's running count of the digit + the equal digits in lower lanes (ballots); the
-// waves' counts are then prefixed per digit on top of (digits below in the array) + (this digit in earlier tiles).
-template <bool W2> __global__ __launch_bounds__(ES_THREADS) void es_sort_scatter_kernel(EsSort s) {
-    __shared__ unsigned wcnt[ES_WAVES][256];
-    __shared__ unsigned sh[ES_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned n = es_live(s.cursor, s.n_host, s.capacity), tile = blockIdx.x;
-    if (tile >= (n + ES_SORT_TILE - 1) / ES_SORT_TILE) return;
-    for (int w = 0; w < ES_WAVES; ++w) wcnt[w][tid] = 0;
-    unsigned total;
-    const unsigned digit_first = es_block_excl_scan(s.totals[tid], sh, tid, &total) + s.hist[(unsigned)tid * s.tiles + tile];
-    // (the scan's barriers also publish the zeroed counters)
-    const u64 below = (1ull << lane) - 1ull;
-    const unsigned seg = tile * ES_SORT_TILE + (unsigned)wave * (64 * ES_SORT_ITEMS);
-    u64 key[ES_SORT_ITEMS];
-    unsigned val[ES_SORT_ITEMS], rank[ES_SORT_ITEMS], val2[W2 ? ES_SORT_ITEMS : 1];
-#pragma unroll
-    for (int r = 0; r < ES_SORT_ITEMS; ++r) {
-        const unsigned i = seg + r * 64 + lane;
-        const bool valid = i < n;
-        u64 k = ~0ull; unsigned v = 0;
-        if (valid) es_sort_load(s, i, &k, &v);
-        if constexpr (W2) val2[r] = valid ? (s.first ? s.open[i] : s.src_w[i]) : 0u;
-        const unsigned d = (unsigned)(k >> s.shift) & 255u;
-        u64 same = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool on = (d >> bit) & 1u;
-            const u64 bal = __ballot(on);
-            same &= on ? bal : ~bal;
-        }
-        const unsigned lower = es_popc(same & below);
-        const unsigned prev = valid ? wcnt[wave][d] : 0u;
-        __builtin_amdgcn_wave_barrier();
-        if (valid && lower == 0) wcnt[wave][d] = prev + es_popc(same);     // one lane per digit present in the round
-        __builtin_amdgcn_wave_barrier();
-        key[r] = k; val[r] = v;
-        rank[r] = prev + lower;
-    }
-    __syncthreads();
-    {   // thread d: the waves' counts of digit d -> first positions
-        unsigned run = digit_first;
-        for (int w = 0; w < ES_WAVES; ++w) { const unsigned c = wcnt[w][tid]; wcnt[w][tid] = run; run += c; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ES_SORT_ITEMS; ++r) {
-        const unsigned i = seg + r * 64 + lane;
-        if (i < n) {
-            const unsigned p = wcnt[wave][(unsigned)(key[r] >> s.shift) & 255u] + rank[r];
-            if (p < n) {
-                s.dst_k[p] = key[r]; s.dst_v[p] = val[r];
-                if constexpr (W2) s.dst_w[p] = val2[r];
-            }
-        }
-    }
+template <bool W2> DEV void rs_store(const EsSort<W2>& s, unsigned, unsigned p, const EsItem<W2>& e) {
+    s.dst_k[p] = e.key; s.dst_v[p] = e.val;
+    if constexpr (W2) s.dst_w[p] = e.open;
 }
 
 // ---- average precision -----------------------------------------------------------------------------------------------------------
@@ -391,7 +252,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_ap_kernel(EsAp a) {
     __shared__ double shd[ES_WAVES];
     const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
     const unsigned n = es_live(a.state, a.n_host, a.capacity);
-    const unsigned s = es_lower_bound(a.keys, n, (u64)c << 32), e = es_lower_bound(a.keys, n, (u64)(c + 1) << 32);
+    const unsigned s = es_class_begin(a.keys, n, c), e = es_class_begin(a.keys, n, c + 1);
     const int ng = a.gt_count[c];
     const unsigned tp_bit = 1u << t, ig_bit = 1u << (16 + t);
     double acc = 0.0;
@@ -420,7 +281,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_ap_kernel(EsAp a) {
                 cnt += ((f[r] & ig_bit) ? 0u : 1u) + ((f[r] & tp_bit) ? 0x10000u : 0u);
             }
             unsigned total;
-            const unsigned ex = es_block_excl_scan(cnt, shu, tid, &total);
+            const unsigned ex = fo_block_excl_scan(cnt, shu, tid, &total);
             rem_ni -= total & 0xFFFFu; rem_tp -= total >> 16;             // now: the counts in front of this chunk
             unsigned rank = rem_ni + (ex & 0xFFFFu), ctp = rem_tp + (ex >> 16);
             double prec[ES_AP_ITEMS], step[ES_AP_ITEMS];
@@ -484,13 +345,13 @@ __global__ __launch_bounds__(ES_THREADS) void es_open_words_kernel(EsOpenWords p
             live = !(p.flags[slot] & ES_INVALID) && c1 >= 1 && c1 < p.U;
             x1 = d[0]; y1 = d[1]; x2 = d[2]; y2 = d[3];
         }
-        const float area_d = (y2 - y1) * (x2 - x1);
+        const EmDet d = em_det(x1, y1, x2, y2);
         float best = -__builtin_inff();
         for (int j0 = 0; j0 < p.M; j0 += ES_OPEN_CHUNK) {             // uniform trip count
             const int j = j0 + tid;
             const bool unk = j < p.M && p.gt_cls[(long long)b * p.M + j] == (long long)p.U;
             unsigned cnt;
-            const unsigned at = es_block_excl_scan(unk ? 1u : 0u, shu, tid, &cnt);      // at < ES_OPEN_CHUNK
+            const unsigned at = fo_block_excl_scan(unk ? 1u : 0u, shu, tid, &cnt);      // at < ES_OPEN_CHUNK
             if (unk) {
                 const float* g = p.gt_boxes + ((long long)b * p.M + j) * 4;
                 box[at][0] = g[0]; box[at][1] = g[1]; box[at][2] = g[2]; box[at][3] = g[3];
@@ -498,12 +359,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_open_words_kernel(EsOpenWords p
             __syncthreads();
             if (live)
                 for (unsigned k = 0; k < cnt; ++k) {
-                    const float g0 = box[k][0], g1 = box[k][1], g2 = box[k][2], g3 = box[k][3];      // yxyx
-                    const float ih = fmaxf(0.f, fminf(y2, g2) - fmaxf(y1, g0));
-                    const float iw = fmaxf(0.f, fminf(x2, g3) - fmaxf(x1, g1));
-                    const float inter = ih * iw;
-                    const float area_g = (g2 - g0) * (g3 - g1);
-                    const float iou = inter / (area_d + area_g - inter);
+                    const float iou = em_iou(d, box[k][0], box[k][1], box[k][2], box[k][3]);      // yxyx
                     if (iou > best) best = iou;
                 }
             __syncthreads();                                          // the chunk is free again
@@ -546,7 +402,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_open_counts_kernel(EsOpenCounts
     __shared__ unsigned sh_pos;
     const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
     const unsigned n = es_live(a.state, a.n_host, a.capacity);
-    const unsigned s = es_lower_bound(a.keys, n, (u64)c << 32), e = es_lower_bound(a.keys, n, (u64)(c + 1) << 32);
+    const unsigned s = es_class_begin(a.keys, n, c), e = es_class_begin(a.keys, n, c + 1);
     const int ng = a.gt_count[c];
     const unsigned tp_bit = 1u << t, ig_bit = 1u << (16 + t);
     unsigned n_det, tp, open_total;
@@ -579,7 +435,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_open_counts_kernel(EsOpenCounts
                     cnt += (f[r] & tp_bit) ? 1u : 0u;
                 }
                 unsigned total;
-                unsigned run = seen + es_block_excl_scan(cnt, shu, tid, &total);
+                unsigned run = seen + fo_block_excl_scan(cnt, shu, tid, &total);
                 if (run < want && want <= run + cnt) {                    // one thread of one chunk
 #pragma unroll
                     for (int r = 0; r < ES_AP_ITEMS; ++r) {
@@ -639,7 +495,7 @@ bool es_layout(long long capacity, int C, EsLayout* L, bool open = false) {
     if (capacity < 1 || capacity > ES_MAX_N || C < 1 || C > ES_MAX_C) return false;
     long long off = 0;
     auto take = [&off](long long bytes) { const long long o = off; off += (bytes + 255) & ~255ll; return o; };
-    L->tiles = (unsigned)((capacity + ES_SORT_TILE - 1) / ES_SORT_TILE);
+    L->tiles = (unsigned)((capacity + RS_TILE - 1) / RS_TILE);
     L->passes = C <= 255 ? 5 : 6;                                         // 4 score digits, then the class (C itself is a key)
     for (int k = 0; k < 2; ++k) { L->keys[k] = take(capacity * 8); L->vals[k] = take(capacity * 4); }
     for (int k = 0; k < 2; ++k) L->vals2[k] = open ? take(capacity * 4) : 0;
@@ -649,10 +505,30 @@ bool es_layout(long long capacity, int C, EsLayout* L, bool open = false) {
     return true;
 }
 
+// the passes of the sort: entries -> buffers 0 -> 1 -> 0 ...; the grid by n_host, or by the capacity when the count is on the device
+template <bool W2> void es_sort(hipStream_t st, const float* scores, const int* classes, const unsigned* flags, const unsigned* open,
+                                const unsigned* state, long long n_host, long long capacity, int C, char* ws, const EsLayout& L) {
+    EsSort<W2> s;
+    s.scores = scores; s.classes = classes; s.flags = flags; s.open = open;
+    s.cursor = state; s.n_host = n_host;
+    s.hist = reinterpret_cast<unsigned*>(ws + L.hist); s.totals = reinterpret_cast<unsigned*>(ws + L.totals);
+    s.capacity = (unsigned)capacity; s.tiles = L.tiles; s.C = C;
+    const unsigned grid = n_host < 0 ? L.tiles : (unsigned)((n_host + RS_TILE - 1) / RS_TILE);
+    for (int pass = 0; pass < L.passes && grid > 0; ++pass) {
+        const int d = pass & 1;
+        s.shift = 8 * pass; s.first = pass == 0;
+        s.src_k = reinterpret_cast<const u64*>(ws + L.keys[1 - d]); s.src_v = reinterpret_cast<const unsigned*>(ws + L.vals[1 - d]);
+        s.dst_k = reinterpret_cast<u64*>(ws + L.keys[d]); s.dst_v = reinterpret_cast<unsigned*>(ws + L.vals[d]);
+        s.src_w = W2 ? reinterpret_cast<const unsigned*>(ws + L.vals2[1 - d]) : nullptr;
+        s.dst_w = W2 ? reinterpret_cast<unsigned*>(ws + L.vals2[d]) : nullptr;
+        rs_sort_pass(st, s, grid, 1);
+    }
+}
+
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
-extern "C" int effdet_eval_scale_sort_tile(void) { return ES_SORT_TILE; }
+extern "C" int effdet_eval_scale_sort_tile(void) { return RS_TILE; }
 
 extern "C" int effdet_eval_match_multi(void* stream, const float* det, const int* det_count, const float* gt_boxes,
                                        const long long* gt_cls, const unsigned char* gt_difficult, int B, int max_det, int M,
@@ -735,28 +611,13 @@ static int es_sorted_run(void* stream, const float* scores, const int* classes, 
         return EFFDET_EINVAL;      // workspace and result must be 8-byte aligned
     char* ws = reinterpret_cast<char*>(workspace);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    EsSort s;
-    s.scores = scores; s.classes = classes; s.flags = flags; s.open = open;
-    s.cursor = state; s.n_host = n < 0 ? -1 : n;
-    s.hist = reinterpret_cast<unsigned*>(ws + L.hist); s.totals = reinterpret_cast<unsigned*>(ws + L.totals);
-    s.capacity = (unsigned)capacity; s.tiles = L.tiles; s.C = num_classes;
-    const unsigned grid = n < 0 ? L.tiles : (unsigned)((n + ES_SORT_TILE - 1) / ES_SORT_TILE);
-    for (int pass = 0; pass < L.passes && grid > 0; ++pass) {
-        const int d = pass & 1;                                           // in -> 0 -> 1 -> 0 ...
-        s.shift = 8 * pass; s.first = pass == 0;
-        s.src_k = reinterpret_cast<const u64*>(ws + L.keys[1 - d]); s.src_v = reinterpret_cast<const unsigned*>(ws + L.vals[1 - d]);
-        s.dst_k = reinterpret_cast<u64*>(ws + L.keys[d]); s.dst_v = reinterpret_cast<unsigned*>(ws + L.vals[d]);
-        s.src_w = open ? reinterpret_cast<const unsigned*>(ws + L.vals2[1 - d]) : nullptr;
-        s.dst_w = open ? reinterpret_cast<unsigned*>(ws + L.vals2[d]) : nullptr;
-        hipLaunchKernelGGL(es_sort_hist_kernel, dim3(grid), dim3(ES_THREADS), 0, st, s);
-        hipLaunchKernelGGL(es_sort_scan_kernel, dim3(256), dim3(ES_THREADS), 0, st, s);
-        if (open) hipLaunchKernelGGL(es_sort_scatter_kernel<true>, dim3(grid), dim3(ES_THREADS), 0, st, s);
-        else hipLaunchKernelGGL(es_sort_scatter_kernel<false>, dim3(grid), dim3(ES_THREADS), 0, st, s);
-    }
+    const long long n_host = n < 0 ? -1 : n;
+    if (open) es_sort<true>(st, scores, classes, flags, open, state, n_host, capacity, num_classes, ws, L);
+    else es_sort<false>(st, scores, classes, flags, nullptr, state, n_host, capacity, num_classes, ws, L);
     const int last = (L.passes - 1) & 1;
     EsAp a;
     a.keys = reinterpret_cast<const u64*>(ws + L.keys[last]); a.flags = reinterpret_cast<const unsigned*>(ws + L.vals[last]);
-    a.state = state; a.n_host = s.n_host; a.capacity = (unsigned)capacity;
+    a.state = state; a.n_host = n_host; a.capacity = (unsigned)capacity;
     a.T = num_thresholds; a.C = num_classes;
     a.gt_count = gt_count; a.gt_imgs = gt_imgs; a.correct = correct_imgs;
     a.result = reinterpret_cast<u64*>(result);
@@ -764,7 +625,7 @@ static int es_sorted_run(void* stream, const float* scores, const int* classes, 
     if (open) {
         EsOpenCounts o;
         o.keys = a.keys; o.flags = a.flags; o.open = reinterpret_cast<const unsigned*>(ws + L.vals2[last]);
-        o.state = state; o.n_host = s.n_host; o.capacity = (unsigned)capacity;
+        o.state = state; o.n_host = n_host; o.capacity = (unsigned)capacity;
         o.T = num_thresholds; o.C = num_classes; o.level = level;
         o.gt_count = gt_count;
         o.mats = reinterpret_cast<long long*>(result) + ES_RESULT_HEAD + 2ll * num_thresholds * num_classes + 2ll * num_classes;

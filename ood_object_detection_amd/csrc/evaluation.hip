@@ -12,10 +12,12 @@
 //                       envelope is a max over the later ranks, and recall advances by 1/num_gt at every true positive.
 //                       O(n^2) pair counting - the loop evaluates <= 100 detections x a handful of images per iteration.
 #include "common.h"
+#include "eval_match.h"
 
 namespace {
 
 constexpr int ET = 256;
+static_assert(ET == EM_THREADS, "the matcher parts of eval_match.h are written for this workgroup size");
 
 struct MatchArgs {
     const float* det; const int* det_count; const float* gt_boxes; const long long* gt_cls;
@@ -30,23 +32,8 @@ __global__ __launch_bounds__(ET) void eval_match_kernel(MatchArgs p) {
     int* gcls = taken + p.M;                         // [M] 0-based class or -1
     float* red_v = reinterpret_cast<float*>(gcls + p.M);   // [4]
     int* red_i = reinterpret_cast<int*>(red_v + 4);         // [4]
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int c = tid; c < p.C; c += ET) seen[c] = 0;
-    for (int j = tid; j < p.M; j += ET) {
-        const long long c1 = p.gt_cls[(long long)b * p.M + j];
-        gcls[j] = (c1 >= 1 && c1 <= p.C) ? (int)(c1 - 1) : -1;
-        taken[j] = 0;
-    }
-    __syncthreads();
-    // ground-truth instance / image counters
-    for (int j = tid; j < p.M; j += ET) {
-        const int c = gcls[j];
-        if (c < 0) continue;
-        atomicAdd(p.gt_count + c, 1);
-        bool first = true;
-        for (int q = 0; q < j; ++q) first = first && gcls[q] != c;
-        if (first) atomicAdd(p.gt_imgs + c, 1);
-    }
+    const int b = blockIdx.x, tid = threadIdx.x;
+    em_stage_gt(p.gt_cls, nullptr, b, p.M, p.C, seen, taken, gcls, nullptr, p.gt_count, p.gt_imgs);      // no `difficult` flags here
     const int n = min(p.det_count[b], p.max_det);
     for (int i = 0; i < p.max_det; ++i) {
         int* out = p.tp + (long long)b * p.max_det + i;
@@ -55,32 +42,11 @@ __global__ __launch_bounds__(ET) void eval_match_kernel(MatchArgs p) {
         const float x1 = d[0], y1 = d[1], x2 = d[2], y2 = d[3];
         const int c = (int)d[5] - 1;
         if (!(y1 < y2 && x1 < x2) || c < 0 || c >= p.C) { if (tid == 0) *out = -1; continue; }      // uniform
-        const float area_d = (y2 - y1) * (x2 - x1);
-        float best = -1.f; int bj = 0x7fffffff;
-        for (int j = tid; j < p.M; j += ET) {
-            if (gcls[j] != c) continue;
-            const float* g = p.gt_boxes + ((long long)b * p.M + j) * 4;             // yxyx
-            const float ih = fmaxf(0.f, fminf(y2, g[2]) - fmaxf(y1, g[0]));
-            const float iw = fmaxf(0.f, fminf(x2, g[3]) - fmaxf(x1, g[1]));
-            const float inter = ih * iw;
-            const float area_g = (g[2] - g[0]) * (g[3] - g[1]);
-            const float iou = inter / (area_d + area_g - inter);
-            if (iou > best) { best = iou; bj = j; }                                 // ascending j: first maximum kept
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o, 64);
-            const int oj = __shfl_xor(bj, o, 64);
-            if (ov > best || (ov == best && oj < bj)) { best = ov; bj = oj; }
-        }
-        __syncthreads();
-        if (lane == 0) { red_v[wave] = best; red_i[wave] = bj; }
-        __syncthreads();
+        float best;
+        const int bj = em_best_box(em_det(x1, y1, x2, y2), c, p.gt_boxes, gcls, b, p.M, red_v, red_i, &best);
         if (tid == 0) {
-            for (int w = 1; w < ET / 64; ++w)
-                if (red_v[w] > best || (red_v[w] == best && red_i[w] < bj)) { best = red_v[w]; bj = red_i[w]; }
             int label = 0;
-            const bool has_gt = bj != 0x7fffffff;
+            const bool has_gt = bj != EM_NO_BOX;
             if (has_gt && best >= p.thr && !taken[bj]) { label = 1; taken[bj] = 1; }
             *out = label;
             if (!seen[c]) {                                                          // top-scoring detection of class c

@@ -3,8 +3,8 @@
 //
 //   append   [B, K] score matrix -> one side's flat buffer, in (b, j) order from a cursor that lives on the device: the ordered
 //            compaction of compact.h, whose base launch also moves the cursor.  No atomic decides a position.
-//   sort     both sides through the same launches (a two-entry problem table, blockIdx.y = side): LSD radix sort of the 32-bit
-//            order-preserving keys, 8 bits a pass, every pass = histogram launch, scan launch, stable scatter launch.
+//   sort     both sides through the same launches (a two-entry problem table, blockIdx.y = side): the LSD radix sort of
+//            radix_sort.h over the 32-bit order-preserving keys, four passes, no payload.
 //   metrics  everything follows from the two sorted arrays by binary search: one launch of per-workgroup partials (uint64 pair
 //            counts, float64 AUPR terms), one workgroup that adds them in a fixed order and fills the result block.
 //
@@ -13,20 +13,14 @@
 // (grids are sized by the capacities; workgroups beyond the live count exit), so the host never reads anything back.
 #include "common.h"
 #include "compact.h"
-
-// all lanes of a wave have issued the LDS accesses before this point (the CPU model of tools/simt_model defines its own)
-#ifndef OE_WAVE_SYNC
-#define OE_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
-#endif
+#include "radix_sort.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
 constexpr int OE_THREADS = 256;
-static_assert(OE_THREADS == FO_THREADS, "the reductions and the compaction of compact.h are written for this workgroup size");
-constexpr int OE_SORT_ITEMS = 16;
-constexpr int OE_SORT_TILE = OE_THREADS * OE_SORT_ITEMS;          // keys of one workgroup per pass
+static_assert(OE_THREADS == FO_THREADS, "the reductions, the compaction and the sort of the shared headers are written for this workgroup size");
 constexpr int OE_MET_ITEMS = 8;
 constexpr int OE_MET_TILE = OE_THREADS * OE_MET_ITEMS;            // sorted scores of one workgroup
 constexpr long long OE_MAX_SCORES = 1ll << 27;                    // per side, and per append call
@@ -54,7 +48,7 @@ bool oe_layout(long long cap_pos, long long cap_neg, OeLayout* L) {
     L->append_counts = take(OE_APPEND_MAX_BLOCKS * 4);
     const long long caps[2] = {cap_pos, cap_neg};
     for (int s = 0; s < 2; ++s) {
-        L->tiles[s] = (unsigned)((caps[s] + OE_SORT_TILE - 1) / OE_SORT_TILE);
+        L->tiles[s] = (unsigned)((caps[s] + RS_TILE - 1) / RS_TILE);
         L->mblocks[s] = (unsigned)((caps[s] + OE_MET_TILE - 1) / OE_MET_TILE);
         L->keys_a[s] = take(caps[s] * 4);
         L->keys_b[s] = take(caps[s] * 4);
@@ -68,27 +62,10 @@ bool oe_layout(long long cap_pos, long long cap_neg, OeLayout* L) {
     return true;
 }
 
-// ---- small device helpers ----------------------------------------------------------------------------------------------------
-// float32 bits -> key whose unsigned order is the order of the floats, and back
-DEV unsigned oe_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : (bits ^ 0x80000000u); }
-DEV unsigned oe_unkey(unsigned key) { return (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key; }
-// largest power of two <= n (0 for 0)
-DEV unsigned oe_floor_pow2(unsigned n) {
-    n |= n >> 1; n |= n >> 2; n |= n >> 4; n |= n >> 8; n |= n >> 16;
-    return n - (n >> 1);
-}
-// a[0 .. n) holds float32 bits in ascending order: the number of entries whose key is < k (strict == 0) or <= k (strict != 0).
-// The trip count follows from n alone, and every read is at an index < n.
+// a[0 .. n) holds float32 bits in ascending order: the number of entries whose key is < k (upper == 0) or <= k (upper != 0), by
+// the search of compact.h: the trip count follows from n alone, and every read is at an index < n
 DEV unsigned oe_bound(const unsigned* a, unsigned n, unsigned k, int upper) {
-    unsigned lo = 0;
-    for (unsigned step = oe_floor_pow2(n); step > 0; step >>= 1) {
-        const unsigned nxt = lo + step;
-        if (nxt <= n) {
-            const unsigned v = oe_key(a[nxt - 1]);
-            if (upper ? v <= k : v < k) lo = nxt;
-        }
-    }
-    return lo;
+    return fo_partition_point(a, n, [=](unsigned bits) { const unsigned v = fo_key(bits); return upper ? v <= k : v < k; });
 }
 
 // ---- append ------------------------------------------------------------------------------------------------------------------
@@ -148,106 +125,31 @@ __global__ __launch_bounds__(256) void oe_append_write_kernel(OeAppend a) {
     if (nan) atomicOr(&a.state[1], OE_SIDE_NAN);                        // an OR of a flag bit: no order to depend on
 }
 
-// ---- sort --------------------------------------------------------------------------------------------------------------------
+// ---- sort: the pass descriptor of radix_sort.h --------------------------------------------------------------------------------
 struct OeSortSide {
     const unsigned* src; unsigned* dst;
     const unsigned* cursor;                     // live count = min(*cursor, capacity)
     unsigned* hist; unsigned* totals;
     unsigned capacity, tiles;                   // tiles by capacity: the row pitch of hist
 };
-struct OeSortTable { OeSortSide s[2]; int shift, first, last; };      // first: src holds float bits; last: dst receives float bits
+struct OeItem { unsigned key; };               // keys only: every metric is a function of the two sorted multisets
+struct OeSort {
+    typedef unsigned Key;
+    typedef OeItem Item;
+    OeSortSide s[2];
+    int shift, first, last;                     // first: src holds float bits; last: dst receives float bits
+};
 
-DEV unsigned oe_sort_load(const OeSortSide& S, const OeSortTable& t, unsigned i) {
-    const unsigned v = S.src[i];
-    return t.first ? oe_key(v) : v;
+DEV RsProblem rs_problem(const OeSort& t, unsigned side) {
+    const OeSortSide& S = t.s[side];
+    return RsProblem{fo_min(S.cursor[0], S.capacity), S.hist, S.totals, S.tiles};
 }
-
-__global__ __launch_bounds__(256) void oe_sort_hist_kernel(OeSortTable t) {
-    __shared__ unsigned h[256];
-    const OeSortSide S = t.s[blockIdx.y];
-    const int tid = threadIdx.x;
-    const unsigned n = fo_min(S.cursor[0], S.capacity), tile = blockIdx.x;
-    if (tile >= (n + OE_SORT_TILE - 1) / OE_SORT_TILE) return;          // the same for the whole workgroup
-    h[tid] = 0;
-    __syncthreads();
-    for (int r = 0; r < OE_SORT_ITEMS; ++r) {
-        const unsigned i = tile * OE_SORT_TILE + r * OE_THREADS + tid;
-        if (i < n) atomicAdd(&h[(oe_sort_load(S, t, i) >> t.shift) & 255u], 1u);      // integer counts in LDS: order independent
-    }
-    __syncthreads();
-    S.hist[(unsigned)tid * S.tiles + tile] = h[tid];
+DEV unsigned rs_key(const OeSort& t, unsigned side, unsigned i) {
+    const unsigned v = t.s[side].src[i];
+    return t.first ? fo_key(v) : v;
 }
-
-// workgroup d of a side: exclusive prefix of digit d's counts over the live tiles (in place), and the digit's total
-__global__ __launch_bounds__(256) void oe_sort_scan_kernel(OeSortTable t) {
-    __shared__ unsigned sh[OE_THREADS];
-    const OeSortSide S = t.s[blockIdx.y];
-    const int tid = threadIdx.x;
-    const unsigned n = fo_min(S.cursor[0], S.capacity), ntiles = (n + OE_SORT_TILE - 1) / OE_SORT_TILE;
-    unsigned* row = S.hist + (unsigned)blockIdx.x * S.tiles;
-    const unsigned chunk = (ntiles + OE_THREADS - 1) / OE_THREADS;
-    const unsigned lo = fo_min((unsigned)tid * chunk, ntiles), hi = fo_min(lo + chunk, ntiles);
-    unsigned sum = 0;
-    for (unsigned k = lo; k < hi; ++k) sum += row[k];
-    unsigned total;
-    unsigned run = fo_block_excl_scan(sum, sh, tid, &total);
-    for (unsigned k = lo; k < hi; ++k) { const unsigned c = row[k]; row[k] = run; run += c; }
-    if (tid == 0) S.totals[blockIdx.x] = total;
-}
-
-// Stable scatter of one tile.  Wave w owns keys [w * 1024, (w + 1) * 1024) of the tile, 64 consecutive ones per round.  A key's
-// rank among the equal digits of its wave = the wave's running count of the digit + the equal digits in lower lanes (ballots);
-// the waves' counts are then prefixed per digit on top of (digits below in the array) + (this digit in earlier tiles).
-__global__ __launch_bounds__(256) void oe_sort_scatter_kernel(OeSortTable t) {
-    __shared__ unsigned wcnt[OE_THREADS / 64][256];
-    __shared__ unsigned sh[OE_THREADS];
-    const OeSortSide S = t.s[blockIdx.y];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned n = fo_min(S.cursor[0], S.capacity), tile = blockIdx.x;
-    if (tile >= (n + OE_SORT_TILE - 1) / OE_SORT_TILE) return;
-    for (int w = 0; w < OE_THREADS / 64; ++w) wcnt[w][tid] = 0;
-    unsigned total;
-    const unsigned digit_first = fo_block_excl_scan(S.totals[tid], sh, tid, &total) + S.hist[(unsigned)tid * S.tiles + tile];
-    // (the scan's barriers also publish the zeroed counters)
-    const u64 below = (1ull << lane) - 1ull;
-    const unsigned seg = tile * OE_SORT_TILE + (unsigned)wave * (64 * OE_SORT_ITEMS);
-    unsigned key[OE_SORT_ITEMS], rank[OE_SORT_ITEMS];
-#pragma unroll
-    for (int r = 0; r < OE_SORT_ITEMS; ++r) {
-        const unsigned i = seg + r * 64 + lane;
-        const bool valid = i < n;
-        const unsigned k = valid ? oe_sort_load(S, t, i) : 0xFFFFFFFFu;
-        const unsigned d = (k >> t.shift) & 255u;
-        u64 same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const u64 bal = __ballot(bit);
-            same &= bit ? bal : ~bal;
-        }
-        const unsigned lower = fo_popc(same & below);
-        const unsigned prev = valid ? wcnt[wave][d] : 0u;
-        OE_WAVE_SYNC();
-        if (valid && lower == 0) wcnt[wave][d] = prev + fo_popc(same);     // one lane per digit present in the round
-        OE_WAVE_SYNC();
-        key[r] = k;
-        rank[r] = prev + lower;
-    }
-    __syncthreads();
-    {   // thread d: the waves' counts of digit d -> first positions
-        unsigned run = digit_first;
-        for (int w = 0; w < OE_THREADS / 64; ++w) { const unsigned c = wcnt[w][tid]; wcnt[w][tid] = run; run += c; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < OE_SORT_ITEMS; ++r) {
-        const unsigned i = seg + r * 64 + lane;
-        if (i < n) {
-            const unsigned p = wcnt[wave][(key[r] >> t.shift) & 255u] + rank[r];
-            if (p < n) S.dst[p] = t.last ? oe_unkey(key[r]) : key[r];
-        }
-    }
-}
+DEV OeItem rs_load(const OeSort& t, unsigned side, unsigned i) { return OeItem{rs_key(t, side, i)}; }
+DEV void rs_store(const OeSort& t, unsigned side, unsigned p, const OeItem& e) { t.s[side].dst[p] = t.last ? fo_unkey(e.key) : e.key; }
 
 // ---- metrics -----------------------------------------------------------------------------------------------------------------
 struct OeMetrics {
@@ -274,8 +176,8 @@ __global__ __launch_bounds__(256) void oe_metrics_part_kernel(OeMetrics m) {
     for (int r = 0; r < OE_MET_ITEMS; ++r) {
         const unsigned i = (unsigned)blockIdx.x * OE_MET_TILE + r * OE_THREADS + tid;
         if (i < n_own) {
-            const unsigned k = oe_key(own[i]);
-            const bool group_end = i + 1 == n_own || oe_key(own[i + 1]) != k;
+            const unsigned k = fo_key(own[i]);
+            const bool group_end = i + 1 == n_own || fo_key(own[i + 1]) != k;
             if (side == 0) {
                 const unsigned lb = oe_bound(other, n_other, k, 0), ub = oe_bound(other, n_other, k, 1);
                 gt += lb; eq += ub - lb;
@@ -329,7 +231,7 @@ __global__ __launch_bounds__(256) void oe_metrics_final_kernel(OeMetrics m) {
         for (int s = 0; s < 2; ++s) if (k < (long long)P && (double)k / dp < m.level) ++k;
         rank = (u64)k;
         thr = m.sorted[0][P - (unsigned)k];                             // the k-th largest positive
-        const unsigned key = oe_key(thr);
+        const unsigned key = fo_key(thr);
         tp = P - oe_bound(m.sorted[0], P, key, 0);
         fp = N - oe_bound(m.sorted[1], N, key, 0);
     }
@@ -344,7 +246,7 @@ __global__ __launch_bounds__(256) void oe_metrics_final_kernel(OeMetrics m) {
 }  // namespace
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------
-extern "C" int effdet_ood_eval_sort_tile(void) { return OE_SORT_TILE; }
+extern "C" int effdet_ood_eval_sort_tile(void) { return RS_TILE; }
 
 extern "C" long long effdet_ood_eval_workspace_bytes(long long capacity_pos, long long capacity_neg) {
     OeLayout L;
@@ -394,7 +296,7 @@ extern "C" int effdet_ood_eval_sort(void* stream, const float* pos, long long ca
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const unsigned grid_x = L.tiles[0] > L.tiles[1] ? L.tiles[0] : L.tiles[1];
     for (int pass = 0; pass < 4; ++pass) {
-        OeSortTable t;
+        OeSort t;
         t.shift = 8 * pass; t.first = pass == 0; t.last = pass == 3;
         for (int s = 0; s < 2; ++s) {
             unsigned* a = reinterpret_cast<unsigned*>(ws + L.keys_a[s]);
@@ -407,9 +309,7 @@ extern "C" int effdet_ood_eval_sort(void* stream, const float* pos, long long ca
             t.s[s].capacity = (unsigned)caps[s];
             t.s[s].tiles = L.tiles[s];
         }
-        hipLaunchKernelGGL(oe_sort_hist_kernel, dim3(grid_x, 2), dim3(OE_THREADS), 0, st, t);
-        hipLaunchKernelGGL(oe_sort_scan_kernel, dim3(256, 2), dim3(OE_THREADS), 0, st, t);
-        hipLaunchKernelGGL(oe_sort_scatter_kernel, dim3(grid_x, 2), dim3(OE_THREADS), 0, st, t);
+        rs_sort_pass(st, t, grid_x, 2);
     }
     return effdet_check_launch();
 }

@@ -261,6 +261,31 @@ def test_sorted_counts_of_one_class_with_70000_entries():
     assert ref['k_star'][0, 0] == 24000 and ref['pos'][0, 0] > 65536 and r['wi'][0] == ref['open_at'][0, 0] / ref['rank_at'][0, 0]
 
 
+def test_sorted_counts_with_300_classes():
+    """more than 255 classes: the class takes two digits of the key, so the sort runs a sixth pass, here with both payload words;
+    tile + 1 entries, so the last one is alone in a second tile.  Classes -1 and 300 and flag bit 31 are invalid entries."""
+    C1, rs = 300, np.random.RandomState(21)
+    n = _tile() + 1
+    scores = (rs.randint(0, 64, n) / np.float32(64)).astype(np.float32)
+    classes = rs.randint(-1, C1 + 1, n)
+    u = rs.uniform(size=n)
+    flags = np.where(u < 0.3, 1, np.where(u < 0.4, 1 << 16, np.where(u < 0.45, 1 << 31, 0))).astype(np.int64)
+    words = rs.randint(0, 2, n)
+    gt_count = np.array([int(((flags == 1) & (classes == c)).sum()) + rs.randint(0, 3) for c in range(C1)])
+    gt_count[C1 - 1] = 0
+    ev = _open(C1 - 1, capacity=n + 7)
+    _load(ev, scores, classes, flags, words, gt_count)
+    ev.enqueue(recall_level=0.625)
+    r = ev.result()
+    ref = O.counts_from_entries(scores, classes, flags, words, gt_count, C1, 1, 0.625)
+    for k in O.MATRICES:
+        assert np.array_equal(r[k], ref[k]), (k, np.nonzero(r[k] != ref[k]))
+    assert len(O.MATRICES) == 7 and (ref['n_det'][0, 256:] > 0).any() and (ref['tp'][0, 256:] > 0).any() and (ref['open_total'][0] > 0).any()
+    order = O.sorted_order(scores, classes, flags, C1)
+    cls, sc, fl, op = ev.sorted()
+    assert np.array_equal(fl, (flags.astype(np.uint32))[order]) and np.array_equal(op, words.astype(np.uint32)[order])
+
+
 def test_sixteen_thresholds_an_entry_ignored_everywhere_is_dropped_from_the_open_counts():
     thresholds = [round(0.2 + 0.05 * i, 2) for i in range(16)]
     gt = np.array([[0, 0, 10, 10], [0, 0, 10, 10], [50, 50, 60, 60], [50, 50, 60, 60]], np.float32)

@@ -200,11 +200,16 @@ def _entries(n, C, seed, levels=4096):
     return scores, classes, flags, gt_count
 
 
-@pytest.mark.parametrize('which', ['1', '255', '257', 'tile-1', 'tile', 'tile+1', '3*tile+17', '65536'])
-def test_sorted_ap_sizes(which):
+SIZES = ['1', '255', '257', 'tile-1', 'tile', 'tile+1', '3*tile+17', '65536']
+# beyond the sizes: 255 classes = five sort passes with the invalid class 255 in the top digit; 256 and 300 = the sixth pass
+MANY_CLASSES = [255, 256, 300]
+
+
+@pytest.mark.parametrize('which,C', [(w, 5) for w in SIZES] + [('tile+1', C) for C in MANY_CLASSES],
+                         ids=SIZES + ['tile+1-%d-classes' % C for C in MANY_CLASSES])
+def test_sorted_ap_sizes(which, C):
     tile = _tile()
     n = eval(which, {'tile': tile})
-    C = 5
     scores, classes, flags, gt_count = _entries(n, C, 1000 + n % 997)
     ev = _dataset(C, capacity=max(n, 2 * tile + 5))
     _load(ev, scores, classes, flags, gt_count)

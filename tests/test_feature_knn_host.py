@@ -42,6 +42,18 @@ def test_entry_points_declared_bound_and_exported():
         src = open(os.path.join(csrc, unit)).read()
         assert not re.search(r'void \w+_(count|base)_kernel\(', src) and 'block_sum(T v' not in src and 'oe_block_sum' not in src, unit
     assert '#include "compact.h"' in open(os.path.join(csrc, 'ood_eval.hip')).read()
+    # the radix sort is stated once, in radix_sort.h, and the integer helpers once, in compact.h
+    for unit in ('ood_eval', 'eval_scale'):
+        src = open(os.path.join(csrc, unit + '.hip')).read()
+        assert '#include "radix_sort.h"' in src and not re.search(r'void \w+_sort_(hist|scan|scatter)_kernel\(', src), unit
+        assert re.search(r'build/%s\.o:.*\bcompact\.h.*\bradix_sort\.h' % unit, mk), unit
+    src = open(os.path.join(csrc, 'eval_scale.hip')).read()
+    assert not re.search(r'\w+_block_excl_scan\(unsigned v|unsigned \w+_(key|floor_pow2|min|popc)\(', src)
+    # the candidate search and the IoU of the two matchers once, in eval_match.h
+    for unit in ('evaluation', 'eval_scale'):
+        src = open(os.path.join(csrc, unit + '.hip')).read()
+        assert '#include "eval_match.h"' in src and '__shfl_xor(bj' not in src and 'inter / (' not in src, unit
+        assert re.search(r'build/%s\.o:.*\beval_match\.h' % unit, mk), unit
 
 
 def _table(n=1, cells=(100,), channel=1, F=64):

@@ -33,6 +33,19 @@ template <class T> static inline T __shfl_xor(T v, int o, int) {
     const T r = (T)simctx.xf[lane ^ o]; simctx.wave->arrive_and_wait();
     return r;
 }
+// The shuffles pass values through a double: exact for float, double and 32-bit integers, not for 64-bit ones.
+template <class T> static inline T __shfl_up(T v, int o, int) {
+    const int lane = threadIdx.x & 63;
+    simctx.xf[lane] = (double)v; simctx.wave->arrive_and_wait();
+    const T r = lane >= o ? (T)simctx.xf[lane - o] : v; simctx.wave->arrive_and_wait();
+    return r;
+}
+template <class T> static inline T __shfl_down(T v, int o, int) {
+    const int lane = threadIdx.x & 63;
+    simctx.xf[lane] = (double)v; simctx.wave->arrive_and_wait();
+    const T r = lane + o < 64 ? (T)simctx.xf[lane + o] : v; simctx.wave->arrive_and_wait();
+    return r;
+}
 static inline unsigned long long __ballot(bool p) {
     const int lane = threadIdx.x & 63;
     simctx.xi[lane] = p ? 1 : 0; simctx.wave->arrive_and_wait();
@@ -45,10 +58,12 @@ static inline unsigned long long __ballot(bool p) {
 template <class T> static inline T atomicAdd(T* p, T v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
 template <class T> static inline T atomicOr(T* p, T v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
 static inline void sim_wave_sync() { simctx.wave->arrive_and_wait(); }
+static inline void __builtin_amdgcn_wave_barrier() { sim_wave_sync(); }
 DEV float wave_reduce_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
 DEV float wave_reduce_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64)); return v; }
 static inline float __int_as_float(int v) { float f; std::memcpy(&f, &v, 4); return f; }
 static inline int __float_as_int(float f) { int v; std::memcpy(&v, &f, 4); return v; }
+static inline unsigned __float_as_uint(float f) { unsigned v; std::memcpy(&v, &f, 4); return v; }
 template <class K, class... A>
 void sim_launch(K kernel, dim3 grid, dim3 block, A... args) {
     const int nt = block.x, nw = (nt + 63) / 64;

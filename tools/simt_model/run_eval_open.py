@@ -9,8 +9,7 @@ arithmetic, indexing and bounds (a guard region follows every buffer), not timin
 
     python3 tools/simt_model/run_eval_open.py [--quick]    needs g++ with C++20 (std::barrier); minutes, a thread per lane
 
-What the model adds to common.h for this unit: __shfl_up / __shfl_down, the wave barrier, __float_as_uint, and a fixed-size array
-in place of the matching kernel's dynamic LDS."""
+What the model adds to common.h for this unit: a fixed-size array in place of the matching kernel's dynamic LDS."""
 import ctypes
 import os
 import shutil
@@ -33,20 +32,6 @@ PRELUDE = '''#include "common.h"
 #undef EFFDET_EINVAL
 #define EFFDET_EINVAL (-22)
 using std::min; using std::floor; using std::fabs;
-template <class T> static inline T __shfl_up(T v, int o, int) {
-    const int lane = threadIdx.x & 63;
-    simctx.xf[lane] = (double)v; simctx.wave->arrive_and_wait();
-    const T r = lane >= o ? (T)simctx.xf[lane - o] : v; simctx.wave->arrive_and_wait();
-    return r;
-}
-template <class T> static inline T __shfl_down(T v, int o, int) {
-    const int lane = threadIdx.x & 63;
-    simctx.xf[lane] = (double)v; simctx.wave->arrive_and_wait();
-    const T r = lane + o < 64 ? (T)simctx.xf[lane + o] : v; simctx.wave->arrive_and_wait();
-    return r;
-}
-static inline void __builtin_amdgcn_wave_barrier() { sim_wave_sync(); }
-static inline unsigned __float_as_uint(float f) { unsigned v; std::memcpy(&v, &f, 4); return v; }
 '''
 DYNAMIC_LDS = 'extern __shared__ int sh[];'
 GUARD = 64
@@ -58,6 +43,8 @@ NAMES = ('effdet_eval_match_multi', 'effdet_eval_open_words', 'effdet_eval_appen
 
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
+    for header in ('compact.h', 'radix_sort.h', 'eval_match.h'):                                  # included by the unit
+        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
     src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'eval_scale.hip')).read()
     assert src.count(DYNAMIC_LDS) == 1
     src = src.replace(DYNAMIC_LDS, 'static int sh[16384];')

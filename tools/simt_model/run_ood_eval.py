@@ -25,7 +25,6 @@ import _ood_eval_ref as R  # noqa: E402
 from ood_object_detection_amd import _lib  # noqa: E402
 
 PRELUDE = ('#include "common.h"\n'
-           '#define OE_WAVE_SYNC() sim_wave_sync()\n'
            '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
 GUARD = 64
 SENTINEL = np.float32(-12345.5)
@@ -33,7 +32,8 @@ SENTINEL = np.float32(-12345.5)
 
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'compact.h'), tmp)       # included by the unit
+    for header in ('compact.h', 'radix_sort.h'):                                                 # included by the unit
+        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
     src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'ood_eval.hip')).read()
     with open(os.path.join(tmp, 'ood_eval.cpp'), 'w') as f:
         f.write(PRELUDE + src)
