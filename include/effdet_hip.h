@@ -240,6 +240,33 @@ int effdet_sepconv_fused(void* stream, int dtype, int B, int nlevels, const int*
                          void* const* out_ptr, const long long* out_image_stride,
                          int ood_classes, int num_anchors, float* ood_energy, float* ood_maxlogit,
                          long long ood_image_stride, const long long* ood_level_off);
+/* Host-only plan query (launches nothing): which instantiation of the kernel template and which geometry a call of
+ * effdet_sepconv_fused with this dtype (EFFDET_PAD_SYMMETRIC is ignored: no form depends on the padding convention), these
+ * levels, n_in, F, N, ood_classes / num_anchors, scale present or NULL and post_act runs - answered by the launcher's own
+ * dispatch, which describes its choice instead of launching.  `aligned` != 0: every output pointer is 16-byte aligned and every
+ * output image stride a whole number of dwords (together with the row lengths this decides vec_ok; two-term calls are refused
+ * without it).  Contract of effdet_mbconv_plan_describe: fills min(n, EFFDET_SEPCONV_PLAN_INTS) ints of `out` and returns that
+ * count, or EFFDET_EINVAL (out == NULL, n <= 0, or anything the launch refuses from the shape: dtype, level count and sizes,
+ * n_in, F not a positive multiple of 8, N, num_anchors * ood_classes != N, a tile that does not fit 160 KiB of LDS).  Slots:
+ *    0  element kind: 0 float32, 1 bf16, 2 two-term bf16
+ *    1  TH, 2 TW: pixel tile;  3 threads per workgroup
+ *    4  FT: compile-time channel count (0: the generic-width kernel)
+ *    5  BN: output channels per chunk (96: class chunk, 64)
+ *    6  OOD: per-anchor chunks with the energy / max-logit epilogue
+ *    7  BST: the branch-free class predict
+ *    8  NIN: inputs the instantiation holds registers for (1 or 3)
+ *    9  META: the MetaHead form (0 from this query: it describes effdet_sepconv_fused)
+ *   10  subs: sub-chunks per anchor (1 without OOD)
+ *   11  nchunks: channel chunks a workgroup walks
+ *   12  tiles_total: workgroups per image
+ *   13  dynamic LDS bytes of a workgroup
+ *   14  the depthwise taps are prefetched into registers (9 F <= 1536 with 512 threads, <= 1280 with 256)
+ *   15  the next W chunk is prefetched into registers
+ *   16  float32 outputs from a 16-bit compute kind (dtype 3 / 6)
+ *   17  vec_ok: 8-channel output pieces leave as vectors */
+#define EFFDET_SEPCONV_PLAN_INTS 18
+int effdet_sepconv_plan_describe(int dtype, int nlevels, const int* level_hw, int n_in, int F, int N, int ood_classes,
+                                 int num_anchors, int has_scale, int post_act, int aligned, int* out, int n);
 
 /* MetaHead (effdet/efficientdet.py:569-695): the fork's functional class head - SeparableConv layers shared by the
  * levels, each followed by F.batch_norm(training=True) (statistics of the current batch, per level) and Swish.

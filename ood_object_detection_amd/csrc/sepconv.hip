@@ -828,8 +828,10 @@ size_t sep_lds_bytes(int F, bool cp = false) {
     return (halo > wt ? halo : wt) + (size_t)BM * arow + (size_t)9 * F * 4 + (size_t)2 * BN * 4;
 }
 
+struct SepPlan { int v[EFFDET_SEPCONV_PLAN_INTS]; };     // slots of effdet_sepconv_plan_describe
+
 template <typename T, int TH, int TW, int BN, bool OOD, int NTH, int FT, bool META = false, int NIN = 3, bool BST = false>
-int launch_sep(hipStream_t st, SepArgs& a, int B) {
+int launch_sep(hipStream_t st, SepArgs& a, int B, SepPlan* plan = nullptr) {
     int tiles = 0;
     for (int i = 0; i < a.nlevels; ++i) {
         a.lv[i].tiles_x = (a.lv[i].W + TW - 1) / TW;
@@ -840,6 +842,22 @@ int launch_sep(hipStream_t st, SepArgs& a, int B) {
     const size_t lds = sep_lds_bytes<T, TH, TW, BN>(a.F, IsFast<T>::value && TW == 16 && NTH == 512 && FT == 64 && !META) + (META ? (size_t)(NTH / 64) * 2 * BN * 4 : 0);   // + statistics scratch
     if (lds > 160 * 1024) return EFFDET_EINVAL;
     a.tiles_total = tiles;
+    if (plan) {                                  // effdet_sepconv_plan_describe: report this instantiation and geometry, launch nothing
+        // What the kernel derives from F, N and the class count at run time.  These four lines restate sepconv_kernel's own
+        // expressions - DPC and d_pref at its "depthwise taps" block, WPC / ppr / prefetch and subs / nchunks at the head of its
+        // phase 3 - and MUST be kept in step with them: a change to DPC, WPC, ppr, subs or nchunks there is a change here.
+        // (tests/test_sepconv_forms_host.py pins the taps switch at 9 F <= 1536 / 1280 and subs / nchunks of a 288-wide head.)
+        constexpr int DPC = (9 * 128 + NTH - 1) / NTH, CHB = OpGeom<T>::CHUNK;
+        constexpr int WPC = (BN * (CHB / 8) + NTH - 1) / NTH;
+        const int nkc = (a.F * (int)sizeof(T) + CHB - 1) / CHB, ppr = nkc * (CHB / 16);
+        const int subs = OOD ? (a.ood_classes + BN - 1) / BN : 1;
+        const int v[EFFDET_SEPCONV_PLAN_INTS] = {
+            IsPair<T>::value ? 2 : (sizeof(T) == 2 ? 1 : 0), TH, TW, NTH, FT, BN, OOD ? 1 : 0, BST ? 1 : 0, NIN, META ? 1 : 0,
+            subs, OOD ? a.num_anchors * subs : (a.N + BN - 1) / BN, tiles, (int)lds,
+            9 * a.F <= DPC * NTH ? 1 : 0, BN * ppr <= NTH * WPC ? 1 : 0, a.out_f32, a.vec_ok};
+        for (int i = 0; i < EFFDET_SEPCONV_PLAN_INTS; ++i) plan->v[i] = v[i];
+        return EFFDET_OK;
+    }
     auto kern = sepconv_kernel<T, TH, TW, BN, OOD, NTH, FT, META, NIN, BST>;
     if (lds > 64 * 1024) {
         static bool attr_done = false;           // one per template instantiation
@@ -855,42 +873,42 @@ int launch_sep(hipStream_t st, SepArgs& a, int B) {
 
 constexpr int BST_TH = 8;                          // pixel-tile rows of the branch-free class predict (16 x 16 tiles: see sepconv_kernel)
 template <typename T, int TH, int TW, int NTH, int FT>
-int dispatch_sep_f(hipStream_t st, SepArgs& a, int B) {
+int dispatch_sep_f(hipStream_t st, SepArgs& a, int B, SepPlan* plan = nullptr) {
     if (a.ood_classes > 0) {
         // class predict: one 96-channel chunk per anchor; widths whose 96-row W chunk no longer fits beside the A tile (float32
         // d5, 288 channels) take 64-row chunks - two sub-chunks per anchor, the running max / sum-exp carries over
         if constexpr (FT == 0) {
-            if (sep_lds_bytes<T, TH, TW, 96>(a.F) > 160 * 1024) return launch_sep<T, TH, TW, 64, true, NTH, FT>(st, a, B);
+            if (sep_lds_bytes<T, TH, TW, 96>(a.F) > 160 * 1024) return launch_sep<T, TH, TW, 64, true, NTH, FT>(st, a, B, plan);
         }
         if constexpr (IsPair<T>::value && NTH == 512) {
             // two-term mode (float32 logits): the same branch-free chunk loop
             if (a.out_f32 && a.ood_classes % 2 == 0 && a.ood_classes <= 96 && a.F <= 64 && a.scale == nullptr && !a.post_act)
-                return launch_sep<T, BST_TH, TW, 96, true, NTH, FT, false, 3, true>(st, a, B);
+                return launch_sep<T, BST_TH, TW, 96, true, NTH, FT, false, 3, true>(st, a, B, plan);
         }
         if constexpr (sizeof(T) == 2 && NTH == 512) {
             // bf16 with dword-aligned class rows (an even class count): the branch-free chunk loop
             // (and a W chunk every thread can prefetch in two pieces: up to 64 channels - wider heads stay on the general loop)
             // (no BN scale, no activation behind the predict conv: the branch-free epilogue below builds on all of that)
             if (a.vec_ok && !a.out_f32 && a.ood_classes % 2 == 0 && a.ood_classes <= 96 && a.F <= 64 && a.scale == nullptr && !a.post_act)
-                return launch_sep<T, BST_TH, TW, 96, true, NTH, FT, false, 3, true>(st, a, B);
+                return launch_sep<T, BST_TH, TW, 96, true, NTH, FT, false, 3, true>(st, a, B, plan);
         }
-        return launch_sep<T, TH, TW, 96, true, NTH, FT>(st, a, B);
+        return launch_sep<T, TH, TW, 96, true, NTH, FT>(st, a, B, plan);
     }
     // head layers read one input: a variant without the registers of the other two
-    if (FT == 64 && a.n_in == 1) return launch_sep<T, TH, TW, 64, false, NTH, FT, false, 1>(st, a, B);
-    return launch_sep<T, TH, TW, 64, false, NTH, FT>(st, a, B);
+    if (FT == 64 && a.n_in == 1) return launch_sep<T, TH, TW, 64, false, NTH, FT, false, 1>(st, a, B, plan);
+    return launch_sep<T, TH, TW, 64, false, NTH, FT>(st, a, B, plan);
 }
 
 // the BiFPN widths of tf_efficientdet_d0..d4 get compile-time channel counts; anything else the generic kernel
 template <typename T, int TH, int TW, int NTH>
-int dispatch_sep(hipStream_t st, SepArgs& a, int B) {
+int dispatch_sep(hipStream_t st, SepArgs& a, int B, SepPlan* plan = nullptr) {
     switch (a.F) {
-        case 64:  return dispatch_sep_f<T, TH, TW, NTH, 64>(st, a, B);
-        case 88:  return dispatch_sep_f<T, TH, TW, NTH, 88>(st, a, B);
-        case 112: return dispatch_sep_f<T, TH, TW, NTH, 112>(st, a, B);
-        case 160: return dispatch_sep_f<T, TH, TW, NTH, 160>(st, a, B);
-        case 224: return dispatch_sep_f<T, TH, TW, NTH, 224>(st, a, B);
-        default:  return dispatch_sep_f<T, TH, TW, NTH, 0>(st, a, B);
+        case 64:  return dispatch_sep_f<T, TH, TW, NTH, 64>(st, a, B, plan);
+        case 88:  return dispatch_sep_f<T, TH, TW, NTH, 88>(st, a, B, plan);
+        case 112: return dispatch_sep_f<T, TH, TW, NTH, 112>(st, a, B, plan);
+        case 160: return dispatch_sep_f<T, TH, TW, NTH, 160>(st, a, B, plan);
+        case 224: return dispatch_sep_f<T, TH, TW, NTH, 224>(st, a, B, plan);
+        default:  return dispatch_sep_f<T, TH, TW, NTH, 0>(st, a, B, plan);
     }
 }
 
@@ -900,14 +918,14 @@ int dispatch_sep(hipStream_t st, SepArgs& a, int B) {
 // sub-chunks (the 96-row chunk would need 198 016 B; the running max / sum-exp carries across the sub-chunks, as in float32 d5).
 // At TW = 8 the depthwise runs on the VALU (float taps on the joined value); the pointwise conv is the same three-product MFMA.
 template <int FT>
-int dispatch_sep_pair_8x8(hipStream_t st, SepArgs& a, int B) {
+int dispatch_sep_pair_8x8(hipStream_t st, SepArgs& a, int B, SepPlan* plan = nullptr) {
     if (a.ood_classes > 0) {
         if constexpr (FT == 0) {
-            if (sep_lds_bytes<bf16p_t, 8, 8, 96>(a.F) > 160 * 1024) return launch_sep<bf16p_t, 8, 8, 64, true, 256, 0>(st, a, B);
+            if (sep_lds_bytes<bf16p_t, 8, 8, 96>(a.F) > 160 * 1024) return launch_sep<bf16p_t, 8, 8, 64, true, 256, 0>(st, a, B, plan);
         }
-        return launch_sep<bf16p_t, 8, 8, 96, true, 256, FT>(st, a, B);
+        return launch_sep<bf16p_t, 8, 8, 96, true, 256, FT>(st, a, B, plan);
     }
-    return launch_sep<bf16p_t, 8, 8, 64, false, 256, FT>(st, a, B);
+    return launch_sep<bf16p_t, 8, 8, 64, false, 256, FT>(st, a, B, plan);
 }
 
 }  // namespace
@@ -919,6 +937,48 @@ struct MetaExtra {
     float* stat_partial;
     void* const* dw_out; const long long* dw_out_image_stride;
 };
+}
+
+// What a launch refuses from the shape alone, before it looks at a pointer (shared with effdet_sepconv_plan_describe).
+// dtype comes in without the pad flag and leaves as the compute kind 0 / 1 / 2; out_f32 receives the float32-output bit.
+static int sep_check_shape(int& dtype, int& out_f32, bool meta, int B, int nlevels, const int* level_hw, int n_in, int fuse_mode,
+                           int F, int N, int ood_classes, int num_anchors) {
+    if (nlevels < 1 || nlevels > 5 || n_in < 1 || n_in > 3 || B <= 0 || !level_hw) return EFFDET_EINVAL;
+    // dtype 3 (= 1 | 2): bfloat16 compute, float32 outputs; dtype 6 (= 2 | 4): two-term bf16 compute, float32 outputs
+    if (dtype != 0 && dtype != 1 && dtype != 2 && dtype != 3 && dtype != 6) return EFFDET_EINVAL;
+    out_f32 = (dtype == 3 || dtype == 6) ? 1 : 0;
+    dtype = dtype == 3 ? 1 : (dtype == 6 ? 2 : dtype);
+    if (dtype == 2 && (meta || (!out_f32 && N % 8))) return EFFDET_EINVAL;      // two-term outputs: whole 8-channel groups; no MetaHead form
+    if (F <= 0 || F % 8 || N <= 0 || fuse_mode < 0 || fuse_mode > 2) return EFFDET_EINVAL;
+    if (fuse_mode == 0 && n_in != 1) return EFFDET_EINVAL;
+    if (ood_classes > 0 && (num_anchors <= 0 || num_anchors * ood_classes != N)) return EFFDET_EINVAL;
+    for (int l = 0; l < nlevels; ++l)
+        if (level_hw[2 * l] <= 0 || level_hw[2 * l + 1] <= 0) return EFFDET_EINVAL;
+    return EFFDET_OK;
+}
+
+// 8-channel output pieces may go out as vectors when the rows are dword aligned (the pointers and image strides are checked per level)
+static int sep_rows_dword_aligned(int N, int ood_classes, size_t esz) {
+    return ((size_t)N * esz) % 4 == 0 && (ood_classes <= 0 || ((size_t)ood_classes * esz) % 4 == 0);
+}
+
+// From the compute kind to the kernel family; `plan` set: the launcher describes its choice instead of launching
+static int sep_dispatch(bool meta, int dtype, hipStream_t st, SepArgs& a, int B, SepPlan* plan) {
+    if (meta) {                                  // MetaHead layers: generic-width kernels with the extra inputs / outputs
+        if (a.ood_classes > 0 || a.fuse_mode != 0 || a.out_f32 || a.scale != nullptr) return EFFDET_EINVAL;   // (no scale: its LDS row carries the statistics pivot)
+        return dtype == 0 ? launch_sep<float, 8, 8, 64, false, 256, 0, true>(st, a, B, plan)
+                          : launch_sep<bf16_t, 8, 16, 64, false, 512, 0, true>(st, a, B, plan);
+    }
+    if (dtype == 0) return dispatch_sep<float, 8, 8, 256>(st, a, B, plan);
+    if (dtype == 2) {
+        // the geometry follows from F alone (never from B or the grid): an image's bits do not depend on the batch it came in.
+        // The 8x16 tile keeps every width whose 64-row form fits (up to 192; wider FT = 0 class heads drop to 64-row chunks there).
+        if (sep_lds_bytes<bf16p_t, 8, 16, 64>(a.F) <= 160 * 1024) return dispatch_sep<bf16p_t, 8, 16, 512>(st, a, B, plan);
+        return a.F == 224 ? dispatch_sep_pair_8x8<224>(st, a, B, plan) : dispatch_sep_pair_8x8<0>(st, a, B, plan);
+    }
+    // bf16: 512 threads per 8x16 tile - the LDS footprint allows two workgroups per CU, so four waves per SIMD
+    // share the VALU-heavy halo and epilogue phases
+    return dispatch_sep<bf16_t, 8, 16, 512>(st, a, B, plan);
 }
 
 static int sepconv_common(
@@ -937,28 +997,21 @@ static int sepconv_common(
     void* const* out_ptr, const long long* out_image_stride,   // [nlevels]
     int ood_classes, int num_anchors, float* ood_energy, float* ood_maxlogit,
     long long ood_image_stride, const long long* ood_level_off) {
-    if (nlevels < 1 || nlevels > 5 || n_in < 1 || n_in > 3 || B <= 0) return EFFDET_EINVAL;
     if (!level_hw || !in_ptr || !in_image_stride || !in_hw || !in_mode || !dw_w || !pw_w || !shift || !affine_row ||
         !out_ptr || !out_image_stride) return EFFDET_EINVAL;
     const int sym = take_pad_flag(dtype);                // padding convention of the on-the-fly 3x3 / s2 max pool (mode 2 inputs)
-    // dtype 3 (= 1 | 2): bfloat16 compute, float32 outputs; dtype 6 (= 2 | 4): two-term bf16 compute, float32 outputs
-    if (dtype != 0 && dtype != 1 && dtype != 2 && dtype != 3 && dtype != 6) return EFFDET_EINVAL;
-    const int out_f32 = (dtype == 3 || dtype == 6) ? 1 : 0;
-    dtype = dtype == 3 ? 1 : (dtype == 6 ? 2 : dtype);
-    if (dtype == 2 && (meta || (!out_f32 && N % 8))) return EFFDET_EINVAL;      // two-term outputs: whole 8-channel groups; no MetaHead form
-    if (F <= 0 || F % 8 || N <= 0 || fuse_mode < 0 || fuse_mode > 2) return EFFDET_EINVAL;
+    int out_f32 = 0;
+    if (sep_check_shape(dtype, out_f32, meta != nullptr, B, nlevels, level_hw, n_in, fuse_mode, F, N, ood_classes, num_anchors) != EFFDET_OK)
+        return EFFDET_EINVAL;
     if (fuse_mode != 0 && !fuse_w) return EFFDET_EINVAL;
-    if (fuse_mode == 0 && n_in != 1) return EFFDET_EINVAL;
-    if (ood_classes > 0) {
-        if (!ood_energy || !ood_maxlogit || !ood_level_off || num_anchors <= 0 || num_anchors * ood_classes != N) return EFFDET_EINVAL;
-    }
+    if (ood_classes > 0 && (!ood_energy || !ood_maxlogit || !ood_level_off)) return EFFDET_EINVAL;
     SepArgs a;
     a.nlevels = nlevels; a.n_in = n_in; a.fuse_mode = fuse_mode; a.fden = fuse_den;
     for (int i = 0; i < 3; ++i) a.fw[i] = (fuse_mode != 0 && i < n_in) ? fuse_w[i] : 0.f;
     for (int i = 0; i < 3; ++i) a.fwn[i] = fuse_mode == 1 ? a.fw[i] / fuse_den : a.fw[i];
     const size_t esz = (dtype == 0 || out_f32) ? 4 : 2;
     a.out_f32 = out_f32;
-    a.vec_ok = ((size_t)N * esz) % 4 == 0 && (ood_classes <= 0 || ((size_t)ood_classes * esz) % 4 == 0);
+    a.vec_ok = sep_rows_dword_aligned(N, ood_classes, esz);
     a.pre_act = pre_act; a.post_act = post_act; a.dw_w = dw_w; a.pw_w = pw_w; a.scale = scale; a.shift = shift;
     a.F = F; a.N = N; a.ood_classes = ood_classes > 0 ? ood_classes : 0; a.num_anchors = num_anchors;
     a.ood_energy = ood_energy; a.ood_maxlogit = ood_maxlogit; a.ood_image_stride = ood_image_stride;
@@ -972,7 +1025,6 @@ static int sepconv_common(
         L.dw_out_image_stride = (meta && meta->dw_out_image_stride) ? meta->dw_out_image_stride[l] : 0;
         if (L.dw_out && reinterpret_cast<uintptr_t>(L.dw_out) % 16) return EFFDET_EINVAL;
         L.H = level_hw[2 * l]; L.W = level_hw[2 * l + 1];
-        if (L.H <= 0 || L.W <= 0) return EFFDET_EINVAL;
         L.affine_row = affine_row[l];
         L.out = out_ptr[l]; L.out_image_stride = out_image_stride[l];
         L.ood_off = (ood_classes > 0) ? ood_level_off[l] : 0;
@@ -993,27 +1045,14 @@ static int sepconv_common(
             } else return EFFDET_EINVAL;
         }
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (meta) {                                  // MetaHead layers: generic-width kernels with the extra inputs / outputs
-        if (ood_classes > 0 || fuse_mode != 0 || out_f32 || scale != nullptr) return EFFDET_EINVAL;   // (no scale: its LDS row carries the statistics pivot)
-        return dtype == 0 ? launch_sep<float, 8, 8, 64, false, 256, 0, true>(st, a, B)
-                          : launch_sep<bf16_t, 8, 16, 64, false, 512, 0, true>(st, a, B);
-    }
-    if (dtype == 0) return dispatch_sep<float, 8, 8, 256>(st, a, B);
     if (dtype == 2) {
         for (int l = 0; l < nlevels; ++l) {                      // 16-byte aligned groups
             if (!out_f32 && (reinterpret_cast<uintptr_t>(a.lv[l].out) % 16 || a.lv[l].out_image_stride % 4)) return EFFDET_EINVAL;
             for (int i = 0; i < n_in; ++i)
                 if (reinterpret_cast<uintptr_t>(a.lv[l].in[i].ptr) % 16 || a.lv[l].in[i].image_stride % 4) return EFFDET_EINVAL;
         }
-        // the geometry follows from F alone (never from B or the grid): an image's bits do not depend on the batch it came in.
-        // The 8x16 tile keeps every width whose 64-row form fits (up to 192; wider FT = 0 class heads drop to 64-row chunks there).
-        if (sep_lds_bytes<bf16p_t, 8, 16, 64>(F) <= 160 * 1024) return dispatch_sep<bf16p_t, 8, 16, 512>(st, a, B);
-        return F == 224 ? dispatch_sep_pair_8x8<224>(st, a, B) : dispatch_sep_pair_8x8<0>(st, a, B);
     }
-    // bf16: 512 threads per 8x16 tile - the LDS footprint allows two workgroups per CU, so four waves per SIMD
-    // share the VALU-heavy halo and epilogue phases
-    return dispatch_sep<bf16_t, 8, 16, 512>(st, a, B);
+    return sep_dispatch(meta != nullptr, dtype, reinterpret_cast<hipStream_t>(stream), a, B, nullptr);
 }
 
 extern "C" int effdet_sepconv_fused(
@@ -1063,6 +1102,35 @@ extern "C" int effdet_sepconv_tiles(int dtype, int nlevels, const int* level_hw,
         tiles += ((level_hw[2 * l + 1] + TW - 1) / TW) * ((level_hw[2 * l] + TH - 1) / TH);
     }
     return tiles;
+}
+
+// Host-only: the template instantiation and geometry launch_sep - reached through the same sep_check_shape / sep_dispatch as a
+// launch - picks for a call of effdet_sepconv_fused; nothing is launched.  `aligned`: every output pointer is 16-byte aligned and
+// every output image stride a whole number of dwords (what, with the row lengths, feeds vec_ok; two-term inputs and outputs must be).
+// Slots:  0 element kind (0 float32, 1 bf16, 2 two-term bf16)   1 TH   2 TW   3 threads   4 FT (0: generic width)   5 BN
+//   6 OOD   7 BST   8 NIN   9 META   10 subs (sub-chunks per anchor)   11 nchunks   12 tiles_total   13 dynamic LDS bytes
+//   14 depthwise taps prefetched   15 W chunk prefetched   16 float32 outputs from a 16-bit compute kind   17 vec_ok
+extern "C" int effdet_sepconv_plan_describe(int dtype, int nlevels, const int* level_hw, int n_in, int F, int N, int ood_classes,
+                                            int num_anchors, int has_scale, int post_act, int aligned, int* out, int n) {
+    if (!out || n <= 0) return EFFDET_EINVAL;
+    (void)take_pad_flag(dtype);                          // (no form depends on the padding convention)
+    int out_f32 = 0;
+    if (sep_check_shape(dtype, out_f32, false, 1, nlevels, level_hw, n_in, n_in == 1 ? 0 : 1, F, N, ood_classes, num_anchors) != EFFDET_OK)
+        return EFFDET_EINVAL;
+    if (dtype == 2 && !aligned) return EFFDET_EINVAL;
+    static const float present = 1.0f;                   // the dispatch only asks whether there is a scale
+    SepArgs a{};
+    a.nlevels = nlevels; a.n_in = n_in; a.F = F; a.N = N;
+    a.ood_classes = ood_classes > 0 ? ood_classes : 0; a.num_anchors = num_anchors;
+    a.scale = has_scale ? &present : nullptr; a.post_act = post_act; a.out_f32 = out_f32;
+    a.vec_ok = aligned && sep_rows_dword_aligned(N, ood_classes, (dtype == 0 || out_f32) ? 4 : 2);
+    for (int l = 0; l < nlevels; ++l) { a.lv[l].H = level_hw[2 * l]; a.lv[l].W = level_hw[2 * l + 1]; }
+    SepPlan plan{};
+    const int rc = sep_dispatch(false, dtype, nullptr, a, 1, &plan);
+    if (rc != EFFDET_OK) return rc;
+    const int m = n < EFFDET_SEPCONV_PLAN_INTS ? n : EFFDET_SEPCONV_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = plan.v[i];
+    return m;
 }
 
 namespace {

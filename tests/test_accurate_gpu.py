@@ -12,6 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import model as om
+from _sepconv_ref import sep_ref as _sep_ref      # float64 arithmetic of one fused node (R64)
 
 DEV = 'cuda:0'
 PAIR = 2
@@ -132,30 +133,6 @@ def test_pw_gemm_group_pair_equals_single_launches():
 # ------------------------------------------------------------------------------------------------------------------
 # fused separable conv (BiFPN node / head layers / class predict + OOD epilogue)
 # ------------------------------------------------------------------------------------------------------------------
-def _sep_ref(ins, modes, fw, den, fuse_mode, pre_act, dw, pw, bias, scale, shift, post_act):
-    """float64 arithmetic of one fused node: combine -> act -> dw3x3 -> pw -> affine -> act"""
-    xs = []
-    for x, m in zip(ins, modes):
-        x = x.double()
-        if m == 1:
-            x = F.interpolate(x, scale_factor=2.0, mode='nearest')
-        elif m == 2:
-            x = om.maxpool_pad(x, 3, 2, 'same')
-        xs.append(x)
-    if fuse_mode == 0:
-        y = xs[0]
-    elif fuse_mode == 1:
-        y = sum((x * w) / den for x, w in zip(xs, fw))
-    else:
-        y = sum(x * w for x, w in zip(xs, fw))
-    if pre_act:
-        y = y * torch.sigmoid(y)
-    y = om.conv2d_pad(y, dw.double(), None, 1, 'same', groups=y.shape[1])
-    y = F.conv2d(y, pw.double(), None if bias is None else bias.double())
-    if scale is not None:
-        y = y * scale.double()[None, :, None, None]
-    y = y + shift.double()[None, :, None, None]
-    return y * torch.sigmoid(y) if post_act else y
 
 
 def _nhwc_q(x):
