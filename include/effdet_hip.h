@@ -969,6 +969,31 @@ int effdet_energy_reg(void* stream, int dtype, const void* logits, const signed 
 /* bytes of the workspace for `rows` = B * N rows (pure host code; -22 for a bad argument) */
 long long effdet_energy_reg_workspace_bytes(long long rows);
 
+/* ---- virtual outlier synthesis (csrc/outlier_synth.hip): sample the class-conditional Gaussians, keep the least likely ------------
+ * For each of the n classes c = class_ids[ci] (device int32 [n]; NULL: c = ci) draw S candidates x = mu_c + L eps, eps ~ N(0, I_F),
+ * and keep the k with the largest |eps|^2, which is the Mahalanobis distance of x: the least likely ones.  eps comes from
+ * Philox4x32-10 with the counter (j, c | q << 16, t_lo, t_hi) and the key (seed_lo, seed_hi) for candidate j, feature block q
+ * (features 4 q .. 4 q + 3) and the draw number t = draw[0] (device int64); a word x gives u1 = (float(x >> 8) + 1) * 2^-24 or
+ * u2 = float(x >> 8) * 2^-24, words (0, 1) and (2, 3) are one Box-Muller pair each: sqrtf(-2 logf(u1)) * cosf / sinf(fl(2 pi) * u2),
+ * float32.  r2 = sum_d eps_d^2 with d ascending, the product and the sum rounded separately.  mu [C][F], U [F][F] = L transposed
+ * (row-major, upper triangular: cov = U^T U), log_const [1] = -sum log L_dd - F / 2 * log(2 pi), valid [C] int8: device memory, read
+ * when the kernels run, so a fit copied into them in place is seen by the next replay of a captured call.
+ *   rows [n][k][F] float32: x_d = mu_c[d] + sum_{d' <= d} U[d'][d] * eps_d' (d' ascending from 0, float32 multiplies and adds);
+ *                           zeros where valid[c] == 0 or c lies outside [0, C)
+ *   index [n][k] int32: the candidates kept, r2 descending, equal r2 by j ascending;  r2 [n][k] float32
+ *   log_density [n][k] float32 = -(r2 * 0.5) + log_const[0];  roles [n * k] int8: 0, or -1 where the rows are zeros
+ * advance != 0: a last one-thread launch sets draw[0] = t + 1.  Limits: F a multiple of 4 in [4, 512], 1 <= C <= 1024,
+ * 1 <= n <= 1024, 1 <= S <= 2^20, n * S <= 2^26, 1 <= k <= S, n * k <= 2^20; -22 otherwise, for a NULL pointer (class_ids
+ * excepted) or a workspace smaller than the query's.  No floating-point atomics, no host synchronisation, no allocation; results
+ * are bit-identical from run to run and for every grouping of the classes into calls (with the same draw[0]). */
+int effdet_outlier_synth(void* stream, int F, int C, int n, const int* class_ids, long long S, int k, unsigned long long seed,
+                         long long* draw, int advance, const float* mu, const float* U, const float* log_const,
+                         const signed char* valid, float* rows, int* index, float* r2, float* log_density, signed char* roles,
+                         void* workspace, long long workspace_bytes);
+/* bytes of the workspace for n classes of S candidates: 20 bytes a candidate plus the sort's counts (pure host code; -22 for a bad
+ * argument) */
+long long effdet_outlier_synth_workspace_bytes(int n, long long S);
+
 /* ---- few-shot episode stage (infer.py:362-447 projection phase, :566-654 meta phase), float32 ------- */
 
 /* Confident anchors per (image, level): confs[l] -> image b's `counts[l]` confidences in (y, x, a) order at

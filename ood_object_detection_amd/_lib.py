@@ -112,6 +112,9 @@ SIGNATURES = {
                                   c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_ll]),
     'effdet_energy_reg_workspace_bytes': (c_ll, [c_ll]),
+    'effdet_outlier_synth_workspace_bytes': (c_ll, [c_int, c_ll]),
+    'effdet_outlier_synth': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_ll, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
     'effdet_sepconv_meta': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_sepconv_tiles': (c_int, [c_int, c_int, c_void_p, c_void_p]),

@@ -21,7 +21,13 @@ The energy and the gradient to the logits are float32; the terms of the sums ove
 float64 from the row's float32 results (the hinge's max(0, .); the maximum and the sum of exponentials of the log-sum-exp, whose last
 three operations are repeated in float64; the joint energy) and added in float64 in a fixed order.  The counts stay on the device,
 nothing synchronises with the host, everything can be captured in a graph and gives the same bits every run.  There is no CPU
-fallback."""
+fallback.
+
+`virtual_outlier_loss` is the regulariser without outlier images (VOS): the outlier side is rows that `ood_synth.OutlierSynthesizer`
+draws in the input space of the class head's last pointwise map, pushed through that map:
+
+    synth = OutlierSynthesizer(config.fpn_channels, config.num_classes, num_anchors)
+    step = PretrainStep(model, ood_regularizer=EnergyRegularizer(config.num_classes, 'logistic'), outlier_synthesizer=synth)"""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -176,3 +182,40 @@ def anchor_roles(cls_targets, outlier_images, background='none'):
         zero = zero | ((~out_img) & (cls_targets == -1))
     # (masks and one subtraction: no index lists, so nothing here waits for the device)
     return (one.to(torch.int8) * 2 + zero.to(torch.int8) - 1).contiguous()        # 1, 0, or -1 (the two masks never overlap)
+
+
+VIRTUAL_KEYS = ('n_virtual', 'mean_l_virtual', 'mean_energy_virtual')
+
+
+def virtual_outlier_loss(reg, class_out, roles, synth, weight, bias, sample=None):
+    """The regulariser on the real logits plus the regulariser on the logits of virtual outliers (VOS, Du et al. 2022): rows drawn by
+    `ood_synth.OutlierSynthesizer` in the input space of the class head's last pointwise map and pushed through that map,
+
+        virtual logits = meta_ops.Linear(rows [n * k, F], weight [A * C, F], bias [A * C])  viewed as [1, n * k * A, C],
+
+    every virtual row's role (0, or -1 for a class that was not valid at the last fit) repeated for its A anchors.
+    -> (reg(class_out, roles)[0] + reg(virtual logits, virtual roles)[0], stats): the two sides of a call have separate means, so
+    with real roles in {1, -1} this is one call over the concatenation.  stats: the real call's, plus n_virtual, mean_l_virtual,
+    mean_energy_virtual (the outlier side of the virtual call).  The sampled rows are constants, as in VOS: the virtual side's gradient
+    reaches weight, bias and phi only.  weight: [A * C, F] or the conv's [A * C, F, 1, 1]; sample: a dict `synth.sample()` returned,
+    None: one is drawn (the draw counter advances)."""
+    from .effdet import meta_ops
+    C = reg.num_classes
+    if synth.C != C:
+        raise ValueError('the sampler has %d classes, the regulariser %d' % (synth.C, C))
+    if weight.dim() not in (2, 4) or weight.shape[1] != synth.F or weight.shape[0] % C or weight.numel() != weight.shape[0] * synth.F:
+        raise ValueError('weight must be [A * %d, %d] or [A * %d, %d, 1, 1]' % (C, synth.F, C, synth.F))
+    if weight.device.type != 'cuda':
+        raise RuntimeError('virtual_outlier_loss: weight must be a GPU tensor (no CPU fallback)')
+    A = weight.shape[0] // C
+    if bias is not None and tuple(bias.shape) != (A * C,):
+        raise ValueError('bias must be [%d]' % (A * C))
+    loss, stats = reg(class_out, roles)
+    s = synth.sample() if sample is None else sample
+    rows = s['rows'].detach()
+    m = rows.shape[0] * rows.shape[1]
+    v_logits = meta_ops.Linear.apply(rows.view(m, synth.F), weight.view(A * C, synth.F), bias).view(1, m * A, C)
+    v_roles = s['roles'].view(m, 1).expand(m, A).reshape(1, m * A)
+    v_loss, v_stats = reg(v_logits, v_roles)
+    stats = dict(stats, n_virtual=v_stats['n_out'], mean_l_virtual=v_stats['mean_l_out'], mean_energy_virtual=v_stats['mean_energy_out'])
+    return loss + v_loss, stats

@@ -28,7 +28,8 @@ def set_bn_eval(module):
 
 class PretrainStep(object):
     def __init__(self, model, lr=1e-3, max_grad_norm=10.0, alpha=0.15, box_loss_weight=50.0, freeze_bn=False,
-                 labeler=True, graph=False, graph_warmup=2, optimizer=None, ood_regularizer=None, ood_background='none'):
+                 labeler=True, graph=False, graph_warmup=2, optimizer=None, ood_regularizer=None, ood_background='none',
+                 outlier_synthesizer=None, synth_refresh_every=100, synth_shrinkage=0.0):
         """graph=True: after `graph_warmup` eager iterations the whole iteration (zero_grad, forward, loss, backward and -
         single GPU - clip + Adam) is captured into one hipGraph and replayed; the ~5 000 launches of a step then cost one
         submission.  Shapes must stay fixed; labels are assigned eagerly and copied into the graph's static buffers.
@@ -38,7 +39,14 @@ class PretrainStep(object):
         ood_regularizer: an `ood_train.EnergyRegularizer`; target['outlier'] ([B] bool) then names the outlier-exposure images, the
         roles of the anchors are formed next to the labels (`ood_train.anchor_roles`, background=ood_background), the loss is the
         detection loss plus the regulariser's, and the returned dict gains 'ood_loss' and the regulariser's statistics.  The default
-        FlatAdam then covers the model's parameters followed by the regulariser's; a caller's optimizer covers them or not."""
+        FlatAdam then covers the model's parameters followed by the regulariser's; a caller's optimizer covers them or not.
+        outlier_synthesizer: an `ood_synth.OutlierSynthesizer` (needs an ood_regularizer; VOS, Du et al. 2022).  Every step adds the
+        penultimate features of the class head at the positive anchors to its statistics (no synchronisation); after every
+        `synth_refresh_every` steps `fit(synth_shrinkage)` runs - the one host read, outside any graph, raising like
+        `FeatureOOD.fit`; once a fit exists the regulariser's term is `ood_train.virtual_outlier_loss`, the virtual rows pushed
+        through class_net.predict.conv_pw, and the returned dict gains n_virtual, mean_l_virtual and mean_energy_virtual.
+        target['outlier'] is then optional (default: no outlier image).  With graph=True the steps before the first fit run
+        eagerly; the capture holds the virtual side and reads a later fit from the buffers `fit` writes in place."""
         from .effdet.anchors import Anchors, AnchorLabeler
         from .effdet.config import set_config_writeable
         from .effdet.loss import DetectionLoss
@@ -54,6 +62,17 @@ class PretrainStep(object):
         self.loss_fn = DetectionLoss(cfg)
         self._grouped = optimizer is not None
         self.ood, self.ood_background = ood_regularizer, ood_background
+        self.synth, self.synth_refresh_every, self.synth_shrinkage = outlier_synthesizer, int(synth_refresh_every), float(synth_shrinkage)
+        if self.synth is not None:
+            if self.ood is None:
+                raise ValueError('an outlier_synthesizer needs an ood_regularizer')
+            if self.synth_refresh_every < 1:
+                raise ValueError('synth_refresh_every must be >= 1')
+            pw = model.class_net.predict.conv_pw
+            if (self.synth.C, self.synth.F) != (cfg.num_classes, pw.weight.shape[1]) or pw.weight.shape[0] != self.synth.A * self.synth.C:
+                raise ValueError('the outlier_synthesizer must have the class head\'s num_classes, width and anchors per cell')
+        self._synth_steps = 0                   # steps since the synthesiser was given: fit after every synth_refresh_every-th
+        self._synth_eager = 0                   # eager steps that ran the virtual side (one comes before a capture)
         if self._grouped:
             self.opt = optimizer
         elif self.ood is None:
@@ -91,10 +110,30 @@ class PretrainStep(object):
         """with a regulariser: the int8 [B, N] role of every anchor from the labels and target['outlier'], else None"""
         if self.ood is None:
             return None
-        if 'outlier' not in target:
-            raise ValueError("an ood_regularizer needs target['outlier'], a [B] bool tensor")
         from .ood_train import anchor_roles
+        if 'outlier' not in target:
+            if self.synth is None:
+                raise ValueError("an ood_regularizer needs target['outlier'], a [B] bool tensor")
+            return anchor_roles(cls_t, torch.zeros(cls_t[0].shape[0], dtype=torch.bool, device=cls_t[0].device), self.ood_background)
         return anchor_roles(cls_t, target['outlier'].to(cls_t[0].device), self.ood_background)
+
+    def _ood_terms(self, class_out, cls_t, roles):
+        """the regulariser's loss and statistics; with a synthesiser the positives' penultimate features join its statistics and,
+        once it is fitted, the virtual outliers join the loss"""
+        if self.synth is None:
+            return self.ood(class_out, roles)
+        self.synth.add_targets(self.model._train_engine.class_penultimate(), cls_t)
+        if not self.synth.fitted:
+            return self.ood(class_out, roles)
+        from .ood_train import virtual_outlier_loss
+        pw = self.model.class_net.predict.conv_pw
+        return virtual_outlier_loss(self.ood, class_out, roles, self.synth, pw.weight, pw.bias)
+
+    def _synth_refresh(self):
+        if self.synth is not None:
+            self._synth_steps += 1
+            if self._synth_steps % self.synth_refresh_every == 0:
+                self.synth.fit(self.synth_shrinkage)
 
     def detections(self, class_out, box_out):
         """pretrain.py:238-245: _post_process + generate_detections(hard NMS, no clipping) for the whole batch.
@@ -151,7 +190,7 @@ class PretrainStep(object):
             loss, class_loss, box_loss = self.loss_fn(class_out, box_out, s_cls, s_box, s_np)
             ood = None
             if s_roles is not None:
-                ood_loss, ood_stats = self.ood(class_out, s_roles)
+                ood_loss, ood_stats = self._ood_terms(class_out, s_cls, s_roles)
                 loss = loss + ood_loss
                 ood = dict(ood_stats, ood_loss=ood_loss.detach())
             loss.backward()
@@ -204,6 +243,7 @@ class PretrainStep(object):
                'grad_norm': None if outs[3] is None else outs[3].clone()}
         if roles is not None:
             res.update({k: v.clone() for k, v in self._cap_ood[1].items()})
+        self._synth_refresh()
         return res
 
     def _allreduce(self, time_allreduce):
@@ -223,6 +263,8 @@ class PretrainStep(object):
         eng = self.model._train_engine
         if eng is not None:
             eng.direct_grad = True          # FlatAdam owns every .grad (views of one flat buffer): add into them directly
+            if self.synth is not None:
+                eng.keep_penultimate = True
 
     def __call__(self, x, target, time_allreduce=False, evaluator=None):
         model, opt = self.model, self.opt
@@ -238,7 +280,14 @@ class PretrainStep(object):
                 self._static_base = None
                 self._calls = 1
         self._engine_flags()
-        if self.graph and evaluator is None and self._calls > self._graph_warmup:
+        use_graph = self.graph and evaluator is None and self._calls > self._graph_warmup
+        if self.synth is not None and self.graph:
+            if not self.synth.fitted:
+                # no fit (yet, or after a clear()): the step has no virtual side, so it runs eagerly, and a capture that holds one goes
+                use_graph, self._cap, self._static_base, self._synth_eager = False, None, None, 0
+            elif self._synth_eager < 1:
+                use_graph = False               # the virtual side runs eagerly once before it is captured (its workspaces exist then)
+        if use_graph:
             cls_t, box_t, npos = self.targets(target)
             roles = self.roles(target, cls_t)
             if self._cap is None:
@@ -252,9 +301,11 @@ class PretrainStep(object):
         loss, class_loss, box_loss = self.loss_fn(class_out, box_out, cls_t, box_t, npos)
         ood = None
         if roles is not None:
-            ood_loss, ood_stats = self.ood(class_out, roles)
+            ood_loss, ood_stats = self._ood_terms(class_out, cls_t, roles)
             loss = loss + ood_loss
             ood = dict(ood_stats, ood_loss=ood_loss.detach())
+            if self.synth is not None and self.synth.fitted:
+                self._synth_eager += 1
         loss.backward()
         if evaluator is not None:
             self.evaluate(class_out, box_out, target, evaluator)
@@ -265,4 +316,5 @@ class PretrainStep(object):
         res = {'loss': loss.detach(), 'class_loss': class_loss, 'box_loss': box_loss, 'grad_norm': norm}
         if ood is not None:
             res.update(ood)
+        self._synth_refresh()
         return res

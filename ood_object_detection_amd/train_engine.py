@@ -505,6 +505,8 @@ class TrainEngine(object):
         self._stage = None                          # the stage whose forward / backward is running (None: called from outside, e.g. meta_grad)
         self.use_tables = True          # False (effdet/meta_grad.py): every derived weight / gradient conv by conv, nothing recorded
         self.direct_grad = False        # True: parameter gradients are added into existing `.grad`s by one multi-tensor launch
+        self.keep_penultimate = False   # True: the class head's forward leaves the input of its last pointwise map (class_penultimate)
+        self._penultimate = None
 
     def _const(self, C, v):
         key = (C, v)
@@ -1097,6 +1099,19 @@ class TrainEngine(object):
         hrec['predict'] = dict(x=t, taps=taps, d=d, W=Wp, Wt=self._transposed(name + 'predict.conv_pw.weight^T', Wp),
                                has_bias=bias is not None, pk=pk,
                                wshape=head.predict.conv_pw.weight.shape, dwshape=head.predict.conv_dw.weight.shape)
+        if self.keep_penultimate and head is self.model.class_net:
+            self._penultimate = (lv, d, t)
+
+    def class_penultimate(self, tower=False):
+        """The penultimate features of the class head of the last training forward (needs `keep_penultimate`): the output of
+        class_net.predict.conv_dw, of which a cell's A * C logits are an affine map (predict.conv_pw).  The packed tensor is
+        level-major ([B * h_l * w_l, F] per level, one behind the other), so the result is a list of per-level [B, F, h, w] views
+        (channel stride 1) in the order of the head outputs and of the labeler's targets.  Read-only: detached, no copy.
+        tower=True: the input of that depthwise conv instead, the output of the head's tower, in the same form."""
+        if self._penultimate is None:
+            raise RuntimeError('class_penultimate: set keep_penultimate and run a training forward with the class head first')
+        lv, d, t = self._penultimate
+        return [v.permute(0, 3, 1, 2) for v in lv.split((t if tower else d).detach())]
 
     def _head_bwd(self, lv, hrec, g, grads):
         """-> d packed pyramid [B * P, F]; parameter gradients into `grads` (conv weights: one reduction over all levels)"""

@@ -64,6 +64,8 @@ DEV float wave_reduce_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(
 static inline float __int_as_float(int v) { float f; std::memcpy(&f, &v, 4); return f; }
 static inline int __float_as_int(float f) { int v; std::memcpy(&v, &f, 4); return v; }
 static inline unsigned __float_as_uint(float f) { unsigned v; std::memcpy(&v, &f, 4); return v; }
+// the high word of a 32 x 32 -> 64 bit product (csrc/outlier_synth.hip: Philox4x32)
+static inline unsigned __umulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
 template <class K, class... A>
 void sim_launch(K kernel, dim3 grid, dim3 block, A... args) {
     const int nt = block.x, nw = (nt + 63) / 64;
