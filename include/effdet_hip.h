@@ -155,6 +155,25 @@ int effdet_pw_gemm_bn_act(void* stream, int dtype, const void* A, long long M, i
 int effdet_pw_gemm_group(void* stream, int dtype, int n, const void* const* A, const long long* M, const int* K,
                          const void* const* W, const int* N, const float* const* scale, const float* const* shift,
                          int act, void* const* C);
+/* Host-only: the kernel instantiation and geometry an effdet_pw_gemm_bn_act call of this shape runs - answered by the launcher's
+ * own dispatch, which describes its choice instead of launching.  gated / has_residual: the pointer is present; `aligned` != 0:
+ * A, W, C and the residual are 32-byte aligned (with N, ldc and c_image_stride this decides vec_ok; two-term calls are refused
+ * without it); rows_per_image, ldc, c_image_stride: 0 for the defaults, as in the launch.  group != 0: the call is a group launch
+ * of this one problem (no gate, no residual, a dense output, BN <= 96).  Contract of effdet_sepconv_plan_describe: fills
+ * min(n, EFFDET_PW_GEMM_PLAN_INTS) ints of `out` and returns that count, or EFFDET_EINVAL (out == NULL, n <= 0, or anything the
+ * launch refuses from the shape); a pad flag in dtype is ignored.  Slots:
+ *    0  BN: output channels per workgroup as instantiated;  1  PT: 16-pixel tiles per wave;  2  NTH: threads per workgroup
+ *    3  GATED;  4  tiles_per_image (128-pixel tiles);  5  n_tiles (output-channel tiles);  6  workgroups of the launch
+ *    7  small: the launch has fewer than 512 workgroups (PT 1, NTH 512 unless BN is 128)
+ *    8  vec_ok: residual loads and output stores are 8-channel vectors
+ *    9  K-chunks;  10  pipeline stages (nst);  11  LDS bytes, static + dynamic;  12  K values per K-chunk
+ * effdet_pw_gemm_group_plan_describe: the same for an effdet_pw_gemm_group call of n_problems problems; slots 4, 5, 8, 9, 10
+ * are those of problem `which`, slot 6 counts the whole launch. */
+#define EFFDET_PW_GEMM_PLAN_INTS 13
+int effdet_pw_gemm_plan_describe(int dtype, long long M, int K, int N, int rows_per_image, int gated, int has_residual,
+                                 long long ldc, long long c_image_stride, int aligned, int group, int* out, int n);
+int effdet_pw_gemm_group_plan_describe(int dtype, int n_problems, const long long* M, const int* K, const int* N, int aligned,
+                                       int which, int* out, int n);
 
 /* depthwise k x k (k = 3|5, stride 1|2, TF-SAME) + folded BN + SiLU.  Wt: [k*k][C] fp32.
  * If pool_partial != NULL it receives [B][effdet_dwconv_blocks_per_image(Ho,Wo,C)][C] partial sums of
@@ -163,6 +182,14 @@ int effdet_dwconv_bn_act(void* stream, int dtype, const void* X, void* Y, const 
                          const float* scale, const float* shift, int act, float* pool_partial,
                          int B, int H, int W, int C, int k, int stride);
 int effdet_dwconv_blocks_per_image(int Ho, int Wo, int C);
+/* Host-only: the geometry an effdet_dwconv_bn_act call on an H x W x C map runs (pooled != 0: with pool_partial), from the
+ * function the launch itself uses; contract of effdet_pw_gemm_plan_describe (the pad flag in dtype selects pad_t / pad_l and is
+ * otherwise stripped).  Slots:
+ *    0  KS;  1  nz: channel slices (grid.z);  2  CG: 8-channel groups per workgroup;  3  PT: pixels in flight per workgroup
+ *    4  threads per workgroup;  5  pixels per workgroup;  6  workgroups per image and slice (= effdet_dwconv_blocks_per_image)
+ *    7  pad_t;  8  pad_l;  9  LDS bytes */
+#define EFFDET_DWCONV_PLAN_INTS 10
+int effdet_dwconv_plan_describe(int dtype, int H, int W, int C, int k, int stride, int pooled, int* out, int n);
 
 /* Fused front half of an inverted-residual block: expand 1x1 (MFMA) + BN + SiLU -> depthwise k x k
  * (TF-SAME, stride 1|2) + BN + SiLU; the expanded activation never leaves LDS.  W1: [mid][Cin] (dtype),

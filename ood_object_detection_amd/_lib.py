@@ -43,6 +43,9 @@ SIGNATURES = {
     'effdet_dwconv_bn_act': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     'effdet_dwconv_blocks_per_image': (c_int, [c_int, c_int, c_int]),
+    'effdet_dwconv_plan_describe': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, P(c_int), c_int]),
+    'effdet_pw_gemm_plan_describe': (c_int, [c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll, c_int, c_int, P(c_int), c_int]),
+    'effdet_pw_gemm_group_plan_describe': (c_int, [c_int, c_int, P(c_ll), P(c_int), P(c_int), c_int, c_int, P(c_int), c_int]),
     'effdet_mbconv_gated_tiles_per_image': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'effdet_mbconv_expand_dw_gated': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -346,8 +346,9 @@ extern "C" int effdet_normalize_u8(void* stream, int out_dtype, const unsigned c
     return effdet_check_launch();
 }
 
-// Geometry helper shared with the host: how many partial-sum blocks per image the depthwise kernel
-// uses for an output of Ho x Wo pixels and C channels.
+// Geometry of the depthwise launch for an output of Ho x Wo pixels and C channels, stated once for the launch, for
+// effdet_dwconv_blocks_per_image (how many partial-sum rows per image the host sizes its buffers by) and for
+// effdet_dwconv_plan_describe.
 // channel slices (grid.z) so that one workgroup handles at most 256 groups of 8 channels
 static inline int dw_slices(int C) {
     const int cg = C / 8;
@@ -355,18 +356,31 @@ static inline int dw_slices(int C) {
     return 1;
 }
 
-extern "C" int effdet_dwconv_blocks_per_image(int Ho, int Wo, int C) {
+struct DwGeom { int nz, CG, PT, threads, pix_per_block, blocks_per_image; };
+
+static int dw_geometry(int Ho, int Wo, int C, DwGeom& g) {
     if (Ho <= 0 || Wo <= 0 || C <= 0 || C % 8) return EFFDET_EINVAL;
-    const int CG = C / 8 / dw_slices(C), PT = 256 / CG;
+    g.nz = dw_slices(C);
+    g.CG = C / 8 / g.nz; g.PT = 256 / g.CG;
+    g.threads = g.CG * g.PT;
     const int npix = Ho * Wo;
-    int ppb = PT * 8;                                     // 8 pixels per thread
-    if (ppb > npix) ppb = ((npix + PT - 1) / PT) * PT;
-    return (npix + ppb - 1) / ppb;
+    int ppb = g.PT * 8;                                   // 8 pixels per thread
+    if (ppb > npix) ppb = ((npix + g.PT - 1) / g.PT) * g.PT;
+    g.pix_per_block = ppb;
+    g.blocks_per_image = (npix + ppb - 1) / ppb;
+    return EFFDET_OK;
 }
 
+extern "C" int effdet_dwconv_blocks_per_image(int Ho, int Wo, int C) {
+    DwGeom g;
+    const int rc = dw_geometry(Ho, Wo, C, g);
+    return rc != EFFDET_OK ? rc : g.blocks_per_image;
+}
+
+// `plan` set: fill the slots of effdet_dwconv_plan_describe instead of launching (pointers are not looked at)
 static int launch_dwconv(void* stream, int dtype, const void* X, void* Y, const float* Wt,
                          const float* scale, const float* shift, int act, float* pool_partial,
-                         int B, int H, int W, int C, int k, int stride) {
+                         int B, int H, int W, int C, int k, int stride, int* plan = nullptr) {
     const int sym = take_pad_flag(dtype);
     if (!X || !Y || !Wt || !scale || !shift || B <= 0 || H <= 0 || W <= 0) return EFFDET_EINVAL;
     if (C <= 0 || C % 8 || (k != 3 && k != 5) || (stride != 1 && stride != 2)) return EFFDET_EINVAL;
@@ -377,15 +391,19 @@ static int launch_dwconv(void* stream, int dtype, const void* X, void* Y, const 
     a.B = B; a.H = H; a.W = W; a.C = C; a.k = k; a.stride = stride; a.act = act;
     a.Ho = same_out(H, stride); a.Wo = same_out(W, stride);
     a.pad_t = pad_before(H, k, stride, sym); a.pad_l = pad_before(W, k, stride, sym);
-    const int nz = dw_slices(C);
-    a.CG = C / 8 / nz; a.PT = 256 / a.CG;
-    const int npix = a.Ho * a.Wo;
-    int ppb = a.PT * 8;
-    if (ppb > npix) ppb = ((npix + a.PT - 1) / a.PT) * a.PT;
-    a.pix_per_block = ppb;
-    a.blocks_per_image = (npix + ppb - 1) / ppb;
-    dim3 grid(a.blocks_per_image, B, nz), block(a.CG * a.PT);
+    DwGeom g;
+    const int rc = dw_geometry(a.Ho, a.Wo, C, g);
+    if (rc != EFFDET_OK) return rc;
+    a.CG = g.CG; a.PT = g.PT;
+    a.pix_per_block = g.pix_per_block;
+    a.blocks_per_image = g.blocks_per_image;
+    dim3 grid(a.blocks_per_image, B, g.nz), block(g.threads);
     const size_t sh = pool_partial ? (size_t)a.PT * a.CG * 8 * sizeof(float) : 0;
+    if (plan) {
+        const int v[EFFDET_DWCONV_PLAN_INTS] = {k, g.nz, g.CG, g.PT, g.threads, g.pix_per_block, g.blocks_per_image, a.pad_t, a.pad_l, (int)sh};
+        for (int i = 0; i < EFFDET_DWCONV_PLAN_INTS; ++i) plan[i] = v[i];
+        return EFFDET_OK;
+    }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype == 0) {
         if (k == 3) hipLaunchKernelGGL((dwconv_kernel<float, 3>), grid, block, sh, st, a);
@@ -398,6 +416,18 @@ static int launch_dwconv(void* stream, int dtype, const void* X, void* Y, const 
         else hipLaunchKernelGGL((dwconv_kernel<bf16p_t, 5>), grid, block, sh, st, a);
     }
     return effdet_check_launch();
+}
+
+extern "C" int effdet_dwconv_plan_describe(int dtype, int H, int W, int C, int k, int stride, int pooled, int* out, int n) {
+    if (!out || n <= 0) return EFFDET_EINVAL;
+    alignas(16) static float present[4];                             // stand-in for every pointer: present, 16-byte aligned
+    int plan[EFFDET_DWCONV_PLAN_INTS];
+    const int rc = launch_dwconv(nullptr, dtype, present, present, present, present, present, 0, pooled ? present : nullptr,
+                                 1, H, W, C, k, stride, plan);
+    if (rc != EFFDET_OK) return rc;
+    const int m = n < EFFDET_DWCONV_PLAN_INTS ? n : EFFDET_DWCONV_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = plan[i];
+    return m;
 }
 
 extern "C" int effdet_dwconv_bn_act(void* stream, int dtype, const void* X, void* Y, const float* Wt,

@@ -36,6 +36,17 @@ template <int V> struct PwInt { static constexpr int value = V; };
 
 constexpr int PW_PIX = 128;                      // pixels per workgroup: 4 waves x 2 MFMA tiles, or 8 waves x 1 (small maps)
 
+// K-chunks per pipeline stage, bytes of an LDS weight row and of the double-buffered weight image, and the K-chunk / stage
+// counts of a K: stated once for the kernel and for effdet_pw_gemm_plan_describe
+template <typename T, int BN> struct PwGeom {
+    static constexpr int KCH = IsPair<T>::value ? 1 : 2;
+    static constexpr int ROWB = KCH * OpGeom<T>::CHUNK + 16;
+    static constexpr int W_BYTES = BN * ROWB;
+    static constexpr int LDS_BYTES = 2 * W_BYTES;
+    __host__ __device__ static inline int chunks(int K) { return (K + OpGeom<T>::KPC - 1) / OpGeom<T>::KPC; }
+    __host__ __device__ static inline int stages(int K) { return (chunks(K) + KCH - 1) / KCH; }
+};
+
 // PT 16-pixel tiles per wave, NTH threads: (2, 256) normally; (1, 512) when the launch has fewer than two workgroups per
 // CU (20x20 maps) - twice the waves per SIMD to hide the per-stage latencies, at the price of reading each W
 // fragment from LDS once per 16 instead of once per 32 pixels
@@ -45,7 +56,7 @@ DEV void pw_gemm_body(const PwArgs& p, const int bid) {
     // (two-term bf16: ONE 128-byte chunk = 32 K values in two terms per stage - the same bytes per pixel and stage, and the same
     // number of operand registers in the A ring, as the two 64-byte chunks of the other dtypes)
     constexpr bool PAIR = IsPair<T>::value;
-    constexpr int KCH = PAIR ? 1 : 2;
+    constexpr int KCH = PwGeom<T, BN>::KCH;
     constexpr int EPC = VecTraits<T>::EPC;          // elements per operand piece
     constexpr int KPC = OpGeom<T>::KPC;             // elements per K-chunk
     constexpr int PB = OpGeom<T>::PIECE, CB = OpGeom<T>::CHUNK;   // bytes of a lane's operand piece / of a K-chunk (16 / 64; two-term: 32 / 128)
@@ -55,9 +66,10 @@ DEV void pw_gemm_body(const PwArgs& p, const int bid) {
     // left over by the accumulators allow - the late layers are latency bound, not bandwidth bound
     // two stages everywhere (four in the 512-thread small-map form were measured slower on d0 blocks 5.x: 0.042 against 0.035 ms)
     constexpr int PF = 2;
-    constexpr int ROWB = KCH * CB + 16;             // bytes per LDS row: one stage of K + 16 pad
-    constexpr int W_BYTES = BN * ROWB;
-    __shared__ __attribute__((aligned(16))) char lds[2 * W_BYTES];
+    constexpr int ROWB = PwGeom<T, BN>::ROWB;       // bytes per LDS row: one stage of K + 16 pad
+    constexpr int W_BYTES = PwGeom<T, BN>::W_BYTES;
+    static_assert(ROWB == KCH * CB + 16, "one stage of K + 16 pad");
+    __shared__ __attribute__((aligned(16))) char lds[PwGeom<T, BN>::LDS_BYTES];
     extern __shared__ __attribute__((aligned(16))) float gate_lds[];   // GATED: this image's SE gate, all K channels (dynamic: K floats)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -70,8 +82,7 @@ DEV void pw_gemm_body(const PwArgs& p, const int bid) {
     const int n0 = nt * BN;
     const int n_count = (N - n0) < BN ? (N - n0) : BN;
     const long long pitch = (long long)K * (long long)sizeof(T);
-    const int nkc = (K + KPC - 1) / KPC;            // K-chunks
-    const int nst = (nkc + KCH - 1) / KCH;          // pipeline stages
+    const int nst = PwGeom<T, BN>::stages(K);       // pipeline stages
     const int kbytes = K * (int)sizeof(T);
 
     // ---- this lane's two pixels (B operand columns): pointers into A, clamped inside the image
@@ -311,8 +322,20 @@ int pw_prepare(PwArgs& a, int& bn, long long& blocks) {
     return EFFDET_OK;
 }
 
+// effdet_pw_gemm_plan_describe: the instantiation and geometry a launch would run (slots in include/effdet_hip.h)
+struct PwPlan { int v[EFFDET_PW_GEMM_PLAN_INTS]; };
+
+template <typename T, int BN, int PT, int NTH, bool GATED>
+void pw_plan_fill(PwPlan* plan, const PwArgs& a, long long blocks, bool small, size_t dyn) {
+    const int v[EFFDET_PW_GEMM_PLAN_INTS] = {BN, PT, NTH, GATED ? 1 : 0, a.tiles_per_image, a.n_tiles, (int)blocks, small ? 1 : 0, a.vec_ok,
+                                             PwGeom<T, BN>::chunks(a.K), PwGeom<T, BN>::stages(a.K), PwGeom<T, BN>::LDS_BYTES + (int)dyn,
+                                             OpGeom<T>::KPC};
+    for (int i = 0; i < EFFDET_PW_GEMM_PLAN_INTS; ++i) plan->v[i] = v[i];
+}
+
+// `plan` set (here and in launch_pw): describe the choice - problem `which` of a group - instead of launching
 template <typename T>
-int launch_pw_group(hipStream_t st, PwGroupArgs& g) {
+int launch_pw_group(hipStream_t st, PwGroupArgs& g, PwPlan* plan = nullptr, int which = 0) {
     int bn0 = 0;
     long long total = 0;
     for (int i = 0; i < g.n; ++i) {
@@ -327,8 +350,9 @@ int launch_pw_group(hipStream_t st, PwGroupArgs& g) {
     g.first[g.n] = (int)total;
     dim3 grid((unsigned)total);
     const bool small = total < 512;
-#define PWG_LAUNCH(BN_) do { if (small && BN_ != 128) hipLaunchKernelGGL((pw_gemm_group_kernel<T, BN_ == 128 ? 96 : BN_, 1, 512>), grid, dim3(512), 0, st, g); \
-                             else hipLaunchKernelGGL((pw_gemm_group_kernel<T, BN_, 2, 256>), grid, dim3(256), 0, st, g); } while (0)
+#define PWG_FORM(BN_, PT_, NTH_) do { if (plan) pw_plan_fill<T, BN_, PT_, NTH_, false>(plan, g.p[which], total, small, 0); \
+                                      else hipLaunchKernelGGL((pw_gemm_group_kernel<T, BN_, PT_, NTH_>), grid, dim3(NTH_), 0, st, g); } while (0)
+#define PWG_LAUNCH(BN_) do { if (small) PWG_FORM(BN_, 1, 512); else PWG_FORM(BN_, 2, 256); } while (0)
     switch (bn0) {
         case 32:  PWG_LAUNCH(32); break;
         case 64:  PWG_LAUNCH(64); break;
@@ -336,11 +360,12 @@ int launch_pw_group(hipStream_t st, PwGroupArgs& g) {
         default: return EFFDET_EINVAL;                                          // lateral convs are 64-88 wide (d0-d2); wider: one launch each
     }
 #undef PWG_LAUNCH
-    return effdet_check_launch();
+#undef PWG_FORM
+    return plan ? EFFDET_OK : effdet_check_launch();
 }
 
 template <typename T>
-int launch_pw(hipStream_t st, PwArgs& a) {
+int launch_pw(hipStream_t st, PwArgs& a, PwPlan* plan = nullptr) {
     // output-channel tile: the smallest of {32, 64, 96, 128, 160, 192} that covers N, else equal tiles <= 192
     int bn; long long blocks;
     const int rc0 = pw_prepare<T>(a, bn, blocks);
@@ -349,8 +374,10 @@ int launch_pw(hipStream_t st, PwArgs& a) {
     const bool small = blocks < 512;                 // fewer than two workgroups per CU: 8 waves x 16 pixels each
     const bool gated = a.gate != nullptr;
     const size_t dyn = gated ? ((size_t)a.K * 4 + 15) / 16 * 16 : 0;          // the SE gate's LDS copy
-#define PW_LAUNCH_G(BN_, G_) do { if (small && BN_ != 128) hipLaunchKernelGGL((pw_gemm_kernel<T, BN_ == 128 ? 96 : BN_, 1, 512, G_>), grid, dim3(512), dyn, st, a); /* the (128, 1, 512) instantiation spills */ \
-                            else hipLaunchKernelGGL((pw_gemm_kernel<T, BN_, 2, 256, G_>), grid, dim3(256), dyn, st, a); } while (0)
+#define PW_FORM(BN_, PT_, NTH_, G_) do { if (plan) pw_plan_fill<T, BN_, PT_, NTH_, G_>(plan, a, blocks, small, dyn); \
+                                         else hipLaunchKernelGGL((pw_gemm_kernel<T, BN_, PT_, NTH_, G_>), grid, dim3(NTH_), dyn, st, a); } while (0)
+#define PW_LAUNCH_G(BN_, G_) do { if (small && BN_ != 128) PW_FORM(BN_ == 128 ? 96 : BN_, 1, 512, G_); /* the (128, 1, 512) instantiation spills */ \
+                                  else PW_FORM(BN_, 2, 256, G_); } while (0)
 #define PW_LAUNCH(BN_) do { if (gated) PW_LAUNCH_G(BN_, true); else PW_LAUNCH_G(BN_, false); } while (0)
     switch (bn) {
         case 32:  PW_LAUNCH(32); break;
@@ -363,7 +390,56 @@ int launch_pw(hipStream_t st, PwArgs& a) {
     }
 #undef PW_LAUNCH
 #undef PW_LAUNCH_G
-    return effdet_check_launch();
+#undef PW_FORM
+    return plan ? EFFDET_OK : effdet_check_launch();
+}
+
+// Everything a single launch refuses, and its defaults (rows_per_image / ldc / c_image_stride <= 0), before the dispatch:
+// shared by effdet_pw_gemm_bn_act and effdet_pw_gemm_plan_describe
+int pw_single(hipStream_t st, int dtype, PwArgs& a, PwPlan* plan) {
+    if (!a.A || !a.W || !a.C || !a.shift || a.M <= 0 || a.K <= 0 || a.N <= 0) return EFFDET_EINVAL;
+    if (a.K % 8 != 0 || a.M > 0x7fffffffLL) return EFFDET_EINVAL;   // 16-byte pieces along K; 32-bit row arithmetic
+    if (a.act < 0 || a.act > 2) return EFFDET_EINVAL;                  // 0 none, 1 SiLU, 2 ReLU
+    if (a.rows_per_image <= 0) a.rows_per_image = (int)a.M;
+    if ((a.M % a.rows_per_image) != 0) return EFFDET_EINVAL;         // workgroups never straddle images
+    if (a.ldc <= 0) a.ldc = a.N;
+    if (a.c_image_stride <= 0) a.c_image_stride = (long long)a.rows_per_image * a.ldc;
+    if (dtype == 0) return launch_pw<float>(st, a, plan);
+    if (dtype == 1) return launch_pw<bf16_t>(st, a, plan);
+    if (dtype == 2) {                                              // two-term bf16: whole 8-channel groups, 32-byte aligned rows
+        if (a.N % 8 || a.ldc % 8 || a.c_image_stride % 8 || reinterpret_cast<uintptr_t>(a.A) % 32 || reinterpret_cast<uintptr_t>(a.W) % 32 ||
+            reinterpret_cast<uintptr_t>(a.C) % 32 || (a.res && reinterpret_cast<uintptr_t>(a.res) % 32)) return EFFDET_EINVAL;
+        return launch_pw<bf16p_t>(st, a, plan);
+    }
+    return EFFDET_EINVAL;
+}
+
+// the same for a group launch
+int pw_group(hipStream_t st, int dtype, int n, const void* const* A, const long long* M, const int* K, const void* const* W, const int* N,
+             const float* const* scale, const float* const* shift, int act, void* const* C, PwPlan* plan, int which) {
+    if (n < 1 || n > PW_GROUP_MAX || !A || !M || !K || !W || !N || !scale || !shift || !C || act < 0 || act > 2) return EFFDET_EINVAL;
+    if (which < 0 || which >= n) return EFFDET_EINVAL;
+    PwGroupArgs g;
+    g.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (!A[i] || !W[i] || !C[i] || !shift[i] || M[i] <= 0 || M[i] > 0x7fffffffLL || K[i] <= 0 || K[i] % 8 || N[i] <= 0) return EFFDET_EINVAL;
+        g.p[i] = PwArgs{A[i], M[i], K[i], W[i], N[i], scale[i], shift[i], act, nullptr, nullptr, (int)M[i], C[i], M[i] * N[i], N[i], 0, 0, 0};
+    }
+    if (dtype == 0) return launch_pw_group<float>(st, g, plan, which);
+    if (dtype == 1) return launch_pw_group<bf16_t>(st, g, plan, which);
+    if (dtype == 2) {
+        for (int i = 0; i < n; ++i)
+            if (N[i] % 8 || reinterpret_cast<uintptr_t>(A[i]) % 32 || reinterpret_cast<uintptr_t>(W[i]) % 32 || reinterpret_cast<uintptr_t>(C[i]) % 32)
+                return EFFDET_EINVAL;
+        return launch_pw_group<bf16p_t>(st, g, plan, which);
+    }
+    return EFFDET_EINVAL;
+}
+
+int pw_plan_out(const PwPlan& plan, int* out, int n) {
+    const int m = n < EFFDET_PW_GEMM_PLAN_INTS ? n : EFFDET_PW_GEMM_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = plan.v[i];
+    return m;
 }
 
 }  // namespace
@@ -376,23 +452,8 @@ extern "C" int effdet_pw_gemm_bn_act(void* stream, int dtype,
                                      const float* gate, int rows_per_image,
                                      void* C, long long c_image_stride, long long ldc) {
     EFFDET_ENTER();
-    if (!A || !W || !C || !shift || M <= 0 || K <= 0 || N <= 0) return EFFDET_EINVAL;
-    if (K % 8 != 0 || M > 0x7fffffffLL) return EFFDET_EINVAL;   // 16-byte pieces along K; 32-bit row arithmetic
-    if (act < 0 || act > 2) return EFFDET_EINVAL;                  // 0 none, 1 SiLU, 2 ReLU
-    if (rows_per_image <= 0) { rows_per_image = (int)(M > 0x7fffffffLL ? 0x7fffffff : M); }
-    if ((M % rows_per_image) != 0) return EFFDET_EINVAL;         // workgroups never straddle images
-    if (ldc <= 0) ldc = N;
-    if (c_image_stride <= 0) c_image_stride = (long long)rows_per_image * ldc;
     PwArgs a{A, M, K, W, N, scale, shift, act, residual, gate, rows_per_image, C, c_image_stride, ldc, 0, 0, 0};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == 0) return launch_pw<float>(st, a);
-    if (dtype == 1) return launch_pw<bf16_t>(st, a);
-    if (dtype == 2) {                                              // two-term bf16: whole 8-channel groups, 32-byte aligned rows
-        if (N % 8 || ldc % 8 || c_image_stride % 8 || reinterpret_cast<uintptr_t>(A) % 32 || reinterpret_cast<uintptr_t>(W) % 32 ||
-            reinterpret_cast<uintptr_t>(C) % 32 || (residual && reinterpret_cast<uintptr_t>(residual) % 32)) return EFFDET_EINVAL;
-        return launch_pw<bf16p_t>(st, a);
-    }
-    return EFFDET_EINVAL;
+    return pw_single(reinterpret_cast<hipStream_t>(stream), dtype, a, nullptr);
 }
 
 // n independent GEMMs (no gate, no residual, dense outputs) in one launch; all N must select the same output tile (<= 96).
@@ -401,21 +462,38 @@ extern "C" int effdet_pw_gemm_group(void* stream, int dtype, int n, const void* 
                                     const void* const* W, const int* N, const float* const* scale, const float* const* shift,
                                     int act, void* const* C) {
     EFFDET_ENTER();
-    if (n < 1 || n > PW_GROUP_MAX || !A || !M || !K || !W || !N || !scale || !shift || !C || act < 0 || act > 2) return EFFDET_EINVAL;
-    PwGroupArgs g;
-    g.n = n;
-    for (int i = 0; i < n; ++i) {
-        if (!A[i] || !W[i] || !C[i] || !shift[i] || M[i] <= 0 || M[i] > 0x7fffffffLL || K[i] <= 0 || K[i] % 8 || N[i] <= 0) return EFFDET_EINVAL;
-        g.p[i] = PwArgs{A[i], M[i], K[i], W[i], N[i], scale[i], shift[i], act, nullptr, nullptr, (int)M[i], C[i], M[i] * N[i], N[i], 0, 0, 0};
+    return pw_group(reinterpret_cast<hipStream_t>(stream), dtype, n, A, M, K, W, N, scale, shift, act, C, nullptr, 0);
+}
+
+// Host-only queries: the launchers above describe their choice instead of launching.  The pointers they test for presence and
+// alignment are stand-ins: 64 (aligned) or 4.
+extern "C" int effdet_pw_gemm_group_plan_describe(int dtype, int n_problems, const long long* M, const int* K, const int* N, int aligned,
+                                                  int which, int* out, int n) {
+    if (!out || n <= 0 || !M || !K || !N || n_problems < 1 || n_problems > PW_GROUP_MAX) return EFFDET_EINVAL;
+    (void)take_pad_flag(dtype);                          // (a 1x1 conv pads nothing)
+    static const float present = 1.0f;
+    void* const at = reinterpret_cast<void*>(aligned ? (uintptr_t)64 : (uintptr_t)4);
+    const void* ptr[PW_GROUP_MAX]; void* cptr[PW_GROUP_MAX]; const float* fptr[PW_GROUP_MAX];
+    for (int i = 0; i < PW_GROUP_MAX; ++i) { ptr[i] = at; cptr[i] = at; fptr[i] = &present; }
+    PwPlan plan{};
+    const int rc = pw_group(nullptr, dtype, n_problems, ptr, M, K, ptr, N, fptr, fptr, 0, cptr, &plan, which);
+    return rc != EFFDET_OK ? rc : pw_plan_out(plan, out, n);
+}
+
+extern "C" int effdet_pw_gemm_plan_describe(int dtype, long long M, int K, int N, int rows_per_image, int gated, int has_residual,
+                                            long long ldc, long long c_image_stride, int aligned, int group, int* out, int n) {
+    if (!out || n <= 0) return EFFDET_EINVAL;
+    if (group) {                                         // a group of this one problem: no gate, no residual, a dense output
+        if (gated || has_residual || (ldc > 0 && ldc != N) || (c_image_stride > 0 && c_image_stride != M * N)) return EFFDET_EINVAL;
+        if (rows_per_image > 0 && rows_per_image != M) return EFFDET_EINVAL;
+        return effdet_pw_gemm_group_plan_describe(dtype, 1, &M, &K, &N, aligned, 0, out, n);
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == 0) return launch_pw_group<float>(st, g);
-    if (dtype == 1) return launch_pw_group<bf16_t>(st, g);
-    if (dtype == 2) {
-        for (int i = 0; i < n; ++i)
-            if (N[i] % 8 || reinterpret_cast<uintptr_t>(A[i]) % 32 || reinterpret_cast<uintptr_t>(W[i]) % 32 || reinterpret_cast<uintptr_t>(C[i]) % 32)
-                return EFFDET_EINVAL;
-        return launch_pw_group<bf16p_t>(st, g);
-    }
-    return EFFDET_EINVAL;
+    (void)take_pad_flag(dtype);
+    static const float present = 1.0f;
+    void* const at = reinterpret_cast<void*>(aligned ? (uintptr_t)64 : (uintptr_t)4);
+    PwArgs a{at, M, K, at, N, &present, &present, 0, has_residual ? at : nullptr, gated ? &present : nullptr, rows_per_image, at,
+             c_image_stride, ldc, 0, 0, 0};
+    PwPlan plan{};
+    const int rc = pw_single(nullptr, dtype, a, &plan);
+    return rc != EFFDET_OK ? rc : pw_plan_out(plan, out, n);
 }
