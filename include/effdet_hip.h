@@ -793,6 +793,46 @@ int effdet_eval_open_sorted(void* stream, const float* scores, const int* classe
 int effdet_relabel_unknown(void* stream, const float* det_in, const int* count, const float* score, long long pitch,
                            long long stride, int B, int max_det, int num_known, float tau, const float* tau_device, float* det_out);
 
+/* ---- COCO-protocol detection evaluation (csrc/coco_eval.hip): COCOeval 'bbox' with crowd regions, area ranges, AP / AR --------- */
+
+/* COCOeval.evaluateImg for every image, at `num_thresholds` (1..15) ascending IoU thresholds and `num_areas` (1..4) area ranges
+ * [lo, hi] (area_ranges [num_areas][2], inclusive), both HOST arrays.  det / det_count / gt_boxes / gt_cls as effdet_eval_match;
+ * gt_crowd [B,M] bytes (NULL: none), gt_area [B,M] float32 (NULL: the float32 box area).  A slot is dropped when it lies beyond
+ * the count, its box is degenerate, its class is outside 1..num_classes, its score is NaN or < min_score, or its 0-based rank
+ * among the kept slots of its class in the image is >= max_rank (the largest max_dets).  Per (t, a) a detection takes, among the
+ * boxes of its class, the one not ignored at a (crowd, or area outside the range) and not taken at (t, a) with the largest IoU
+ * >= thresholds[t], the last on equal IoU; if there is none, the ignored box by the same rule (a crowd box, IoU = intersection /
+ * detection area, can be matched any number of times).  flags [B,max_det,num_areas]: bit t = true positive, bit 16 + t = ignored
+ * (matched to an ignored box, or unmatched with its own box area outside the range), bit 31 = dropped; rank [B,max_det] (-1:
+ * dropped); kept (NULL, or [2 B] for effdet_coco_append): kept slots of image b, then its NaN scores; npig [C][num_areas] += the
+ * boxes of class c not ignored at a.  40 M + 4 num_classes bytes of LDS <= 64 KiB; B * max_det <= 2^24. */
+int effdet_coco_match(void* stream, const float* det, const int* det_count, const float* gt_boxes, const long long* gt_cls,
+                      const unsigned char* gt_crowd, const float* gt_area, int B, int max_det, int M, int num_classes,
+                      const float* thresholds, int num_thresholds, const float* area_ranges, int num_areas, int max_rank,
+                      float min_score, unsigned int* flags, int* rank, int* kept, int* npig);
+/* effdet_eval_append for the kept slots of effdet_coco_match: (score, 0-based class, num_areas flag words, rank) to scores, classes,
+ * words [capacity][num_areas] and ranks at the device cursor; `state` as there. */
+int effdet_coco_append(void* stream, const float* det, const unsigned int* flags, const int* rank, const int* kept, int B, int max_det,
+                       int num_areas, float* scores, int* classes, unsigned int* words, int* ranks, long long capacity,
+                       unsigned int* state);
+/* pure host queries: workspace size; byte offset in the workspace, after effdet_coco_sorted, of the sorted 64-bit keys (which = 0,
+ * as effdet_eval_ap_sorted_offset), the entries' indices (1), their flag words [n][num_areas] (2) and ranks (3); size of the result */
+long long effdet_coco_sorted_workspace_bytes(long long capacity, int num_classes, int num_areas);
+long long effdet_coco_sorted_offset(long long capacity, int num_classes, int num_areas, int which);
+long long effdet_coco_sorted_result_bytes(int num_thresholds, int num_classes, int num_areas, int num_max_dets);
+/* COCOeval.accumulate over the first n entries (n < 0: min(state[0], capacity), read on the device): the stable radix sort by
+ * (class, score descending), then per (t, c, a, m) over the entries with rank < max_dets[m] not ignored at (t, a): rc = tp / npig,
+ * pr = tp / ((fp + tp) + 2^-52) in float64, made non-increasing from the right; q[r] = pr at the first entry with rc >= rec_thr[r]
+ * (0: none); AP = (q[0] + q[1] + ...) / num_rec, AR = the last rc (0 without entries), both NaN where npig = 0.  max_dets: 1..4
+ * ascending ints (HOST); rec_thr: 1..256 ASCENDING float64 on the DEVICE (not checked: another order gives unspecified q, never
+ * an access out of bounds).  result: 8-byte words {n, lost, NaN scores, T, C, A, Mx, R}, AP [T][C][A][Mx] float64, AR the same,
+ * then int64 npig [C][A].  precision (NULL, or [T][R][C][A][Mx] float64 on the device): q itself, NaN where npig = 0.
+ * Capturable; bit-identical from run to run. */
+int effdet_coco_sorted(void* stream, const float* scores, const int* classes, const unsigned int* words, const int* ranks,
+                       long long capacity, long long n, const unsigned int* state, int num_thresholds, int num_classes, int num_areas,
+                       const int* max_dets, int num_max_dets, const double* rec_thr, int num_rec, const int* npig, void* workspace,
+                       long long workspace_bytes, void* result, double* precision);
+
 /* ---- OOD evaluation helpers -------------------------------------------- */
 
 /* The fork's novelty score (infer.py:425-427, 465-471, 607-616), reported beside energy / max-logit:

@@ -191,6 +191,15 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_ll, c_void_p]),
     'effdet_relabel_unknown': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_int, c_int, c_int, c_float, c_void_p,
                                        c_void_p]),
+    'effdet_coco_match': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_coco_append': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_ll, c_void_p]),
+    'effdet_coco_sorted_workspace_bytes': (c_ll, [c_ll, c_int, c_int]),
+    'effdet_coco_sorted_offset': (c_ll, [c_ll, c_int, c_int, c_int]),
+    'effdet_coco_sorted_result_bytes': (c_ll, [c_int, c_int, c_int, c_int]),
+    'effdet_coco_sorted': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_int,
+                                   c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p]),
     'effdet_train_fold_bn': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_train_convbn_grads': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -24,6 +24,12 @@ DEV float em_iou(const EmDet& d, float g0, float g1, float g2, float g3) {
     const float area_g = (g2 - g0) * (g3 - g1);
     return inter / (d.area + area_g - inter);
 }
+// against a COCO crowd region (coco_eval.hip): the same intersection over the detection's own area
+DEV float em_iou_crowd(const EmDet& d, float g0, float g1, float g2, float g3) {
+    const float ih = fmaxf(0.f, fminf(d.y2, g2) - fmaxf(d.y1, g0));
+    const float iw = fmaxf(0.f, fminf(d.x2, g3) - fmaxf(d.x1, g1));
+    return (ih * iw) / d.area;
+}
 
 // All threads call it, once, before the first search.  LDS: seen[C] = 0 (class already had its top-scoring detection), taken[M] = 0,
 // gcls[M] = the 0-based class of box j of image b or -1, and, when gdif is given, gdif[M] = the box is `difficult` (gt_difficult

@@ -1,3 +1,4 @@
 from .detection_evaluator import ObjectDetectionEvaluator, PascalDetectionEvaluator  # noqa: F401
 from .dataset_evaluator import DatasetDetectionEvaluator  # noqa: F401
 from .open_set_evaluator import OpenSetDetectionEvaluator  # noqa: F401
+from .coco_evaluator import CocoDetectionEvaluator  # noqa: F401

@@ -1,0 +1,228 @@
+#!/usr/bin/env python
+"""The COCO-protocol evaluation of csrc/coco_eval.hip without a GPU: the unit compiled by g++ against the CPU model of common.h and
+driven through its C ABI on numpy arrays - matching (crowd regions, area ranges, ties, ranks), the append, the sort with the entry
+index as payload, the gather, AP / AR and the precision table - against the restatement of tests/_coco_eval_ref.py at small shapes
+(M on both sides of the 256-thread staging loop, images without ground truth or detections, NaN scores, classes out of range, a class
+of more than 2048 entries (a second chunk in the AP kernel), entries on both sides of a sort tile, npig that meets the recall
+thresholds exactly).  Flag words, ranks, npig, the sorted order, precision, AP and AR are compared EXACTLY.  It checks arithmetic,
+indexing and bounds (a guard region follows every buffer), not timing or the memory model.
+
+    python3 tools/simt_model/run_coco_eval.py [--quick]    needs g++ with C++20 (std::barrier); minutes, a thread per lane
+
+What the model adds to common.h for this unit: a fixed-size array in place of the matching kernel's dynamic LDS."""
+import ctypes
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+import _coco_eval_ref as K  # noqa: E402
+from ood_object_detection_amd import _lib  # noqa: E402
+
+PRELUDE = '''#include "common.h"
+#include <cstdint>
+#undef EFFDET_EINVAL
+#define EFFDET_EINVAL (-22)
+using std::min; using std::floor; using std::fabs;
+'''
+DYNAMIC_LDS = 'extern __shared__ double cc_lds[];'
+GUARD = 64
+NAMES = ('effdet_coco_match', 'effdet_coco_append', 'effdet_coco_sorted_workspace_bytes', 'effdet_coco_sorted_offset',
+         'effdet_coco_sorted_result_bytes', 'effdet_coco_sorted')
+
+
+def build(tmp):
+    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
+    for header in ('compact.h', 'radix_sort.h', 'eval_match.h'):                                  # included by the unit
+        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
+    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'coco_eval.hip')).read()
+    assert src.count(DYNAMIC_LDS) == 1
+    src = src.replace(DYNAMIC_LDS, 'static double cc_lds[8192];')
+    with open(os.path.join(tmp, 'coco_eval.cpp'), 'w') as f:
+        f.write(PRELUDE + src)
+    out = os.path.join(tmp, 'libcoco_eval_model.so')
+    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-o', out,
+                    os.path.join(tmp, 'coco_eval.cpp')], check=True)
+    lib = ctypes.CDLL(out)
+    for name in NAMES:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+    return lib
+
+
+def ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def guarded(n, dtype, fill):
+    return np.full(n + GUARD, fill, dtype)
+
+
+class Model:
+    """The calls of CocoDetectionEvaluator on host memory"""
+
+    def __init__(self, lib, C, thresholds, areas, max_dets, rec_thr, capacity, min_score=0.0):
+        self.lib, self.C, self.cap, self.min_score = lib, C, capacity, min_score
+        self.T, self.A, self.Mx, self.R = len(thresholds), len(areas), len(max_dets), len(rec_thr)
+        self.thr = (ctypes.c_float * self.T)(*thresholds)
+        self.areas = (ctypes.c_float * (2 * self.A))(*[v for r in areas for v in r])
+        self.max_dets = (ctypes.c_int * self.Mx)(*max_dets)
+        self.rec = np.asarray(rec_thr, np.float64).copy()
+        self.scores, self.classes = guarded(capacity, np.float32, -7.5), guarded(capacity, np.int32, -77)
+        self.words, self.ranks = guarded(capacity * self.A, np.uint32, 0xA5A5A5A5), guarded(capacity, np.int32, -77)
+        self.ws_bytes = lib.effdet_coco_sorted_workspace_bytes(capacity, C, self.A)
+        self.res_words = lib.effdet_coco_sorted_result_bytes(self.T, C, self.A, self.Mx) // 8
+        assert self.ws_bytes > 0 and self.res_words > 0
+        self.ws = np.full(self.ws_bytes // 8 + GUARD, 0x5A5A5A5A5A5A5A5A, np.uint64)
+        self.result = guarded(self.res_words, np.int64, -99)
+        self.precision = guarded(self.T * self.R * C * self.A * self.Mx, np.float64, -9.25)
+        self.state = np.zeros(4, np.uint32)
+        self.npig = guarded(C * self.A, np.int32, 0)
+
+    def add_batch(self, det, cnt, gtb, gtc, crowd, area):
+        B, max_det, _ = det.shape
+        M, A = gtb.shape[1], self.A
+        flags, rank = guarded(B * max_det * A, np.uint32, 0xA5A5A5A5), guarded(B * max_det, np.int32, -5)
+        kept = guarded(2 * B, np.int32, -5)
+        rc = self.lib.effdet_coco_match(None, ptr(det), ptr(cnt), ptr(gtb), ptr(gtc), ptr(crowd), ptr(area), B, max_det, M, self.C,
+                                        self.thr, self.T, self.areas, A, self.max_dets[self.Mx - 1], self.min_score, ptr(flags),
+                                        ptr(rank), ptr(kept), ptr(self.npig))
+        assert rc == 0, rc
+        rc = self.lib.effdet_coco_append(None, ptr(det), ptr(flags), ptr(rank), ptr(kept), B, max_det, A, ptr(self.scores),
+                                         ptr(self.classes), ptr(self.words), ptr(self.ranks), self.cap, ptr(self.state))
+        assert rc == 0, rc
+        assert (flags[B * max_det * A:] == 0xA5A5A5A5).all() and (rank[B * max_det:] == -5).all(), 'a write beyond a per-batch buffer'
+        assert (kept[2 * B:] == -5).all() and (self.npig[self.C * A:] == 0).all()
+        return flags[:B * max_det * A].reshape(B, max_det, A), rank[:B * max_det].reshape(B, max_det)
+
+    def evaluate(self, n=-1):
+        rc = self.lib.effdet_coco_sorted(None, ptr(self.scores), ptr(self.classes), ptr(self.words), ptr(self.ranks), self.cap, n,
+                                         ptr(self.state), self.T, self.C, self.A, self.max_dets, self.Mx, ptr(self.rec), self.R,
+                                         ptr(self.npig), ptr(self.ws), self.ws_bytes, ptr(self.result), ptr(self.precision))
+        assert rc == 0, rc
+        assert (self.scores[self.cap:] == -7.5).all() and (self.classes[self.cap:] == -77).all(), 'a write beyond the entries'
+        assert (self.words[self.cap * self.A:] == 0xA5A5A5A5).all() and (self.ranks[self.cap:] == -77).all()
+        assert (self.ws[self.ws_bytes // 8:] == 0x5A5A5A5A5A5A5A5A).all(), 'a write beyond the workspace'
+        assert (self.result[self.res_words:] == -99).all(), 'a write beyond the result block'
+        assert (self.precision[self.T * self.R * self.C * self.A * self.Mx:] == -9.25).all(), 'a write beyond the precision table'
+        from ood_object_detection_amd.effdet.evaluation.coco_evaluator import parse_coco_result
+        r = parse_coco_result(self.result[:self.res_words])
+        r['precision'] = self.precision[:self.T * self.R * self.C * self.A * self.Mx].reshape(self.T, self.R, self.C, self.A, self.Mx)
+        return r
+
+    def sorted(self, n):
+        ws = self.ws.view(np.uint8)
+        off = [self.lib.effdet_coco_sorted_offset(self.cap, self.C, self.A, w) for w in range(4)]
+        keys = ws[off[0]:off[0] + 8 * n].view(np.uint64)
+        index = ws[off[1]:off[1] + 4 * n].view(np.uint32)
+        words = ws[off[2]:off[2] + 4 * n * self.A].view(np.uint32).reshape(n, self.A)
+        ranks = ws[off[3]:off[3] + 4 * n].view(np.int32)
+        return keys, index, words, ranks
+
+
+def same(a, b):
+    """bitwise equality of float64 arrays, NaN = NaN"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and \
+        np.array_equal(np.where(np.isnan(a), 0.0, a).view(np.uint64), np.where(np.isnan(b), 0.0, b).view(np.uint64))
+
+
+def compare(name, got, ref, m, n):
+    assert got['n'] == n and got['lost'] == 0, (name, got['n'], n)
+    assert np.array_equal(got['npig'], ref['npig']), (name, 'npig')
+    for k in ('precision', 'ap', 'ar'):
+        assert same(got[k], ref[k]), (name, k, np.nanmax(np.abs(np.nan_to_num(got[k]) - np.nan_to_num(ref[k]))))
+    keys, index, words, ranks = m.sorted(n)
+    order = K.sorted_entries(m.scores[:n], m.classes[:n], m.C)
+    assert np.array_equal(index[:len(order)], order), (name, 'sorted order')
+    assert np.array_equal(words[:len(order)], m.words[:n * m.A].reshape(n, m.A)[order]) and np.array_equal(ranks[:len(order)], m.ranks[:n][order])
+
+
+def check_case(lib, name, images, C, M, max_det, thresholds=K.COCO_THRESHOLDS, areas=K.COCO_AREAS, max_dets=K.COCO_MAX_DETS,
+               rec_thr=K.COCO_REC_THRS, splits=1, min_score=0.0):
+    ref = K.evaluate(images, C, thresholds, areas, max_dets, rec_thr, min_score)
+    m = Model(lib, C, thresholds, areas, max_dets, rec_thr, len(images) * max_det + 5, min_score)
+    flags, ranks = [], []
+    for idx in np.array_split(np.arange(len(images)), splits):
+        f, r = m.add_batch(*K.pack([images[i] for i in idx], max_det, M))
+        flags.append(f)
+        ranks.append(r)
+    flags, ranks = np.concatenate(flags), np.concatenate(ranks)
+    for i, im in enumerate(images):
+        n = len(im['det_scores'])
+        assert np.array_equal(flags[i, :n], ref['flags'][i]), (name, 'flags', i, flags[i, :n], ref['flags'][i])
+        assert np.array_equal(ranks[i, :n], ref['ranks'][i]), (name, 'ranks', i)
+        assert (flags[i, n:] == 0x80000000).all() and (ranks[i, n:] == -1).all()
+    n = len(ref['scores'])
+    assert np.array_equal(m.scores[:n], ref['scores'] + np.float32(0)) and np.array_equal(m.classes[:n], ref['classes'])
+    got = m.evaluate()
+    compare(name, got, ref, m, n)
+    tp = int(sum(((f & 1) != 0).sum() for f in ref['flags']))
+    print('%-52s %5d entries, %4d TP at (t 0), mAP %.6f ok' % (name, n, tp, np.nanmean(ref['ap'][:, :, 0, -1])))
+
+
+def check_entries(lib, name, n, C, npig_values, seed, big=0, T=2, A=2, max_dets=(1, 10, 100), rec_thr=K.COCO_REC_THRS):
+    """entries put into the buffers directly: scores with ties, random words and ranks; the first `big` entries are of class 0"""
+    rs = np.random.RandomState(seed)
+    m = Model(lib, C, [0.5, 0.75][:T], K.COCO_AREAS[:A], max_dets, rec_thr, n + 3)
+    scores = (rs.randint(0, 64, n) / np.float32(64)).astype(np.float32)
+    classes = rs.randint(0, C, n)
+    classes[:big] = 0
+    u = rs.uniform(size=(n, A))
+    tpw = (u < 0.35) * 1 + (rs.uniform(size=(n, A)) < 0.3) * 2
+    igw = ((u > 0.9) * 1 + (rs.uniform(size=(n, A)) > 0.9) * 2) << 16
+    words = (tpw | igw).astype(np.uint32) & np.uint32((1 << T) - 1 | (((1 << T) - 1) << 16))
+    ranks = rs.randint(0, 120, n).astype(np.int32)
+    ranks[:big] = rs.randint(0, 10, big)
+    npig = np.array([[npig_values[(c * A + a) % len(npig_values)] for a in range(A)] for c in range(C)], np.int64)
+    m.scores[:n], m.classes[:n], m.words[:n * A], m.ranks[:n] = scores, classes, words.reshape(-1), ranks
+    m.state[0] = n
+    m.npig[:C * A] = npig.reshape(-1)
+    got = m.evaluate()
+    ref = K.accumulate(scores, classes, words, ranks, npig, C, T, max_dets, rec_thr)
+    ref['npig'] = npig
+    compare(name, got, ref, m, n)
+    print('%-52s %5d entries ok' % (name, n))
+
+
+def worked_example(lib):
+    im = dict(gt_boxes=np.array([[0, 0, 10, 10], [20, 20, 30, 30]], np.float32), gt_classes=np.array([0, 0]),
+              det_boxes=np.array([[0, 0, 10, 10], [40, 40, 50, 50], [20, 20, 30, 30]], np.float32),
+              det_scores=np.array([0.9, 0.8, 0.7], np.float32), det_classes=np.array([0, 0, 0]))
+    m = Model(lib, 1, [0.5], [K.COCO_AREAS[0]], [100], K.COCO_REC_THRS, 8)
+    m.add_batch(*K.pack([im], 3, 2))
+    got = m.evaluate()
+    s = 0.0
+    for v in [1.0] * 51 + [2.0 / (3.0 + np.spacing(1))] * 50:
+        s = s + v
+    assert got['ap'][0, 0, 0, 0] == s / 101 and got['ar'][0, 0, 0, 0] == 1.0, got
+    print('worked example: AP %.6f = (51 + 50 * 2/3) / 101, AR 1 ok' % got['ap'][0, 0, 0, 0])
+
+
+def main():
+    quick = '--quick' in sys.argv[1:]
+    with tempfile.TemporaryDirectory() as tmp:
+        lib = build(tmp)
+        worked_example(lib)
+        check_case(lib, 'M 1, T 1, A 1', K.random_images(1, 3, 3, 1, 12), 3, 1, 12, thresholds=[0.5], areas=[K.COCO_AREAS[0]], max_dets=[100])
+        check_case(lib, 'M 40, COCO parameters, 2 batches', K.random_images(2, 4, 4, 40, 30, scores_levels=16), 4, 40, 31, splits=2)
+        check_case(lib, 'M 40, min_score 0.25, max_dets 1 3 5', K.random_images(3, 3, 3, 40, 30), 3, 40, 30, max_dets=(1, 3, 5), min_score=0.25)
+        if not quick:
+            check_case(lib, 'M 257, T 15', K.random_images(4, 3, 5, 257, 40), 5, 257, 40, thresholds=np.linspace(0.25, 0.95, 15))
+            check_case(lib, 'M 300, 300 detections', K.random_images(5, 2, 5, 300, 300, scores_levels=64), 5, 300, 300, splits=2)
+            tile = 4096
+            check_entries(lib, 'tile + 1 entries, 3 classes', tile + 1, 3, [4, 10, 20, 50, 100, 0], 11)
+        check_entries(lib, '600 entries, 3 classes', 600, 3, [4, 10, 20, 50, 100, 0], 12)
+        check_entries(lib, '2500 entries, class 0 beyond an AP chunk', 2500, 2, [50, 100, 1000, 7], 13, big=2049)
+
+
+if __name__ == '__main__':
+    main()
