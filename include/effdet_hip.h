@@ -833,6 +833,26 @@ int effdet_coco_sorted(void* stream, const float* scores, const int* classes, co
                        const int* max_dets, int num_max_dets, const double* rec_thr, int num_rec, const int* npig, void* workspace,
                        long long workspace_bytes, void* result, double* precision);
 
+/* ---- LVIS federated detection evaluation (csrc/lvis_eval.hip): per-image category sets, one cap over all categories ------------- */
+
+/* pure host query: the LDS bytes of one effdet_lvis_match workgroup, 40 M + 12 ceil(num_classes / 32) + 8 max_det + 16;
+ * -22 for max_det outside 1..2048, M < 1 or num_classes outside 1..65535.  The launch needs it <= 64 KiB. */
+long long effdet_lvis_match_lds_bytes(int max_det, int M, int num_classes);
+/* LVISEval.evaluate_img for every image: effdet_coco_match without crowd regions, with the det rows IN ANY ORDER and per image
+ * neg_cls [B,Kn] / nel_cls [B,Ke] int64 1-based category lists (<= 0 or > num_classes: padding): the categories checked absent and
+ * the categories not exhaustively annotated.  neg_cls NULL: every category is judged in every image; nel_cls NULL: no category is
+ * not-exhaustive; a non-NULL list may have length 0 (the empty set).  A slot is valid when it lies below the count, its box is not
+ * degenerate, its class is in 1..num_classes and its score is neither NaN nor < min_score.  Its image rank r is the number of valid
+ * slots of the image with a larger score, or an equal score and a lower index; it is dropped when r >= max_rank (LVIS's cap over
+ * ALL categories), and then when its class is neither the class of a box of the image nor in neg_cls.  The kept slots are matched
+ * in ascending r by effdet_coco_match's rule; an unmatched detection is ignored at (t, a) when its own box area is outside the
+ * range or its class is in nel_cls, else a false positive.  flags / rank (the image rank; -1: dropped) / kept / npig as
+ * effdet_coco_match, so effdet_coco_append and effdet_coco_sorted take them as they are.  max_det <= 2048; B * max_det <= 2^24. */
+int effdet_lvis_match(void* stream, const float* det, const int* det_count, const float* gt_boxes, const long long* gt_cls,
+                      const float* gt_area, int B, int max_det, int M, int num_classes, const float* thresholds, int num_thresholds,
+                      const float* area_ranges, int num_areas, int max_rank, float min_score, const long long* neg_cls, int Kn,
+                      const long long* nel_cls, int Ke, unsigned int* flags, int* rank, int* kept, int* npig);
+
 /* ---- OOD evaluation helpers -------------------------------------------- */
 
 /* The fork's novelty score (infer.py:425-427, 465-471, 607-616), reported beside energy / max-logit:

@@ -200,6 +200,10 @@ SIGNATURES = {
     'effdet_coco_sorted_result_bytes': (c_ll, [c_int, c_int, c_int, c_int]),
     'effdet_coco_sorted': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_int,
                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p]),
+    'effdet_lvis_match_lds_bytes': (c_ll, [c_int, c_int, c_int]),
+    'effdet_lvis_match': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
     'effdet_train_fold_bn': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_train_convbn_grads': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -59,7 +59,7 @@ constexpr int CC_AP_CHUNK = CC_THREADS * CC_AP_ITEMS;             // segment ent
 constexpr long long CC_MAX_N = 1ll << 24;
 constexpr int CC_MAX_T = 15, CC_MAX_A = 4, CC_MAX_MX = 4, CC_MAX_R = 256, CC_MAX_C = 65535;
 constexpr unsigned CC_DROPPED = 0x80000000u;
-constexpr int CC_CROWD = 1 << 4, CC_OF_CLASS = 1 << 5;            // box bits beside the ignore bits 0 .. A-1
+constexpr int CC_CROWD = EM_ROW_CROWD, CC_OF_CLASS = EM_ROW_OF_CLASS;      // box bits beside the ignore bits 0 .. A-1
 constexpr int CC_RESULT_HEAD = 8;                                 // 8-byte words before the AP array
 constexpr int CC_NO_K = 0x7fffffff;                               // k_r of a recall threshold that no count reaches
 
@@ -178,16 +178,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
         __syncthreads();
         if (tid < 64) {
             int b1 = -1, b2 = -1;                    // the best box not ignored / ignored at my_a
-            float v1 = my_thr, v2 = my_thr;
-            if (active)
-                for (int j = 0; j < p.M; ++j) {      // every lane reads the same LDS words: broadcasts
-                    const int m = rmeta[j];
-                    if (!(m & CC_OF_CLASS)) continue;
-                    if (!(m & CC_CROWD) && ((taken[j] >> pair) & 1ull)) continue;
-                    const float v = iou[j];
-                    if ((m >> my_a) & 1) { if (v >= v2) { v2 = v; b2 = j; } }
-                    else { if (v >= v1) { v1 = v; b1 = j; } }      // >=: the last index on equal IoU
-                }
+            if (active) em_walk_row(rmeta, taken, iou, p.M, pair, my_a, my_thr, &b1, &b2);
             const int bj = b1 >= 0 ? b1 : b2;
             const bool tp = active && b1 >= 0;
             const bool ign = active && b1 < 0 && (b2 >= 0 || dd.area < my_lo || dd.area > my_hi);

@@ -1,7 +1,8 @@
 // What the two greedy matchers (evaluation.hip: one threshold, a `tp` label per slot; eval_scale.hip: up to 16 thresholds, a flag
 // word per slot) and the open words of eval_scale.hip state once: the float32 IoU, the staging of an image's
 // ground truth with its per-class counters, and the search for a detection's candidate box.  One workgroup of EM_THREADS threads
-// per image.  What thread 0 does with the candidate differs between the two kernels and stays there.
+// per image.  What thread 0 does with the candidate differs between the two kernels and stays there.  coco_eval.hip and
+// lvis_eval.hip share the IoU and the walk of a detection's IoU row by the lane that owns an (IoU threshold, area range) pair.
 //
 // Both units are compiled with -ffp-contract=off: the IoU must round like the reference's separate float32 numpy operations
 // (effdet/evaluation/np_box_ops.py), so its operations stay in this order, one rounding each.
@@ -29,6 +30,26 @@ DEV float em_iou_crowd(const EmDet& d, float g0, float g1, float g2, float g3) {
     const float ih = fmaxf(0.f, fminf(d.y2, g2) - fmaxf(d.y1, g0));
     const float iw = fmaxf(0.f, fminf(d.x2, g3) - fmaxf(d.x1, g1));
     return (ih * iw) / d.area;
+}
+
+// The lane that owns pair (t, a) of coco_eval.hip / lvis_eval.hip walks the detection's IoU row in LDS.  rmeta[j]: 0 for a box of
+// another class, else EM_ROW_OF_CLASS | EM_ROW_CROWD (a crowd region) | bit a (ignored at area range a); taken[j] bit `pair`: taken
+// at this pair (a crowd region stays free).  -> *free_box: the box not ignored at a with the largest IoU >= thr, the LAST index on
+// equal IoU (>=); *ign_box: the same among the ignored boxes; -1 where there is none.  Every lane reads the same words: broadcasts.
+constexpr int EM_ROW_CROWD = 1 << 4, EM_ROW_OF_CLASS = 1 << 5;
+DEV void em_walk_row(const int* rmeta, const unsigned long long* taken, const float* iou, int M, int pair, int a, float thr,
+                     int* free_box, int* ign_box) {
+    int b1 = -1, b2 = -1;
+    float v1 = thr, v2 = thr;
+    for (int j = 0; j < M; ++j) {
+        const int m = rmeta[j];
+        if (!(m & EM_ROW_OF_CLASS)) continue;
+        if (!(m & EM_ROW_CROWD) && ((taken[j] >> pair) & 1ull)) continue;
+        const float v = iou[j];
+        if ((m >> a) & 1) { if (v >= v2) { v2 = v; b2 = j; } }
+        else { if (v >= v1) { v1 = v; b1 = j; } }
+    }
+    *free_box = b1; *ign_box = b2;
 }
 
 // All threads call it, once, before the first search.  LDS: seen[C] = 0 (class already had its top-scoring detection), taken[M] = 0,

@@ -2,3 +2,4 @@ from .detection_evaluator import ObjectDetectionEvaluator, PascalDetectionEvalua
 from .dataset_evaluator import DatasetDetectionEvaluator  # noqa: F401
 from .open_set_evaluator import OpenSetDetectionEvaluator  # noqa: F401
 from .coco_evaluator import CocoDetectionEvaluator  # noqa: F401
+from .lvis_evaluator import LvisDetectionEvaluator  # noqa: F401

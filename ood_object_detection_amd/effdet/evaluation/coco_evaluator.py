@@ -8,8 +8,8 @@ device.  `enqueue()` sorts (class, score descending, equal scores in arrival ord
 area range, max_dets); `result()` is the one device-to-host copy.  Nothing before `result()` synchronises with the host, so
 `add_batch` and `enqueue` can be captured in a `torch.cuda.graph`; the same images give the same bits however they are split into
 `add_batch` calls.  The means over classes and thresholds (`evaluate()`, `stats`) are host arithmetic over the entries that are not
-NaN (pycocotools: `> -1`).  No CPU fallback.  Not built: masks, keypoints, LVIS rules, `useCats=0`, merging evaluators across ranks
-on the device.
+NaN (pycocotools: `> -1`).  No CPU fallback.  LVIS's federated rules are `LvisDetectionEvaluator` (lvis_evaluator.py).  Not built:
+masks, keypoints, `useCats=0`, merging evaluators across ranks on the device.
 """
 import ctypes
 

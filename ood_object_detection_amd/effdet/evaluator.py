@@ -8,6 +8,8 @@ nothing back before `evaluate()`.  Ground truth comes from `dataset.parser` as p
 `parser.img_ids`, `parser.coco.imgToAnns[img_id]` (dicts with `bbox` xywh, `category_id`, `iscrowd`, `area`), `parser.cat_ids`
 and `parser.cat_id_to_label` when set.  Boxes are NOT filtered the way the training parser filters them: COCOeval sees every
 annotation.  `save()` writes the COCO-style json from predictions kept on the host, only with `keep_predictions=True`.
+`LvisEvaluator` is LVIS `bbox` AP under the federated rules (`LvisDetectionEvaluator`, csrc/lvis_eval.hip), from an LVIS json
+dict through `lvis_ground_truth`; `create_evaluator` mirrors the reference's dispatch and does not name it.
 """
 import abc
 import json
@@ -18,11 +20,12 @@ import torch
 import torch.distributed as dist
 
 from .distributed import all_gather_container
-from .evaluation import CocoDetectionEvaluator, ObjectDetectionEvaluator, PascalDetectionEvaluator
+from .evaluation import CocoDetectionEvaluator, LvisDetectionEvaluator, ObjectDetectionEvaluator, PascalDetectionEvaluator
 
 _logger = logging.getLogger(__name__)
 
-__all__ = ['CocoEvaluator', 'PascalEvaluator', 'OpenImagesEvaluator', 'create_evaluator', 'coco_ground_truth']
+__all__ = ['CocoEvaluator', 'LvisEvaluator', 'PascalEvaluator', 'OpenImagesEvaluator', 'create_evaluator', 'coco_ground_truth',
+           'lvis_ground_truth']
 
 
 def coco_ground_truth(anns, cat_id_to_label=None, cat_ids=None, M=None):
@@ -64,6 +67,62 @@ def coco_ground_truth(anns, cat_id_to_label=None, cat_ids=None, M=None):
         for j, (b, label, cr, ar) in enumerate(r):
             boxes[i, j], cls[i, j], crowd[i, j], area[i, j] = b, label, cr, ar
     return torch.from_numpy(boxes), torch.from_numpy(cls), torch.from_numpy(crowd), torch.from_numpy(area)
+
+
+def lvis_ground_truth(dataset_dict, cat_id_to_label=None, M=None, Kn=None, Ke=None):
+    """dataset_dict: an LVIS annotation json as a dict - `images` (dicts with `id`, `neg_category_ids`,
+    `not_exhaustive_category_ids`), `annotations` (dicts with `image_id`, `bbox` x, y, w, h, `area`, `category_id`), `categories`
+    (dicts with `id`, `name`, `frequency`).  Pure host.  -> dict(gt_boxes [N, M, 4] float32 yxyx, gt_cls [N, M] int64 1-based label
+    (-1: padding), gt_area [N, M] float32 (the annotation's `area`, w * h without one), neg_cls [N, Kn] and nel_cls [N, Ke] int64
+    1-based labels (-1: padding), img_ids: row i = image i of `images`, categories: [{'id': label, 'name', 'frequency'}]).  The
+    label is cat_id_to_label[category_id] when the map is given, else the category id itself; annotations and list entries of a
+    category outside the map or outside `categories` are left out.  M, Kn, Ke: padded lengths, at least the longest list (default:
+    exactly that, and at least 1)."""
+    cats = dataset_dict['categories']
+    known = {c['id'] for c in cats}
+
+    def label(cid):
+        if cid not in known or (cat_id_to_label and cid not in cat_id_to_label):
+            return None
+        lab = int(cat_id_to_label[cid]) if cat_id_to_label else int(cid)
+        if lab < 1:
+            raise ValueError('labels are 1-based, got %d for category %r' % (lab, cid))
+        return lab
+    categories = []
+    for c in cats:
+        if label(c['id']) is not None:
+            entry = {'id': label(c['id']), 'name': str(c.get('name', c['id']))}
+            if 'frequency' in c:
+                entry['frequency'] = c['frequency']
+            categories.append(entry)
+    images = dataset_dict['images']
+    row = {im['id']: i for i, im in enumerate(images)}
+    boxes = [[] for _ in images]
+    for a in dataset_dict['annotations']:
+        lab = label(a['category_id'])
+        if lab is None or a['image_id'] not in row:
+            continue
+        x, y, w, h = (float(v) for v in a['bbox'])
+        boxes[row[a['image_id']]].append(((y, x, y + h, x + w), lab, float(a['area']) if 'area' in a else w * h))
+    lists = [[[l for l in (label(c) for c in im.get(key, ())) if l is not None] for im in images]
+             for key in ('neg_category_ids', 'not_exhaustive_category_ids')]
+
+    def padded(name, asked, rows):
+        longest = max([len(r) for r in rows] + [1])
+        if asked is not None and asked < longest:
+            raise ValueError('%s = %d is shorter than the longest list (%d)' % (name, asked, longest))
+        return longest if asked is None else asked
+    M, Kn, Ke = padded('M', M, boxes), padded('Kn', Kn, lists[0]), padded('Ke', Ke, lists[1])
+    N = len(images)
+    gt_boxes, gt_cls, gt_area = np.zeros((N, M, 4), np.float32), np.full((N, M), -1, np.int64), np.zeros((N, M), np.float32)
+    neg, nel = np.full((N, Kn), -1, np.int64), np.full((N, Ke), -1, np.int64)
+    for i in range(N):
+        for j, (b, lab, ar) in enumerate(boxes[i]):
+            gt_boxes[i, j], gt_cls[i, j], gt_area[i, j] = b, lab, ar
+        neg[i, :len(lists[0][i])] = lists[0][i]
+        nel[i, :len(lists[1][i])] = lists[1][i]
+    return dict(gt_boxes=torch.from_numpy(gt_boxes), gt_cls=torch.from_numpy(gt_cls), gt_area=torch.from_numpy(gt_area),
+                neg_cls=torch.from_numpy(neg), nel_cls=torch.from_numpy(nel), img_ids=[im['id'] for im in images], categories=categories)
 
 
 class Evaluator:
@@ -189,6 +248,44 @@ class CocoEvaluator(Evaluator):
                 if k.startswith('A') and '@' in k:
                     _logger.info('%s = %.3f', k, v)
             metric = float(self.metrics['stats'][0])
+        metric = self._broadcast(metric)
+        self.reset()
+        return metric
+
+
+class LvisEvaluator(Evaluator):
+    """LVIS `bbox` AP from an LVIS annotation dict (`lvis_ground_truth`): `target['img_idx']` indexes `dataset_dict['images']`."""
+
+    def __init__(self, dataset_dict, distributed=False, pred_yxyx=False, keep_predictions=False, device='cuda:0', capacity=1 << 20,
+                 cat_id_to_label=None, min_score=0.0):
+        super().__init__(distributed=distributed, pred_yxyx=pred_yxyx, keep_predictions=keep_predictions, device=device)
+        self._gt = lvis_ground_truth(dataset_dict, cat_id_to_label=cat_id_to_label)
+        if not self._gt['categories']:
+            raise ValueError('the dataset has no categories')
+        self._dataset = type('Ids', (), dict(img_ids=self._gt['img_ids']))()
+        self._make = lambda: LvisDetectionEvaluator(self._gt['categories'], min_score=min_score, capacity=capacity, device=device)
+
+    def _ground_truth_tables(self):
+        return tuple(self._gt[k] for k in ('gt_boxes', 'gt_cls', 'gt_area', 'neg_cls', 'nel_cls'))
+
+    def _add(self, det, count, gt):
+        self._evaluator.add_batch(det, count, *gt)
+
+    def reset(self):
+        if self._built is not None:
+            self._built.clear()
+        self.img_indices = []
+        self.predictions = []
+
+    def evaluate(self):
+        """LVIS AP@[.5:.95] over all categories; `self.metrics` keeps the thirteen figures and the per-class AP.  Resets."""
+        metric = 0.0
+        if not self.distributed or dist.get_rank() == 0:
+            self.metrics = self._evaluator.evaluate()
+            for k, v in self.metrics.items():
+                if k.startswith('A') and '/' not in k:
+                    _logger.info('%s = %.3f', k, v)
+            metric = float(self.metrics['AP'])
         metric = self._broadcast(metric)
         self.reset()
         return metric
