@@ -31,8 +31,9 @@
 //            ignored box at once.  `taken` is one 64-bit word per box (bit t A + a), set by a 64-bit LDS atomic OR because two
 //            lanes may take the same box; a lane reads only its own bit, so the pairs never wait for each other.  Two ballots
 //            turn the lanes' verdicts into the A flag words.
-//   append   as eval_scale.hip: positions from the images' kept counts and a cursor on the device; (score, class, A words, rank).
-//   sort     radix_sort.h over the 48-bit (class, score descending) key with the ENTRY INDEX as payload, so the scatter kernel's
+//   append   ev_append of eval_sorted.h: positions from the images' kept counts and a cursor on the device; the payload of an
+//            entry beside (score, class) is its A words and its rank.
+//   sort     ev_sort over the 48-bit (class, score descending) key with the ENTRY INDEX as payload, so the scatter kernel's
 //            registers hold one payload word whatever A is; one gather launch then lays words and ranks out in sorted order.
 //   AP       one workgroup per (c, t, a, m) - C T A Mx of them (9600 for COCO), each over a segment of n / C entries: more
 //            workgroups than the device has wave slots and no serial loop over pairs inside one.  The chunks of 2048 go from the
@@ -46,64 +47,20 @@
 #include "compact.h"
 #include "radix_sort.h"
 #include "eval_match.h"
+#include "eval_sorted.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int CC_THREADS = 256;
-constexpr int CC_WAVES = CC_THREADS / 64;
-static_assert(CC_THREADS == FO_THREADS && CC_THREADS == EM_THREADS, "the shared headers are written for this workgroup size");
-constexpr int CC_AP_ITEMS = 8;
-constexpr int CC_AP_CHUNK = CC_THREADS * CC_AP_ITEMS;             // segment entries of one AP step (counts fit 16 bits)
-constexpr long long CC_MAX_N = 1ll << 24;
-constexpr int CC_MAX_T = 15, CC_MAX_A = 4, CC_MAX_MX = 4, CC_MAX_R = 256, CC_MAX_C = 65535;
-constexpr unsigned CC_DROPPED = 0x80000000u;
-constexpr int CC_CROWD = EM_ROW_CROWD, CC_OF_CLASS = EM_ROW_OF_CLASS;      // box bits beside the ignore bits 0 .. A-1
+constexpr int CC_THREADS = EV_THREADS;
+constexpr int CC_MAX_MX = 4, CC_MAX_R = 256;
 constexpr int CC_RESULT_HEAD = 8;                                 // 8-byte words before the AP array
 constexpr int CC_NO_K = 0x7fffffff;                               // k_r of a recall threshold that no count reaches
-
-DEV unsigned cc_live(const unsigned* cursor, long long n_host, unsigned capacity) {
-    return n_host >= 0 ? (unsigned)n_host : fo_min(cursor[0], capacity);
-}
-// sum in a fixed order (butterfly inside a wave, then the waves in order); sh: [CC_WAVES] in LDS, free again on return
-DEV unsigned cc_block_sum(unsigned v, unsigned* sh, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    if ((tid & 63) == 0) sh[tid >> 6] = v;
-    __syncthreads();
-    unsigned tot = sh[0];
-#pragma unroll
-    for (int w = 1; w < CC_WAVES; ++w) tot = tot + sh[w];
-    __syncthreads();
-    return tot;
-}
-// maximum over the threads above this one (0 for the last); *total: over all.  Values are >= 0.
-DEV double cc_block_excl_rmax(double v, double* sh, int tid, double* total) {
-    const int lane = tid & 63, wave = tid >> 6;
-    double incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_down(incl, o, 64);
-        if (lane + o < 64) incl = fmax(incl, t);
-    }
-    const double nxt = __shfl_down(incl, 1, 64);
-    double ex = lane < 63 ? nxt : 0.0;
-    if (lane == 0) sh[wave] = incl;
-    __syncthreads();
-    double tot = 0.0;
-#pragma unroll
-    for (int w = 0; w < CC_WAVES; ++w) { const double s = sh[w]; if (w > wave) ex = fmax(ex, s); tot = fmax(tot, s); }
-    __syncthreads();
-    *total = tot;
-    return ex;
-}
 
 // ---- matching --------------------------------------------------------------------------------------------------------------------
 struct CcMatch {
     const float* det; const int* det_count; const float* gt_boxes; const long long* gt_cls; const unsigned char* gt_crowd;
     const float* gt_area;
-    int B, max_det, M, C, T, A, max_rank; float min_score; float thr[CC_MAX_T]; float lo[CC_MAX_A], hi[CC_MAX_A];
+    int B, max_det, M, C, T, A, max_rank; float min_score; float thr[EM_MAX_T]; float lo[EM_MAX_A], hi[EM_MAX_A];
     unsigned* flags; int* rank; int* kept; int* npig;
 };
 
@@ -115,8 +72,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
     float* box = reinterpret_cast<float*>(taken + p.M);           // [M][4] yxyx
     float* iou = box + 4 * p.M;                                   // [M] the detection's row
     int* gcls = reinterpret_cast<int*>(iou + p.M);                // [M] 0-based class or -1
-    int* gmeta = gcls + p.M;                                      // [M] bit a: ignored at a, CC_CROWD
-    int* rmeta = gmeta + p.M;                                     // [M] gmeta | CC_OF_CLASS for the boxes of the detection's class, else 0
+    int* gmeta = gcls + p.M;                                      // [M] bit a: ignored at a, EM_ROW_CROWD
+    int* rmeta = gmeta + p.M;                                     // [M] gmeta | EM_ROW_OF_CLASS for the boxes of the detection's class, else 0
     int* seen = rmeta + p.M;                                      // [C] kept detections of the class so far
     const int b = blockIdx.x, tid = threadIdx.x;
     for (int c = tid; c < p.C; c += CC_THREADS) seen[c] = 0;
@@ -129,9 +86,9 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
         box[4 * j] = g0; box[4 * j + 1] = g1; box[4 * j + 2] = g2; box[4 * j + 3] = g3;
         const bool crowd = p.gt_crowd && p.gt_crowd[at];
         const float area = p.gt_area ? p.gt_area[at] : (g2 - g0) * (g3 - g1);
-        int meta = crowd ? CC_CROWD : 0;
+        int meta = crowd ? EM_ROW_CROWD : 0;
 #pragma unroll
-        for (int a = 0; a < CC_MAX_A; ++a) {
+        for (int a = 0; a < EM_MAX_A; ++a) {
             if (a >= p.A) continue;
             const bool ig = crowd || area < p.lo[a] || area > p.hi[a];
             meta |= (ig ? 1 : 0) << a;
@@ -145,9 +102,9 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
     const int my_t = pair / p.A, my_a = pair % p.A;
     float my_thr = 0.f, my_lo = 0.f, my_hi = 0.f;
 #pragma unroll
-    for (int t = 0; t < CC_MAX_T; ++t) if (t == my_t) my_thr = p.thr[t];
+    for (int t = 0; t < EM_MAX_T; ++t) if (t == my_t) my_thr = p.thr[t];
 #pragma unroll
-    for (int a = 0; a < CC_MAX_A; ++a) if (a == my_a) { my_lo = p.lo[a]; my_hi = p.hi[a]; }
+    for (int a = 0; a < EM_MAX_A; ++a) if (a == my_a) { my_lo = p.lo[a]; my_hi = p.hi[a]; }
     __syncthreads();
     const int n = min(p.det_count[b], p.max_det);
     int kept = 0, nans = 0;                          // thread 0's
@@ -161,7 +118,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
         const int rk = ok ? seen[c] : 0;             // written by thread 0 before the barrier that ended the last kept round
         ok = ok && rk < p.max_rank;
         if (!ok) {                                   // the same for the whole workgroup
-            if (tid < p.A) p.flags[slot * p.A + tid] = CC_DROPPED;
+            if (tid < p.A) p.flags[slot * p.A + tid] = EM_DROPPED;
             if (tid == 0) p.rank[slot] = -1;
             continue;
         }
@@ -169,9 +126,9 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
         for (int j = tid; j < p.M; j += CC_THREADS) {
             int m = 0;
             if (gcls[j] == c) {
-                m = gmeta[j] | CC_OF_CLASS;
+                m = gmeta[j] | EM_ROW_OF_CLASS;
                 const float* g = box + 4 * j;
-                iou[j] = (m & CC_CROWD) ? em_iou_crowd(dd, g[0], g[1], g[2], g[3]) : em_iou(dd, g[0], g[1], g[2], g[3]);
+                iou[j] = (m & EM_ROW_CROWD) ? em_iou_crowd(dd, g[0], g[1], g[2], g[3]) : em_iou(dd, g[0], g[1], g[2], g[3]);
             }
             rmeta[j] = m;
         }
@@ -182,7 +139,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
             const int bj = b1 >= 0 ? b1 : b2;
             const bool tp = active && b1 >= 0;
             const bool ign = active && b1 < 0 && (b2 >= 0 || dd.area < my_lo || dd.area > my_hi);
-            if (active && bj >= 0 && !(rmeta[bj] & CC_CROWD)) atomicOr(&taken[bj], (u64)(1ull << pair));
+            if (active && bj >= 0 && !(rmeta[bj] & EM_ROW_CROWD)) atomicOr(&taken[bj], (u64)(1ull << pair));
             const u64 tpm = __ballot(tp), igm = __ballot(ign);
             if (tid < p.A) {
                 unsigned w = 0;
@@ -200,79 +157,18 @@ __global__ __launch_bounds__(CC_THREADS) void cc_match_kernel(CcMatch p) {
     if (tid == 0 && p.kept) { p.kept[b] = kept; p.kept[p.B + b] = nans; }
 }
 
-// ---- append ----------------------------------------------------------------------------------------------------------------------
-struct CcAppend {
-    const float* det; const unsigned* flags; const int* rank; const int* kept; int B, max_det, A;
-    float* scores; int* classes; unsigned* words; int* ranks; unsigned capacity; unsigned* state;     // state: {cursor, lost, NaN scores, 0}
-};
-
-// workgroup b: image b's kept slots, in slot order, from cursor + the kept counts of the images before it
-__global__ __launch_bounds__(CC_THREADS) void cc_append_write_kernel(CcAppend a) {
-    __shared__ unsigned shu[CC_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    unsigned before = 0;
-    for (int k = tid; k < b; k += CC_THREADS) before += (unsigned)a.kept[k];
-    unsigned pos = fo_min(a.state[0], a.capacity) + cc_block_sum(before, shu, tid);
-    for (int i0 = 0; i0 < a.max_det; i0 += CC_THREADS) {
-        const int i = i0 + tid;
-        const long long slot = (long long)b * a.max_det + i;
-        const bool keep = i < a.max_det && !(a.flags[slot * a.A] & CC_DROPPED);
-        unsigned total;
-        const unsigned p = pos + fo_block_excl_scan(keep ? 1u : 0u, shu, tid, &total);
-        if (keep && p < a.capacity) {                                     // beyond the capacity: counted by the cursor launch
-            float v = a.det[slot * 6 + 4];
-            if (v == 0.f) v = 0.f;                                        // -0.0 is stored as +0.0: the two tie
-            a.scores[p] = v;
-            a.classes[p] = (int)a.det[slot * 6 + 5] - 1;
-            for (int w = 0; w < a.A; ++w) a.words[(long long)p * a.A + w] = a.flags[slot * a.A + w];
-            a.ranks[p] = a.rank[slot];
-        }
-        pos += total;
-    }
-}
-
-// one workgroup: the cursor moves (clamped to the capacity; the surplus and the NaN scores are counted)
-__global__ __launch_bounds__(CC_THREADS) void cc_append_cursor_kernel(CcAppend a) {
-    __shared__ unsigned shu[CC_WAVES];
-    const int tid = threadIdx.x;
-    unsigned kept = 0, nans = 0;
-    for (int k = tid; k < a.B; k += CC_THREADS) { kept += (unsigned)a.kept[k]; nans += (unsigned)a.kept[a.B + k]; }
-    kept = cc_block_sum(kept, shu, tid);
-    nans = cc_block_sum(nans, shu, tid);
-    if (tid == 0) {
-        const u64 end = (u64)fo_min(a.state[0], a.capacity) + kept;
-        if (end > a.capacity) {
-            const u64 lost = (u64)a.state[1] + (end - a.capacity);
-            a.state[1] = lost > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)lost;
-        }
-        a.state[0] = end > a.capacity ? a.capacity : (unsigned)end;
-        const u64 nn = (u64)a.state[2] + nans;
-        a.state[2] = nn > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)nn;
-    }
+// ---- append: the A flag words and the rank travel with (score, class) -------------------------------------------------------------
+struct CcAppend : EvAppend { const unsigned* flags; const int* rank; int A; unsigned* words; int* ranks; };
+DEV bool ev_keep(const CcAppend& a, long long slot, unsigned* word) { *word = a.flags[slot * a.A]; return !(*word & EM_DROPPED); }
+DEV void ev_store(const CcAppend& a, long long slot, unsigned p, unsigned) {      // the A words are read again, as they always were
+    for (int w = 0; w < a.A; ++w) a.words[(long long)p * a.A + w] = a.flags[slot * a.A + w];
+    a.ranks[p] = a.rank[slot];
 }
 
 // ---- sort: the pass descriptor of radix_sort.h; the payload is the entry's index --------------------------------------------------
 struct CcItem { u64 key; unsigned val; };
-struct CcSort {
-    typedef u64 Key;
-    typedef CcItem Item;
-    const float* scores; const int* classes;                              // the first pass reads these
-    const u64* src_k; const unsigned* src_v; u64* dst_k; unsigned* dst_v;
-    const unsigned* cursor; long long n_host;
-    unsigned* hist; unsigned* totals;
-    unsigned capacity, tiles;
-    int shift, first, C;
-};
-DEV RsProblem rs_problem(const CcSort& s, unsigned) { return RsProblem{cc_live(s.cursor, s.n_host, s.capacity), s.hist, s.totals, s.tiles}; }
-// (class << 32) | ~key(score): ascending = class, then score descending.  A class outside 0..C-1 or a NaN score gets class C.
-DEV u64 rs_key(const CcSort& s, unsigned, unsigned i) {
-    if (!s.first) return s.src_k[i];
-    const int c = s.classes[i];
-    float v = s.scores[i];
-    const bool ok = c >= 0 && c < s.C && v == v;
-    if (v == 0.f) v = 0.f;
-    return ((u64)(ok ? (unsigned)c : (unsigned)s.C) << 32) | (u64)(~fo_key(__float_as_uint(v)));
-}
+struct CcSort : EvSort { typedef CcItem Item; };
+DEV u64 rs_key(const CcSort& s, unsigned, unsigned i) { return ev_key(s, i, [](unsigned) { return true; }); }
 DEV CcItem rs_load(const CcSort& s, unsigned, unsigned i) {
     CcItem e;
     e.key = rs_key(s, 0, i);
@@ -288,7 +184,7 @@ struct CcGather {
 // thread i: the words and the rank of the entry at sorted position i
 __global__ __launch_bounds__(CC_THREADS) void cc_gather_kernel(CcGather g) {
     const unsigned i = blockIdx.x * CC_THREADS + threadIdx.x;
-    if (i >= cc_live(g.cursor, g.n_host, g.capacity)) return;
+    if (i >= ev_live(g.cursor, g.n_host, g.capacity)) return;
     const unsigned src = g.index[i];
     if (src >= g.capacity) return;
     for (int w = 0; w < g.A; ++w) g.out_words[(long long)i * g.A + w] = g.words[(long long)src * g.A + w];
@@ -306,8 +202,8 @@ struct CcAp {
 
 // workgroup (c, (t, a, m)): bit 0 of an entry = it counts (rank < max_dets[m], not ignored at (t, a)), bit 1 = true positive
 __global__ __launch_bounds__(CC_THREADS) void cc_ap_kernel(CcAp p) {
-    __shared__ unsigned shu[CC_WAVES];
-    __shared__ double shd[CC_WAVES];
+    __shared__ unsigned shu[EV_WAVES];
+    __shared__ double shd[EV_WAVES];
     __shared__ int kr[CC_MAX_R];
     __shared__ double q[CC_MAX_R];
     const int c = blockIdx.x, tid = threadIdx.x;
@@ -315,10 +211,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_ap_kernel(CcAp p) {
     int md = 0;
 #pragma unroll
     for (int k = 0; k < CC_MAX_MX; ++k) if (k == m) md = p.maxdet[k];
-    const unsigned n = cc_live(p.state, p.n_host, p.capacity);
-    const u64 k_lo = (u64)c << 32, k_hi = (u64)(c + 1) << 32;
-    const unsigned s = fo_partition_point(p.keys, n, [=](u64 v) { return v < k_lo; });
-    const unsigned e = fo_partition_point(p.keys, n, [=](u64 v) { return v < k_hi; });
+    const unsigned n = ev_live(p.state, p.n_host, p.capacity);
+    const unsigned s = ev_class_begin(p.keys, n, c), e = ev_class_begin(p.keys, n, c + 1);
     const int ng = p.npig[(long long)c * p.A + a];
     const unsigned tp_bit = 1u << t, ig_bit = 1u << (16 + t);
     auto entry = [&](unsigned i) -> unsigned {       // i < e
@@ -354,18 +248,18 @@ __global__ __launch_bounds__(CC_THREADS) void cc_ap_kernel(CcAp p) {
                 const unsigned f = entry(i);
                 tot += (f & 1u) + ((f & 2u) ? 0x10000u : 0u);
             }
-            rem_n += cc_block_sum(tot & 0xFFFFu, shu, tid);
-            rem_tp += cc_block_sum(tot >> 16, shu, tid);
+            rem_n += ev_block_sum<unsigned>(tot & 0xFFFFu, shu, tid);
+            rem_tp += ev_block_sum<unsigned>(tot >> 16, shu, tid);
         }
         tot_tp = rem_tp;
         __syncthreads();                                                  // kr and q are written
         double carry = 0.0;                                               // largest precision of the chunks behind this one
-        const unsigned nchunks = (e - s + CC_AP_CHUNK - 1) / CC_AP_CHUNK;
+        const unsigned nchunks = (e - s + EV_AP_CHUNK - 1) / EV_AP_CHUNK;
         for (unsigned ch = nchunks; ch-- > 0;) {
-            const unsigned i0 = s + ch * CC_AP_CHUNK + (unsigned)tid * CC_AP_ITEMS;
-            unsigned f[CC_AP_ITEMS], cnt = 0;
+            const unsigned i0 = s + ch * EV_AP_CHUNK + (unsigned)tid * EV_AP_ITEMS;
+            unsigned f[EV_AP_ITEMS], cnt = 0;
 #pragma unroll
-            for (int r = 0; r < CC_AP_ITEMS; ++r) {
+            for (int r = 0; r < EV_AP_ITEMS; ++r) {
                 f[r] = i0 + r < e ? entry(i0 + r) : 0u;
                 cnt += (f[r] & 1u) + ((f[r] & 2u) ? 0x10000u : 0u);
             }
@@ -373,20 +267,20 @@ __global__ __launch_bounds__(CC_THREADS) void cc_ap_kernel(CcAp p) {
             const unsigned ex = fo_block_excl_scan(cnt, shu, tid, &total);
             rem_n -= total & 0xFFFFu; rem_tp -= total >> 16;              // now: the counts in front of this chunk
             unsigned rank = rem_n + (ex & 0xFFFFu), ctp = rem_tp + (ex >> 16);
-            double prec[CC_AP_ITEMS];
-            unsigned at_rank[CC_AP_ITEMS], at_tp[CC_AP_ITEMS];
+            double prec[EV_AP_ITEMS];
+            unsigned at_rank[EV_AP_ITEMS], at_tp[EV_AP_ITEMS];
 #pragma unroll
-            for (int r = 0; r < CC_AP_ITEMS; ++r) {
+            for (int r = 0; r < EV_AP_ITEMS; ++r) {
                 rank += f[r] & 1u; ctp += (f[r] >> 1) & 1u;
                 at_rank[r] = rank; at_tp[r] = ctp;
                 prec[r] = (f[r] & 1u) ? (double)ctp / ((double)rank + 0x1p-52) : 0.0;      // (fp + tp) + eps: rank is their exact sum
             }
 #pragma unroll
-            for (int r = CC_AP_ITEMS - 2; r >= 0; --r) prec[r] = fmax(prec[r], prec[r + 1]);      // envelope inside the thread
+            for (int r = EV_AP_ITEMS - 2; r >= 0; --r) prec[r] = fmax(prec[r], prec[r + 1]);      // envelope inside the thread
             double chunk_max;
-            const double later = fmax(cc_block_excl_rmax(prec[0], shd, tid, &chunk_max), carry);
+            const double later = fmax(ev_block_excl_rmax(prec[0], shd, tid, &chunk_max), carry);
 #pragma unroll
-            for (int r = 0; r < CC_AP_ITEMS; ++r) {
+            for (int r = 0; r < EV_AP_ITEMS; ++r) {
                 if (!(f[r] & 1u)) continue;
                 const double env = fmax(prec[r], later);
                 if (at_rank[r] == 1u)                                     // the first entry: every threshold that the count 0 reaches
@@ -418,22 +312,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_ap_kernel(CcAp p) {
 }
 
 // ---- workspace layout (host) -------------------------------------------------------------------------------------------------------
-struct CcLayout { long long keys[2], vals[2], hist, totals, words, ranks, total; unsigned tiles; int passes; };
-
-bool cc_layout(long long capacity, int C, int A, CcLayout* L) {
-    if (capacity < 1 || capacity > CC_MAX_N || C < 1 || C > CC_MAX_C || A < 1 || A > CC_MAX_A) return false;
-    long long off = 0;
-    auto take = [&off](long long bytes) { const long long o = off; off += (bytes + 255) & ~255ll; return o; };
-    L->tiles = (unsigned)((capacity + RS_TILE - 1) / RS_TILE);
-    L->passes = C <= 255 ? 5 : 6;                                         // 4 score digits, then the class (C itself is a key)
-    for (int k = 0; k < 2; ++k) { L->keys[k] = take(capacity * 8); L->vals[k] = take(capacity * 4); }
-    L->hist = take(256ll * L->tiles * 4);
-    L->totals = take(256 * 4);
-    L->words = take(capacity * 4 * A);
-    L->ranks = take(capacity * 4);
-    L->total = off;
-    return true;
-}
+// the sort's buffers, then the gathered words [capacity][A] and ranks [capacity]
+bool cc_layout(long long capacity, int C, int A, EvLayout* L) { return A >= 1 && A <= EM_MAX_A && ev_layout(capacity, C, 4ll * A, 4, L); }
 
 }  // namespace
 
@@ -445,15 +325,10 @@ extern "C" int effdet_coco_match(void* stream, const float* det, const int* det_
     EFFDET_ENTER();
     if (!det || !det_count || !gt_boxes || !gt_cls || !thresholds || !area_ranges || !flags || !rank || !npig)
         return EFFDET_EINVAL;      // null pointer
-    if (num_thresholds < 1 || num_thresholds > CC_MAX_T) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 15
-    for (int t = 0; t < num_thresholds; ++t)
-        if (!(thresholds[t] == thresholds[t]) || (t > 0 && !(thresholds[t] > thresholds[t - 1])))
-            return EFFDET_EINVAL;      // thresholds must ascend
-    if (num_areas < 1 || num_areas > CC_MAX_A) return EFFDET_EINVAL;      // 1 <= num_areas <= 4
-    for (int a = 0; a < num_areas; ++a)
-        if (!(area_ranges[2 * a] <= area_ranges[2 * a + 1])) return EFFDET_EINVAL;      // an area range needs lo <= hi
-    if (B <= 0 || max_det <= 0 || M <= 0 || (long long)B * max_det > CC_MAX_N) return EFFDET_EINVAL;      // bad B, max_det or M
-    if (num_classes < 1 || num_classes > CC_MAX_C) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
+    if (!em_thresholds_ok(thresholds, num_thresholds, EM_MAX_T)) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 15, ascending, no NaN
+    if (!em_areas_ok(area_ranges, num_areas)) return EFFDET_EINVAL;      // 1 <= num_areas <= 4, an area range needs lo <= hi
+    if (!em_slots_ok(B, max_det) || M <= 0) return EFFDET_EINVAL;      // bad B, max_det or M
+    if (!em_classes_ok(num_classes)) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
     if (max_rank < 1) return EFFDET_EINVAL;      // max_rank (the largest max_dets) must be positive
     if (min_score != min_score) return EFFDET_EINVAL;      // min_score is NaN
     const size_t sh = cc_match_lds(M, num_classes);
@@ -462,8 +337,8 @@ extern "C" int effdet_coco_match(void* stream, const float* det, const int* det_
     a.det = det; a.det_count = det_count; a.gt_boxes = gt_boxes; a.gt_cls = gt_cls; a.gt_crowd = gt_crowd; a.gt_area = gt_area;
     a.B = B; a.max_det = max_det; a.M = M; a.C = num_classes; a.T = num_thresholds; a.A = num_areas; a.max_rank = max_rank;
     a.min_score = min_score;
-    for (int t = 0; t < CC_MAX_T; ++t) a.thr[t] = t < num_thresholds ? thresholds[t] : 0.f;
-    for (int k = 0; k < CC_MAX_A; ++k) { a.lo[k] = k < num_areas ? area_ranges[2 * k] : 0.f; a.hi[k] = k < num_areas ? area_ranges[2 * k + 1] : 0.f; }
+    for (int t = 0; t < EM_MAX_T; ++t) a.thr[t] = t < num_thresholds ? thresholds[t] : 0.f;
+    for (int k = 0; k < EM_MAX_A; ++k) { a.lo[k] = k < num_areas ? area_ranges[2 * k] : 0.f; a.hi[k] = k < num_areas ? area_ranges[2 * k + 1] : 0.f; }
     a.flags = flags; a.rank = rank; a.kept = kept; a.npig = npig;
     hipLaunchKernelGGL(cc_match_kernel, dim3(B), dim3(CC_THREADS), sh, reinterpret_cast<hipStream_t>(stream), a);
     return effdet_check_launch();
@@ -474,31 +349,27 @@ extern "C" int effdet_coco_append(void* stream, const float* det, const unsigned
                                   long long capacity, unsigned int* state) {
     EFFDET_ENTER();
     if (!det || !flags || !rank || !kept || !scores || !classes || !words || !ranks || !state) return EFFDET_EINVAL;      // null pointer
-    if (B <= 0 || max_det <= 0 || (long long)B * max_det > CC_MAX_N) return EFFDET_EINVAL;      // bad B or max_det
-    if (num_areas < 1 || num_areas > CC_MAX_A) return EFFDET_EINVAL;      // 1 <= num_areas <= 4
-    if (capacity < 1 || capacity > CC_MAX_N) return EFFDET_EINVAL;      // 1 <= capacity <= 2^24
-    CcAppend a{det, flags, rank, kept, B, max_det, num_areas, scores, classes, words, ranks, (unsigned)capacity, state};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(cc_append_write_kernel, dim3(B), dim3(CC_THREADS), 0, st, a);
-    hipLaunchKernelGGL(cc_append_cursor_kernel, dim3(1), dim3(CC_THREADS), 0, st, a);
-    return effdet_check_launch();
+    if (!em_slots_ok(B, max_det)) return EFFDET_EINVAL;      // bad B or max_det
+    if (num_areas < 1 || num_areas > EM_MAX_A) return EFFDET_EINVAL;      // 1 <= num_areas <= 4
+    if (!ev_capacity_ok(capacity)) return EFFDET_EINVAL;      // 1 <= capacity <= 2^24
+    const CcAppend a{{det, kept, B, max_det, scores, classes, (unsigned)capacity, state}, flags, rank, num_areas, words, ranks};
+    return ev_append(stream, a);
 }
 
 extern "C" long long effdet_coco_sorted_workspace_bytes(long long capacity, int num_classes, int num_areas) {
-    CcLayout L;
+    EvLayout L;
     return cc_layout(capacity, num_classes, num_areas, &L) ? L.total : (long long)EFFDET_EINVAL;
 }
 
 extern "C" long long effdet_coco_sorted_offset(long long capacity, int num_classes, int num_areas, int which) {
-    CcLayout L;
+    EvLayout L;
     if (which < 0 || which > 3 || !cc_layout(capacity, num_classes, num_areas, &L)) return EFFDET_EINVAL;
-    const int last = (L.passes - 1) & 1;
-    return which == 0 ? L.keys[last] : which == 1 ? L.vals[last] : which == 2 ? L.words : L.ranks;
+    return which == 0 ? L.keys[ev_last(L)] : which == 1 ? L.vals[ev_last(L)] : L.extra[which - 2];
 }
 
 extern "C" long long effdet_coco_sorted_result_bytes(int num_thresholds, int num_classes, int num_areas, int num_max_dets) {
-    if (num_thresholds < 1 || num_thresholds > CC_MAX_T || num_classes < 1 || num_classes > CC_MAX_C || num_areas < 1 ||
-        num_areas > CC_MAX_A || num_max_dets < 1 || num_max_dets > CC_MAX_MX)
+    if (num_thresholds < 1 || num_thresholds > EM_MAX_T || !em_classes_ok(num_classes) || num_areas < 1 || num_areas > EM_MAX_A ||
+        num_max_dets < 1 || num_max_dets > CC_MAX_MX)
         return EFFDET_EINVAL;
     return 8ll * (CC_RESULT_HEAD + 2ll * num_thresholds * num_classes * num_areas * num_max_dets + (long long)num_classes * num_areas);
 }
@@ -511,12 +382,12 @@ extern "C" int effdet_coco_sorted(void* stream, const float* scores, const int* 
     if (!scores || !classes || !words || !ranks || !max_dets || !rec_thr || !npig || !workspace || !result)
         return EFFDET_EINVAL;      // null pointer
     if (n < 0 && !state) return EFFDET_EINVAL;      // n < 0 takes the count from `state`, which is null
-    if (num_thresholds < 1 || num_thresholds > CC_MAX_T) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 15
+    if (num_thresholds < 1 || num_thresholds > EM_MAX_T) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 15
     if (num_max_dets < 1 || num_max_dets > CC_MAX_MX) return EFFDET_EINVAL;      // 1 <= num_max_dets <= 4
     for (int k = 0; k < num_max_dets; ++k)
         if (max_dets[k] < 1 || (k > 0 && max_dets[k] <= max_dets[k - 1])) return EFFDET_EINVAL;      // max_dets must be positive and ascend
     if (num_rec < 1 || num_rec > CC_MAX_R) return EFFDET_EINVAL;      // 1 <= num_rec <= 256
-    CcLayout L;
+    EvLayout L;
     if (!cc_layout(capacity, num_classes, num_areas, &L)) return EFFDET_EINVAL;      // capacity in [1, 2^24], classes in [1, 65535], areas in [1, 4]
     if (n > capacity) return EFFDET_EINVAL;      // n exceeds the capacity
     if (workspace_bytes < L.total) return EFFDET_EINVAL;      // workspace too small
@@ -526,23 +397,12 @@ extern "C" int effdet_coco_sorted(void* stream, const float* scores, const int* 
     char* ws = reinterpret_cast<char*>(workspace);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long long n_host = n < 0 ? -1 : n;
-    CcSort s;
-    s.scores = scores; s.classes = classes; s.cursor = state; s.n_host = n_host;
-    s.hist = reinterpret_cast<unsigned*>(ws + L.hist); s.totals = reinterpret_cast<unsigned*>(ws + L.totals);
-    s.capacity = (unsigned)capacity; s.tiles = L.tiles; s.C = num_classes;
-    const unsigned grid = n_host < 0 ? L.tiles : (unsigned)((n_host + RS_TILE - 1) / RS_TILE);
-    for (int pass = 0; pass < L.passes && grid > 0; ++pass) {             // entries -> buffers 0 -> 1 -> 0 ...
-        const int d = pass & 1;
-        s.shift = 8 * pass; s.first = pass == 0;
-        s.src_k = reinterpret_cast<const u64*>(ws + L.keys[1 - d]); s.src_v = reinterpret_cast<const unsigned*>(ws + L.vals[1 - d]);
-        s.dst_k = reinterpret_cast<u64*>(ws + L.keys[d]); s.dst_v = reinterpret_cast<unsigned*>(ws + L.vals[d]);
-        rs_sort_pass(st, s, grid, 1);
-    }
-    const int last = (L.passes - 1) & 1;
+    const unsigned grid = ev_sort(st, CcSort(), scores, classes, state, n_host, capacity, num_classes, ws, L, [](CcSort&, int) {});
+    const int last = ev_last(L);
     CcGather g;
     g.index = reinterpret_cast<const unsigned*>(ws + L.vals[last]); g.words = words; g.ranks = ranks;
     g.cursor = state; g.n_host = n_host; g.capacity = (unsigned)capacity; g.A = num_areas;
-    g.out_words = reinterpret_cast<unsigned*>(ws + L.words); g.out_ranks = reinterpret_cast<int*>(ws + L.ranks);
+    g.out_words = reinterpret_cast<unsigned*>(ws + L.extra[0]); g.out_ranks = reinterpret_cast<int*>(ws + L.extra[1]);
     if (grid > 0) hipLaunchKernelGGL(cc_gather_kernel, dim3(grid * (RS_TILE / CC_THREADS)), dim3(CC_THREADS), 0, st, g);
     CcAp a;
     a.keys = reinterpret_cast<const u64*>(ws + L.keys[last]); a.words = g.out_words; a.ranks = g.out_ranks;

@@ -1,10 +1,13 @@
-// What the two greedy matchers (evaluation.hip: one threshold, a `tp` label per slot; eval_scale.hip: up to 16 thresholds, a flag
-// word per slot) and the open words of eval_scale.hip state once: the float32 IoU, the staging of an image's
-// ground truth with its per-class counters, and the search for a detection's candidate box.  One workgroup of EM_THREADS threads
-// per image.  What thread 0 does with the candidate differs between the two kernels and stays there.  coco_eval.hip and
-// lvis_eval.hip share the IoU and the walk of a detection's IoU row by the lane that owns an (IoU threshold, area range) pair.
+// What the greedy matchers state once.  One workgroup of EM_THREADS threads per image.
+//   evaluation.hip (one threshold, a `tp` label per slot), eval_scale.hip (up to 16 thresholds, a flag word per slot, and its open
+//   words): the float32 IoU, the staging of an image's ground truth with its per-class counters (em_stage_gt) and the search for
+//   a detection's candidate box (em_best_box).  What thread 0 does with the candidate differs between the kernels and stays there.
+//   coco_eval.hip, lvis_eval.hip (the COCO rule per (IoU threshold, area range) pair, A flag words per slot): the IoU, the limits
+//   and the flag bits, and the walk of a detection's IoU row by the lane that owns a pair (em_walk_row).  The staging, the row and
+//   the verdict are written out in both kernels: stated once here they compiled to slower kernels (profiles/README.md, eval_shared_*).
+//   All four units: the host-side argument checks of their C ABI (em_slots_ok, em_classes_ok, em_thresholds_ok, em_areas_ok).
 //
-// Both units are compiled with -ffp-contract=off: the IoU must round like the reference's separate float32 numpy operations
+// The units are compiled with -ffp-contract=off: the IoU must round like the reference's separate float32 numpy operations
 // (effdet/evaluation/np_box_ops.py), so its operations stay in this order, one rounding each.
 #pragma once
 #include "common.h"
@@ -32,11 +35,15 @@ DEV float em_iou_crowd(const EmDet& d, float g0, float g1, float g2, float g3) {
     return (ih * iw) / d.area;
 }
 
+// ---- the COCO rule (coco_eval.hip:6-25), for coco_eval.hip and lvis_eval.hip ------------------------------------------------------
+constexpr int EM_MAX_T = 15, EM_MAX_A = 4;                      // T A <= 60 pairs: a lane of wave 0 each, a bit of `taken` each
+constexpr unsigned EM_DROPPED = 0x80000000u;                    // a slot's flag words: bit t true positive, bit 16 + t ignored, bit 31
+constexpr int EM_ROW_CROWD = 1 << 4, EM_ROW_OF_CLASS = 1 << 5;  // box bits beside the ignore bits 0 .. A-1
+
 // The lane that owns pair (t, a) of coco_eval.hip / lvis_eval.hip walks the detection's IoU row in LDS.  rmeta[j]: 0 for a box of
 // another class, else EM_ROW_OF_CLASS | EM_ROW_CROWD (a crowd region) | bit a (ignored at area range a); taken[j] bit `pair`: taken
 // at this pair (a crowd region stays free).  -> *free_box: the box not ignored at a with the largest IoU >= thr, the LAST index on
 // equal IoU (>=); *ign_box: the same among the ignored boxes; -1 where there is none.  Every lane reads the same words: broadcasts.
-constexpr int EM_ROW_CROWD = 1 << 4, EM_ROW_OF_CLASS = 1 << 5;
 DEV void em_walk_row(const int* rmeta, const unsigned long long* taken, const float* iou, int M, int pair, int a, float thr,
                      int* free_box, int* ign_box) {
     int b1 = -1, b2 = -1;
@@ -52,6 +59,8 @@ DEV void em_walk_row(const int* rmeta, const unsigned long long* taken, const fl
     *free_box = b1; *ign_box = b2;
 }
 
+
+// ---- the PASCAL matchers (evaluation.hip, eval_scale.hip) -----------------------------------------------------------------------------
 // All threads call it, once, before the first search.  LDS: seen[C] = 0 (class already had its top-scoring detection), taken[M] = 0,
 // gcls[M] = the 0-based class of box j of image b or -1, and, when gdif is given, gdif[M] = the box is `difficult` (gt_difficult
 // may be null: none is).  Then the counters, by integer atomics (order independent): gt_count[c] += boxes of class c - with gdif,
@@ -103,6 +112,27 @@ DEV int em_best_box(const EmDet& d, int c, const float* gt_boxes, const int* gcl
             if (red_v[w] > best || (red_v[w] == best && red_i[w] < bj)) { best = red_v[w]; bj = red_i[w]; }
     *iou = best;
     return bj;
+}
+
+// ---- host: the argument checks of the units' C ABI -----------------------------------------------------------------------------------
+constexpr long long EM_MAX_N = 1ll << 24;                       // slots of a call, entries of a buffer
+constexpr int EM_MAX_C = 65535;
+// B images of max_det slots
+bool em_slots_ok(int B, int max_det) { return B > 0 && max_det > 0 && (long long)B * max_det <= EM_MAX_N; }
+bool em_classes_ok(int num_classes, int least = 1) { return num_classes >= least && num_classes <= EM_MAX_C; }
+// 1 .. max_T thresholds, none NaN, ascending
+bool em_thresholds_ok(const float* thr, int T, int max_T) {
+    if (T < 1 || T > max_T) return false;
+    for (int t = 0; t < T; ++t)
+        if (!(thr[t] == thr[t]) || (t > 0 && !(thr[t] > thr[t - 1]))) return false;
+    return true;
+}
+// 1 .. EM_MAX_A area ranges [A][2], lo <= hi each (a NaN bound is refused)
+bool em_areas_ok(const float* area_ranges, int A) {
+    if (A < 1 || A > EM_MAX_A) return false;
+    for (int a = 0; a < A; ++a)
+        if (!(area_ranges[2 * a] <= area_ranges[2 * a + 1])) return false;
+    return true;
 }
 
 }  // namespace

@@ -8,7 +8,8 @@
 //            difficult is IGNORED at the thresholds its IoU reaches (per_image_evaluation.py:391-407, :471).  One flag word per slot.
 //   append   (score, class, flag word) of the valid slots -> capacity-sized buffers at a cursor that lives on the device, in (image,
 //            slot) order: the images' kept counts come from the match launch, a workgroup adds up the counts of the images before
-//            its own, a one-workgroup launch moves the cursor.  No atomic decides a position.
+//            its own, a one-workgroup launch moves the cursor.  No atomic decides a position.  (ev_append of eval_sorted.h, which
+//            states the accumulate stage once for this unit and coco_eval.hip: reductions, append, key, layout, passes.)
 //   sort     the stable LSD radix sort of radix_sort.h over 48-bit keys (class, then score descending) with the flag word as payload,
 //            five passes, six beyond 255 classes.  Equal scores keep their arrival order; every class is one contiguous segment;
 //            invalid entries sort behind the last class.
@@ -29,62 +30,14 @@
 #include "compact.h"
 #include "radix_sort.h"
 #include "eval_match.h"
+#include "eval_sorted.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int ES_THREADS = 256;
-constexpr int ES_WAVES = ES_THREADS / 64;
-static_assert(ES_THREADS == FO_THREADS && ES_THREADS == EM_THREADS, "the shared headers are written for this workgroup size");
-constexpr int ES_AP_ITEMS = 8;
-constexpr int ES_AP_CHUNK = ES_THREADS * ES_AP_ITEMS;             // segment entries of one AP step (counts fit 16 bits)
-constexpr long long ES_MAX_N = 1ll << 24;
-constexpr int ES_MAX_T = 16, ES_MAX_C = 65535;
+constexpr int ES_THREADS = EV_THREADS;
+constexpr int ES_MAX_T = 16;
 constexpr unsigned ES_INVALID = 0x80000000u;
 constexpr int ES_RESULT_HEAD = 8;                                 // 8-byte words before the AP matrix
-
-// keys[0 .. n) sorted: the first entry of class c (the search of compact.h: the trip count follows from n alone, every read is at
-// an index < n).  Class c is the segment [es_class_begin(c), es_class_begin(c + 1)).
-DEV unsigned es_class_begin(const u64* keys, unsigned n, int c) {
-    const u64 k = (u64)c << 32;
-    return fo_partition_point(keys, n, [=](u64 v) { return v < k; });
-}
-
-// ---- workgroup reductions in float64 order: all ES_THREADS threads call them; sh: [ES_WAVES] in LDS, free again when the call
-// returns.  (The integer scan is fo_block_excl_scan of compact.h.) ------------------------------------------------------------------
-// sum in a fixed order (butterfly inside a wave, then the waves in order): the same bits every run
-template <typename V> DEV V es_block_sum(V v, V* sh, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-    if ((tid & 63) == 0) sh[tid >> 6] = v;
-    __syncthreads();
-    V tot = sh[0];
-#pragma unroll
-    for (int w = 1; w < ES_WAVES; ++w) tot = tot + sh[w];
-    __syncthreads();
-    return tot;
-}
-// maximum over the threads above this one (0 for the last); *total: over all.  Values are >= 0.
-DEV double es_block_excl_rmax(double v, double* sh, int tid, double* total) {
-    const int lane = tid & 63, wave = tid >> 6;
-    double incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_down(incl, o, 64);
-        if (lane + o < 64) incl = fmax(incl, t);
-    }
-    const double nxt = __shfl_down(incl, 1, 64);
-    double ex = lane < 63 ? nxt : 0.0;
-    if (lane == 0) sh[wave] = incl;
-    __syncthreads();
-    double tot = 0.0;
-#pragma unroll
-    for (int w = 0; w < ES_WAVES; ++w) { const double s = sh[w]; if (w > wave) ex = fmax(ex, s); tot = fmax(tot, s); }
-    __syncthreads();
-    *total = tot;
-    return ex;
-}
 
 // ---- matching --------------------------------------------------------------------------------------------------------------------
 struct EsMatch {
@@ -140,90 +93,25 @@ __global__ __launch_bounds__(ES_THREADS) void es_match_kernel(EsMatch p) {
     if (tid == 0 && p.kept) { p.kept[b] = kept; p.kept[p.B + b] = nans; }
 }
 
-// ---- append ----------------------------------------------------------------------------------------------------------------------
-struct EsAppend {
-    const float* det; const unsigned* flags; const int* kept; int B, max_det;
-    float* scores; int* classes; unsigned* out_flags; unsigned capacity; unsigned* state;     // state: {cursor, lost, NaN scores, 0}
-    const unsigned* open; unsigned* out_open;                                                 // the open words (null: none), same positions
-};
-
-// workgroup b: image b's valid slots, in slot order, from cursor + the kept counts of the images before it
-__global__ __launch_bounds__(ES_THREADS) void es_append_write_kernel(EsAppend a) {
-    __shared__ unsigned shu[ES_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    unsigned before = 0;
-    for (int k = tid; k < b; k += ES_THREADS) before += (unsigned)a.kept[k];
-    unsigned pos = fo_min(a.state[0], a.capacity) + es_block_sum<unsigned>(before, shu, tid);
-    for (int i0 = 0; i0 < a.max_det; i0 += ES_THREADS) {
-        const int i = i0 + tid;
-        const long long slot = (long long)b * a.max_det + i;
-        const unsigned f = i < a.max_det ? a.flags[slot] : ES_INVALID;
-        const bool keep = !(f & ES_INVALID);
-        unsigned total;
-        const unsigned p = pos + fo_block_excl_scan(keep ? 1u : 0u, shu, tid, &total);
-        if (keep && p < a.capacity) {                                     // beyond the capacity: counted by the cursor launch
-            float v = a.det[slot * 6 + 4];
-            if (v == 0.f) v = 0.f;                                        // -0.0 is stored as +0.0: the two tie
-            a.scores[p] = v;
-            a.classes[p] = (int)a.det[slot * 6 + 5] - 1;
-            a.out_flags[p] = f;
-            if (a.out_open) a.out_open[p] = a.open[slot];
-        }
-        pos += total;
-    }
+// ---- append: the flag word travels with (score, class), and the open word (null: none) at the same position ---------------------
+struct EsAppend : EvAppend { const unsigned* flags; unsigned* out_flags; const unsigned* open; unsigned* out_open; };
+DEV bool ev_keep(const EsAppend& a, long long slot, unsigned* word) { *word = a.flags[slot]; return !(*word & ES_INVALID); }
+DEV void ev_store(const EsAppend& a, long long slot, unsigned p, unsigned word) {
+    a.out_flags[p] = word;
+    if (a.out_open) a.out_open[p] = a.open[slot];
 }
 
-// one workgroup: the cursor moves (clamped to the capacity; the surplus and the NaN scores are counted)
-__global__ __launch_bounds__(ES_THREADS) void es_append_cursor_kernel(EsAppend a) {
-    __shared__ unsigned shu[ES_WAVES];
-    const int tid = threadIdx.x;
-    unsigned kept = 0, nans = 0;
-    for (int k = tid; k < a.B; k += ES_THREADS) { kept += (unsigned)a.kept[k]; nans += (unsigned)a.kept[a.B + k]; }
-    kept = es_block_sum<unsigned>(kept, shu, tid);
-    nans = es_block_sum<unsigned>(nans, shu, tid);
-    if (tid == 0) {
-        const u64 end = (u64)fo_min(a.state[0], a.capacity) + kept;
-        if (end > a.capacity) {
-            const u64 lost = (u64)a.state[1] + (end - a.capacity);
-            a.state[1] = lost > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)lost;
-        }
-        a.state[0] = end > a.capacity ? a.capacity : (unsigned)end;
-        const u64 nn = (u64)a.state[2] + nans;
-        a.state[2] = nn > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)nn;
-    }
-}
-
-// ---- sort: the pass descriptor of radix_sort.h (one problem; W2: a second payload word, the open word) -----------------------------
+// ---- sort: the pass descriptor of radix_sort.h (W2: a second payload word, the open word) ------------------------------------------
 template <bool W2> struct EsItem { u64 key; unsigned val; };
 template <> struct EsItem<true> { u64 key; unsigned val, open; };
-template <bool W2> struct EsSort {
-    typedef u64 Key;
+template <bool W2> struct EsSort : EvSort {
     typedef EsItem<W2> Item;
-    const float* scores; const int* classes; const unsigned* flags;      // the first pass reads these
-    const u64* src_k; const unsigned* src_v; u64* dst_k; unsigned* dst_v;
+    const unsigned* flags;                                                // the first pass reads these
     const unsigned* open; const unsigned* src_w; unsigned* dst_w;         // W2 only
-    const unsigned* cursor; long long n_host;                             // live count: n_host, or min(*cursor, capacity) when n_host < 0
-    unsigned* hist; unsigned* totals;
-    unsigned capacity, tiles;                                             // tiles by capacity: the row pitch of hist
-    int shift, first, C;
 };
-
-DEV unsigned es_live(const unsigned* cursor, long long n_host, unsigned capacity) {
-    return n_host >= 0 ? (unsigned)n_host : fo_min(cursor[0], capacity);
-}
-template <bool W2> DEV RsProblem rs_problem(const EsSort<W2>& s, unsigned) {
-    return RsProblem{es_live(s.cursor, s.n_host, s.capacity), s.hist, s.totals, s.tiles};
-}
-// (class << 32) | ~key(score): ascending = class, then score descending.  Invalid entries (flag bit 31, class outside 0..C-1, NaN
-// score) get class C: behind every class.
+// an entry whose flag word has bit 31 is not valid
 template <bool W2> DEV u64 rs_key(const EsSort<W2>& s, unsigned, unsigned i) {
-    if (!s.first) return s.src_k[i];
-    const unsigned f = s.flags[i];
-    const int c = s.classes[i];
-    float v = s.scores[i];
-    const bool ok = !(f & ES_INVALID) && c >= 0 && c < s.C && v == v;
-    if (v == 0.f) v = 0.f;
-    return ((u64)(ok ? (unsigned)c : (unsigned)s.C) << 32) | (u64)(~fo_key(__float_as_uint(v)));
+    return ev_key(s, i, [&s](unsigned k) { return !(s.flags[k] & ES_INVALID); });
 }
 template <bool W2> DEV EsItem<W2> rs_load(const EsSort<W2>& s, unsigned, unsigned i) {
     EsItem<W2> e;
@@ -248,11 +136,11 @@ struct EsAp {
 
 // workgroup (c, t): AP of class c at threshold t, and the (c, t) entries of the result block
 __global__ __launch_bounds__(ES_THREADS) void es_ap_kernel(EsAp a) {
-    __shared__ unsigned shu[ES_WAVES];
-    __shared__ double shd[ES_WAVES];
+    __shared__ unsigned shu[EV_WAVES];
+    __shared__ double shd[EV_WAVES];
     const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
-    const unsigned n = es_live(a.state, a.n_host, a.capacity);
-    const unsigned s = es_class_begin(a.keys, n, c), e = es_class_begin(a.keys, n, c + 1);
+    const unsigned n = ev_live(a.state, a.n_host, a.capacity);
+    const unsigned s = ev_class_begin(a.keys, n, c), e = ev_class_begin(a.keys, n, c + 1);
     const int ng = a.gt_count[c];
     const unsigned tp_bit = 1u << t, ig_bit = 1u << (16 + t);
     double acc = 0.0;
@@ -266,17 +154,17 @@ __global__ __launch_bounds__(ES_THREADS) void es_ap_kernel(EsAp a) {
                 const unsigned f = a.flags[i];
                 tot += ((f & ig_bit) ? 0u : 1u) + ((f & tp_bit) ? 0x10000u : 0u);
             }
-            rem_ni += es_block_sum<unsigned>(tot & 0xFFFFu, shu, tid);
-            rem_tp += es_block_sum<unsigned>(tot >> 16, shu, tid);
+            rem_ni += ev_block_sum<unsigned>(tot & 0xFFFFu, shu, tid);
+            rem_tp += ev_block_sum<unsigned>(tot >> 16, shu, tid);
         }
         const double dng = (double)ng;
         double carry = 0.0;                                               // largest precision of the chunks behind this one
-        const unsigned nchunks = (e - s + ES_AP_CHUNK - 1) / ES_AP_CHUNK;
+        const unsigned nchunks = (e - s + EV_AP_CHUNK - 1) / EV_AP_CHUNK;
         for (unsigned q = nchunks; q-- > 0;) {
-            const unsigned i0 = s + q * ES_AP_CHUNK + (unsigned)tid * ES_AP_ITEMS;
-            unsigned f[ES_AP_ITEMS], cnt = 0;
+            const unsigned i0 = s + q * EV_AP_CHUNK + (unsigned)tid * EV_AP_ITEMS;
+            unsigned f[EV_AP_ITEMS], cnt = 0;
 #pragma unroll
-            for (int r = 0; r < ES_AP_ITEMS; ++r) {
+            for (int r = 0; r < EV_AP_ITEMS; ++r) {
                 f[r] = i0 + r < e ? a.flags[i0 + r] : ig_bit;              // beyond the segment: ignored
                 cnt += ((f[r] & ig_bit) ? 0u : 1u) + ((f[r] & tp_bit) ? 0x10000u : 0u);
             }
@@ -284,23 +172,23 @@ __global__ __launch_bounds__(ES_THREADS) void es_ap_kernel(EsAp a) {
             const unsigned ex = fo_block_excl_scan(cnt, shu, tid, &total);
             rem_ni -= total & 0xFFFFu; rem_tp -= total >> 16;             // now: the counts in front of this chunk
             unsigned rank = rem_ni + (ex & 0xFFFFu), ctp = rem_tp + (ex >> 16);
-            double prec[ES_AP_ITEMS], step[ES_AP_ITEMS];
+            double prec[EV_AP_ITEMS], step[EV_AP_ITEMS];
 #pragma unroll
-            for (int r = 0; r < ES_AP_ITEMS; ++r) {
+            for (int r = 0; r < EV_AP_ITEMS; ++r) {
                 const bool ni = !(f[r] & ig_bit), tp = f[r] & tp_bit;
                 rank += ni ? 1u : 0u; ctp += tp ? 1u : 0u;
                 prec[r] = ni ? (double)ctp / (double)rank : 0.0;
                 step[r] = tp ? (double)ctp / dng - (double)(ctp - 1u) / dng : 0.0;
             }
 #pragma unroll
-            for (int r = ES_AP_ITEMS - 2; r >= 0; --r) prec[r] = fmax(prec[r], prec[r + 1]);      // envelope inside the thread
+            for (int r = EV_AP_ITEMS - 2; r >= 0; --r) prec[r] = fmax(prec[r], prec[r + 1]);      // envelope inside the thread
             double chunk_max;
-            const double later = fmax(es_block_excl_rmax(prec[0], shd, tid, &chunk_max), carry);
+            const double later = fmax(ev_block_excl_rmax(prec[0], shd, tid, &chunk_max), carry);
             double sum = 0.0;
 #pragma unroll
-            for (int r = 0; r < ES_AP_ITEMS; ++r)
+            for (int r = 0; r < EV_AP_ITEMS; ++r)
                 if (f[r] & tp_bit) sum += step[r] * fmax(prec[r], later);
-            acc += es_block_sum<double>(sum, shd, tid);
+            acc += ev_block_sum<double>(sum, shd, tid);
             carry = fmax(carry, chunk_max);
         }
     }
@@ -332,7 +220,7 @@ struct EsOpenWords {
 // thread reads the same LDS word (a broadcast).  A maximum over `>` does not depend on the order of the boxes.
 __global__ __launch_bounds__(ES_THREADS) void es_open_words_kernel(EsOpenWords p) {
     __shared__ float box[ES_OPEN_CHUNK][4];
-    __shared__ unsigned shu[ES_WAVES];
+    __shared__ unsigned shu[EV_WAVES];
     const int b = blockIdx.x, tid = threadIdx.x;
     for (int i0 = 0; i0 < p.max_det; i0 += ES_THREADS) {
         const int i = i0 + tid;
@@ -389,20 +277,20 @@ DEV void es_open_totals(const EsOpenCounts& a, unsigned s, unsigned e, unsigned 
         const unsigned f = a.flags[i];
         c_ni += (f & ig_bit) ? 0u : 1u; c_tp += (f & tp_bit) ? 1u : 0u; c_op += (a.open[i] & tp_bit) ? 1u : 0u;
     }
-    *ni = es_block_sum<unsigned>(c_ni, shu, tid);
-    *tp = es_block_sum<unsigned>(c_tp, shu, tid);
-    *op = es_block_sum<unsigned>(c_op, shu, tid);
+    *ni = ev_block_sum<unsigned>(c_ni, shu, tid);
+    *tp = ev_block_sum<unsigned>(c_tp, shu, tid);
+    *op = ev_block_sum<unsigned>(c_op, shu, tid);
 }
 
 // workgroup (c, t): the counts of class c at threshold t.  Pass 1: the totals, then k_star = the reachable cumulative-TP count
 // whose recall is nearest the level (float64, ties to the smaller count; the candidates floor(level n_gt) - 1 .. + 2 suffice).
 // Pass 2: the first position with that count (the chunks from the front, an integer scan each), and the counts up to it.
 __global__ __launch_bounds__(ES_THREADS) void es_open_counts_kernel(EsOpenCounts a) {
-    __shared__ unsigned shu[ES_WAVES];
+    __shared__ unsigned shu[EV_WAVES];
     __shared__ unsigned sh_pos;
     const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
-    const unsigned n = es_live(a.state, a.n_host, a.capacity);
-    const unsigned s = es_class_begin(a.keys, n, c), e = es_class_begin(a.keys, n, c + 1);
+    const unsigned n = ev_live(a.state, a.n_host, a.capacity);
+    const unsigned s = ev_class_begin(a.keys, n, c), e = ev_class_begin(a.keys, n, c + 1);
     const int ng = a.gt_count[c];
     const unsigned tp_bit = 1u << t, ig_bit = 1u << (16 + t);
     unsigned n_det, tp, open_total;
@@ -425,12 +313,12 @@ __global__ __launch_bounds__(ES_THREADS) void es_open_counts_kernel(EsOpenCounts
             const unsigned want = (unsigned)k_star;
             unsigned seen = 0;
             bool found = false;
-            const unsigned nchunks = (e - s + ES_AP_CHUNK - 1) / ES_AP_CHUNK;
+            const unsigned nchunks = (e - s + EV_AP_CHUNK - 1) / EV_AP_CHUNK;
             for (unsigned q = 0; q < nchunks && !found; ++q) {            // `found` is the same for the whole workgroup
-                const unsigned i0 = s + q * ES_AP_CHUNK + (unsigned)tid * ES_AP_ITEMS;
-                unsigned f[ES_AP_ITEMS], cnt = 0;
+                const unsigned i0 = s + q * EV_AP_CHUNK + (unsigned)tid * EV_AP_ITEMS;
+                unsigned f[EV_AP_ITEMS], cnt = 0;
 #pragma unroll
-                for (int r = 0; r < ES_AP_ITEMS; ++r) {
+                for (int r = 0; r < EV_AP_ITEMS; ++r) {
                     f[r] = i0 + r < e ? a.flags[i0 + r] : 0u;
                     cnt += (f[r] & tp_bit) ? 1u : 0u;
                 }
@@ -438,7 +326,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_open_counts_kernel(EsOpenCounts
                 unsigned run = seen + fo_block_excl_scan(cnt, shu, tid, &total);
                 if (run < want && want <= run + cnt) {                    // one thread of one chunk
 #pragma unroll
-                    for (int r = 0; r < ES_AP_ITEMS; ++r) {
+                    for (int r = 0; r < EV_AP_ITEMS; ++r) {
                         if (f[r] & tp_bit) { ++run; if (run == want) sh_pos = i0 + r; }
                     }
                 }
@@ -481,48 +369,17 @@ __global__ __launch_bounds__(ES_THREADS) void es_relabel_unknown_kernel(EsRelabe
     o[0] = v0; o[1] = v1; o[2] = v2; o[3] = v3; o[4] = v4; o[5] = cls;
 }
 
-// ---- workspace layout (host) -------------------------------------------------------------------------------------------------------
-struct EsLayout { long long keys[2], vals[2], vals2[2], hist, totals, total; unsigned tiles; int passes; };
+// ---- workspace layout (host): the sort's buffers, then the second payload pair when there are open words ---------------------------
+bool es_layout(long long capacity, int C, EvLayout* L, bool open = false) { return ev_layout(capacity, C, open ? 4 : 0, open ? 4 : 0, L); }
 
-int es_append(void* stream, const EsAppend& a) {
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(es_append_write_kernel, dim3(a.B), dim3(ES_THREADS), 0, st, a);
-    hipLaunchKernelGGL(es_append_cursor_kernel, dim3(1), dim3(ES_THREADS), 0, st, a);
-    return effdet_check_launch();
-}
-
-bool es_layout(long long capacity, int C, EsLayout* L, bool open = false) {
-    if (capacity < 1 || capacity > ES_MAX_N || C < 1 || C > ES_MAX_C) return false;
-    long long off = 0;
-    auto take = [&off](long long bytes) { const long long o = off; off += (bytes + 255) & ~255ll; return o; };
-    L->tiles = (unsigned)((capacity + RS_TILE - 1) / RS_TILE);
-    L->passes = C <= 255 ? 5 : 6;                                         // 4 score digits, then the class (C itself is a key)
-    for (int k = 0; k < 2; ++k) { L->keys[k] = take(capacity * 8); L->vals[k] = take(capacity * 4); }
-    for (int k = 0; k < 2; ++k) L->vals2[k] = open ? take(capacity * 4) : 0;
-    L->hist = take(256ll * L->tiles * 4);
-    L->totals = take(256 * 4);
-    L->total = off;
-    return true;
-}
-
-// the passes of the sort: entries -> buffers 0 -> 1 -> 0 ...; the grid by n_host, or by the capacity when the count is on the device
 template <bool W2> void es_sort(hipStream_t st, const float* scores, const int* classes, const unsigned* flags, const unsigned* open,
-                                const unsigned* state, long long n_host, long long capacity, int C, char* ws, const EsLayout& L) {
+                                const unsigned* state, long long n_host, long long capacity, int C, char* ws, const EvLayout& L) {
     EsSort<W2> s;
-    s.scores = scores; s.classes = classes; s.flags = flags; s.open = open;
-    s.cursor = state; s.n_host = n_host;
-    s.hist = reinterpret_cast<unsigned*>(ws + L.hist); s.totals = reinterpret_cast<unsigned*>(ws + L.totals);
-    s.capacity = (unsigned)capacity; s.tiles = L.tiles; s.C = C;
-    const unsigned grid = n_host < 0 ? L.tiles : (unsigned)((n_host + RS_TILE - 1) / RS_TILE);
-    for (int pass = 0; pass < L.passes && grid > 0; ++pass) {
-        const int d = pass & 1;
-        s.shift = 8 * pass; s.first = pass == 0;
-        s.src_k = reinterpret_cast<const u64*>(ws + L.keys[1 - d]); s.src_v = reinterpret_cast<const unsigned*>(ws + L.vals[1 - d]);
-        s.dst_k = reinterpret_cast<u64*>(ws + L.keys[d]); s.dst_v = reinterpret_cast<unsigned*>(ws + L.vals[d]);
-        s.src_w = W2 ? reinterpret_cast<const unsigned*>(ws + L.vals2[1 - d]) : nullptr;
-        s.dst_w = W2 ? reinterpret_cast<unsigned*>(ws + L.vals2[d]) : nullptr;
-        rs_sort_pass(st, s, grid, 1);
-    }
+    s.flags = flags; s.open = open; s.src_w = nullptr; s.dst_w = nullptr;
+    ev_sort(st, s, scores, classes, state, n_host, capacity, C, ws, L, [ws, &L](EsSort<W2>& p, int d) {
+        if (!W2) return;
+        p.src_w = reinterpret_cast<const unsigned*>(ws + L.extra[1 - d]); p.dst_w = reinterpret_cast<unsigned*>(ws + L.extra[d]);
+    });
 }
 
 }  // namespace
@@ -537,12 +394,9 @@ extern "C" int effdet_eval_match_multi(void* stream, const float* det, const int
     EFFDET_ENTER();
     if (!det || !det_count || !gt_boxes || !gt_cls || !thresholds || !flags || !gt_count || !gt_imgs || !correct_imgs)
         return EFFDET_EINVAL;      // null pointer
-    if (num_thresholds < 1 || num_thresholds > ES_MAX_T) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 16
-    for (int t = 0; t < num_thresholds; ++t)
-        if (!(thresholds[t] == thresholds[t]) || (t > 0 && !(thresholds[t] > thresholds[t - 1])))
-            return EFFDET_EINVAL;      // thresholds must ascend
-    if (B <= 0 || max_det <= 0 || M <= 0 || (long long)B * max_det > ES_MAX_N) return EFFDET_EINVAL;      // bad B, max_det or M
-    if (num_classes < 1 || num_classes > ES_MAX_C) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
+    if (!em_thresholds_ok(thresholds, num_thresholds, ES_MAX_T)) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 16, ascending, no NaN
+    if (!em_slots_ok(B, max_det) || M <= 0) return EFFDET_EINVAL;      // bad B, max_det or M
+    if (!em_classes_ok(num_classes)) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
     const size_t sh = ((size_t)num_classes + 3 * (size_t)M + 8) * sizeof(int);
     if (sh > 64 * 1024) return EFFDET_EINVAL;      // (num_classes + 3 M + 8) ints exceed 64 KiB of LDS
     EsMatch a;
@@ -558,10 +412,10 @@ extern "C" int effdet_eval_append(void* stream, const float* det, const unsigned
                                   float* scores, int* classes, unsigned int* out_flags, long long capacity, unsigned int* state) {
     EFFDET_ENTER();
     if (!det || !flags || !kept || !scores || !classes || !out_flags || !state) return EFFDET_EINVAL;      // null pointer
-    if (B <= 0 || max_det <= 0 || (long long)B * max_det > ES_MAX_N) return EFFDET_EINVAL;      // bad B or max_det
-    if (capacity < 1 || capacity > ES_MAX_N) return EFFDET_EINVAL;      // 1 <= capacity <= 2^24
-    EsAppend a{det, flags, kept, B, max_det, scores, classes, out_flags, (unsigned)capacity, state, nullptr, nullptr};
-    return es_append(stream, a);
+    if (!em_slots_ok(B, max_det)) return EFFDET_EINVAL;      // bad B or max_det
+    if (!ev_capacity_ok(capacity)) return EFFDET_EINVAL;      // 1 <= capacity <= 2^24
+    const EsAppend a{{det, kept, B, max_det, scores, classes, (unsigned)capacity, state}, flags, out_flags, nullptr, nullptr};
+    return ev_append(stream, a);
 }
 
 extern "C" int effdet_eval_append_open(void* stream, const float* det, const unsigned int* flags, const unsigned int* open,
@@ -570,26 +424,25 @@ extern "C" int effdet_eval_append_open(void* stream, const float* det, const uns
     EFFDET_ENTER();
     if (!det || !flags || !open || !kept || !scores || !classes || !out_flags || !out_open || !state)
         return EFFDET_EINVAL;      // null pointer
-    if (B <= 0 || max_det <= 0 || (long long)B * max_det > ES_MAX_N) return EFFDET_EINVAL;      // bad B or max_det
-    if (capacity < 1 || capacity > ES_MAX_N) return EFFDET_EINVAL;      // 1 <= capacity <= 2^24
-    EsAppend a{det, flags, kept, B, max_det, scores, classes, out_flags, (unsigned)capacity, state, open, out_open};
-    return es_append(stream, a);
+    if (!em_slots_ok(B, max_det)) return EFFDET_EINVAL;      // bad B or max_det
+    if (!ev_capacity_ok(capacity)) return EFFDET_EINVAL;      // 1 <= capacity <= 2^24
+    const EsAppend a{{det, kept, B, max_det, scores, classes, (unsigned)capacity, state}, flags, out_flags, open, out_open};
+    return ev_append(stream, a);
 }
 
 extern "C" long long effdet_eval_ap_sorted_workspace_bytes(long long capacity, int num_classes) {
-    EsLayout L;
+    EvLayout L;
     return es_layout(capacity, num_classes, &L) ? L.total : (long long)EFFDET_EINVAL;
 }
 
 extern "C" long long effdet_eval_ap_sorted_offset(long long capacity, int num_classes, int which) {
-    EsLayout L;
+    EvLayout L;
     if ((which != 0 && which != 1) || !es_layout(capacity, num_classes, &L)) return EFFDET_EINVAL;
-    const int last = (L.passes - 1) & 1;
-    return which == 0 ? L.keys[last] : L.vals[last];
+    return which == 0 ? L.keys[ev_last(L)] : L.vals[ev_last(L)];
 }
 
 extern "C" long long effdet_eval_ap_sorted_result_bytes(int num_thresholds, int num_classes) {
-    if (num_thresholds < 1 || num_thresholds > ES_MAX_T || num_classes < 1 || num_classes > ES_MAX_C) return EFFDET_EINVAL;
+    if (num_thresholds < 1 || num_thresholds > ES_MAX_T || !em_classes_ok(num_classes)) return EFFDET_EINVAL;
     return 8ll * (ES_RESULT_HEAD + 2ll * num_thresholds * num_classes + 2ll * num_classes);
 }
 
@@ -602,8 +455,8 @@ static int es_sorted_run(void* stream, const float* scores, const int* classes, 
         return EFFDET_EINVAL;      // null pointer
     if (n < 0 && !state) return EFFDET_EINVAL;      // n < 0 takes the count from `state`, which is null
     if (num_thresholds < 1 || num_thresholds > ES_MAX_T) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 16
-    if (num_classes < 1 || num_classes > ES_MAX_C) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
-    EsLayout L;
+    if (!em_classes_ok(num_classes)) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
+    EvLayout L;
     if (!es_layout(capacity, num_classes, &L, open != nullptr)) return EFFDET_EINVAL;      // 1 <= capacity <= 2^24
     if (n > capacity) return EFFDET_EINVAL;      // n exceeds the capacity
     if (workspace_bytes < L.total) return EFFDET_EINVAL;      // workspace too small
@@ -614,7 +467,7 @@ static int es_sorted_run(void* stream, const float* scores, const int* classes, 
     const long long n_host = n < 0 ? -1 : n;
     if (open) es_sort<true>(st, scores, classes, flags, open, state, n_host, capacity, num_classes, ws, L);
     else es_sort<false>(st, scores, classes, flags, nullptr, state, n_host, capacity, num_classes, ws, L);
-    const int last = (L.passes - 1) & 1;
+    const int last = ev_last(L);
     EsAp a;
     a.keys = reinterpret_cast<const u64*>(ws + L.keys[last]); a.flags = reinterpret_cast<const unsigned*>(ws + L.vals[last]);
     a.state = state; a.n_host = n_host; a.capacity = (unsigned)capacity;
@@ -624,7 +477,7 @@ static int es_sorted_run(void* stream, const float* scores, const int* classes, 
     hipLaunchKernelGGL(es_ap_kernel, dim3((unsigned)num_classes, (unsigned)num_thresholds), dim3(ES_THREADS), 0, st, a);
     if (open) {
         EsOpenCounts o;
-        o.keys = a.keys; o.flags = a.flags; o.open = reinterpret_cast<const unsigned*>(ws + L.vals2[last]);
+        o.keys = a.keys; o.flags = a.flags; o.open = reinterpret_cast<const unsigned*>(ws + L.extra[last]);
         o.state = state; o.n_host = n_host; o.capacity = (unsigned)capacity;
         o.T = num_thresholds; o.C = num_classes; o.level = level;
         o.gt_count = gt_count;
@@ -649,12 +502,9 @@ extern "C" int effdet_eval_open_words(void* stream, const float* det, const unsi
                                       int num_thresholds, unsigned int* open) {
     EFFDET_ENTER();
     if (!det || !flags || !gt_boxes || !gt_cls || !thresholds || !open) return EFFDET_EINVAL;      // null pointer
-    if (num_thresholds < 1 || num_thresholds > ES_MAX_T) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 16
-    for (int t = 0; t < num_thresholds; ++t)
-        if (!(thresholds[t] == thresholds[t]) || (t > 0 && !(thresholds[t] > thresholds[t - 1])))
-            return EFFDET_EINVAL;      // thresholds must ascend
-    if (B <= 0 || max_det <= 0 || M <= 0 || (long long)B * max_det > ES_MAX_N) return EFFDET_EINVAL;      // bad B, max_det or M
-    if (num_classes < 2 || num_classes > ES_MAX_C) return EFFDET_EINVAL;      // 2 <= num_classes <= 65535
+    if (!em_thresholds_ok(thresholds, num_thresholds, ES_MAX_T)) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 16, ascending, no NaN
+    if (!em_slots_ok(B, max_det) || M <= 0) return EFFDET_EINVAL;      // bad B, max_det or M
+    if (!em_classes_ok(num_classes, 2)) return EFFDET_EINVAL;      // 2 <= num_classes <= 65535
     EsOpenWords a;
     a.det = det; a.flags = flags; a.gt_boxes = gt_boxes; a.gt_cls = gt_cls;
     a.B = B; a.max_det = max_det; a.M = M; a.U = num_classes; a.T = num_thresholds;
@@ -665,19 +515,18 @@ extern "C" int effdet_eval_open_words(void* stream, const float* det, const unsi
 }
 
 extern "C" long long effdet_eval_open_sorted_workspace_bytes(long long capacity, int num_classes) {
-    EsLayout L;
+    EvLayout L;
     return es_layout(capacity, num_classes, &L, true) ? L.total : (long long)EFFDET_EINVAL;
 }
 
 extern "C" long long effdet_eval_open_sorted_offset(long long capacity, int num_classes, int which) {
-    EsLayout L;
+    EvLayout L;
     if (which < 0 || which > 2 || !es_layout(capacity, num_classes, &L, true)) return EFFDET_EINVAL;
-    const int last = (L.passes - 1) & 1;
-    return which == 0 ? L.keys[last] : which == 1 ? L.vals[last] : L.vals2[last];
+    return which == 0 ? L.keys[ev_last(L)] : which == 1 ? L.vals[ev_last(L)] : L.extra[ev_last(L)];
 }
 
 extern "C" long long effdet_eval_open_sorted_result_bytes(int num_thresholds, int num_classes) {
-    if (num_thresholds < 1 || num_thresholds > ES_MAX_T || num_classes < 2 || num_classes > ES_MAX_C) return EFFDET_EINVAL;
+    if (num_thresholds < 1 || num_thresholds > ES_MAX_T || !em_classes_ok(num_classes, 2)) return EFFDET_EINVAL;
     return 8ll * (ES_RESULT_HEAD + (2ll + ES_OPEN_MATS) * num_thresholds * num_classes + 2ll * num_classes);
 }
 
@@ -699,8 +548,8 @@ extern "C" int effdet_relabel_unknown(void* stream, const float* det_in, const i
                                       float* det_out) {
     EFFDET_ENTER();
     if (!det_in || !count || !score || !det_out) return EFFDET_EINVAL;      // null pointer
-    if (B <= 0 || max_det <= 0 || (long long)B * max_det > ES_MAX_N) return EFFDET_EINVAL;      // bad B or max_det
-    if (num_known < 1 || num_known >= ES_MAX_C) return EFFDET_EINVAL;      // 1 <= num_known <= 65534
+    if (!em_slots_ok(B, max_det)) return EFFDET_EINVAL;      // bad B or max_det
+    if (num_known < 1 || num_known >= EM_MAX_C) return EFFDET_EINVAL;      // 1 <= num_known <= 65534
     if (pitch < 0 || stride < 0) return EFFDET_EINVAL;      // negative pitch or stride
     EsRelabel a{det_in, count, score, pitch, stride, B, max_det, num_known, tau, tau_device, det_out};
     const unsigned grid = (unsigned)(((long long)B * max_det + ES_THREADS - 1) / ES_THREADS);

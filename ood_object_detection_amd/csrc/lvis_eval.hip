@@ -45,19 +45,17 @@ typedef unsigned long long u64;
 
 constexpr int LV_THREADS = 256;
 static_assert(LV_THREADS == FO_THREADS && LV_THREADS == EM_THREADS, "the shared headers are written for this workgroup size");
-constexpr long long LV_MAX_N = 1ll << 24;
-constexpr int LV_MAX_T = 15, LV_MAX_A = 4, LV_MAX_C = 65535, LV_MAX_DET = 2048;
-constexpr unsigned LV_DROPPED = 0x80000000u;
+constexpr int LV_MAX_DET = 2048;
 
 struct LvMatch {
     const float* det; const int* det_count; const float* gt_boxes; const long long* gt_cls; const float* gt_area;
     const long long* neg_cls; const long long* nel_cls;
-    int B, max_det, M, C, T, A, max_rank, Kn, Ke; float min_score; float thr[LV_MAX_T]; float lo[LV_MAX_A], hi[LV_MAX_A];
+    int B, max_det, M, C, T, A, max_rank, Kn, Ke; float min_score; float thr[EM_MAX_T]; float lo[EM_MAX_A], hi[EM_MAX_A];
     unsigned* flags; int* rank; int* kept; int* npig;
 };
 
 long long lv_match_lds(int max_det, int M, int C) {
-    if (max_det < 1 || max_det > LV_MAX_DET || M < 1 || C < 1 || C > LV_MAX_C) return EFFDET_EINVAL;
+    if (max_det < 1 || max_det > LV_MAX_DET || M < 1 || !em_classes_ok(C)) return EFFDET_EINVAL;
     return 40ll * M + 12ll * ((C + 31) / 32) + 8ll * max_det + 16;
 }
 
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_match_kernel(LvMatch p) {
         const float area = p.gt_area ? p.gt_area[at] : (g2 - g0) * (g3 - g1);
         int meta = 0;
 #pragma unroll
-        for (int a = 0; a < LV_MAX_A; ++a) {
+        for (int a = 0; a < EM_MAX_A; ++a) {
             if (a >= p.A) continue;
             const bool ig = area < p.lo[a] || area > p.hi[a];
             meta |= (ig ? 1 : 0) << a;
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_match_kernel(LvMatch p) {
             p.rank[slot] = r;
             ++kept;
         } else {
-            for (int a = 0; a < p.A; ++a) p.flags[slot * p.A + a] = LV_DROPPED;
+            for (int a = 0; a < p.A; ++a) p.flags[slot * p.A + a] = EM_DROPPED;
             p.rank[slot] = -1;
         }
     }
@@ -159,9 +157,9 @@ __global__ __launch_bounds__(LV_THREADS) void lv_match_kernel(LvMatch p) {
     const int my_t = pair / p.A, my_a = pair % p.A;
     float my_thr = 0.f, my_lo = 0.f, my_hi = 0.f;
 #pragma unroll
-    for (int t = 0; t < LV_MAX_T; ++t) if (t == my_t) my_thr = p.thr[t];
+    for (int t = 0; t < EM_MAX_T; ++t) if (t == my_t) my_thr = p.thr[t];
 #pragma unroll
-    for (int a = 0; a < LV_MAX_A; ++a) if (a == my_a) { my_lo = p.lo[a]; my_hi = p.hi[a]; }
+    for (int a = 0; a < EM_MAX_A; ++a) if (a == my_a) { my_lo = p.lo[a]; my_hi = p.hi[a]; }
     const int walk = min(p.max_det, p.max_rank);
     for (int r = 0; r < walk; ++r) {
         const int i = inv[r];
@@ -217,16 +215,11 @@ extern "C" int effdet_lvis_match(void* stream, const float* det, const int* det_
     EFFDET_ENTER();
     if (!det || !det_count || !gt_boxes || !gt_cls || !thresholds || !area_ranges || !flags || !rank || !npig)
         return EFFDET_EINVAL;      // null pointer
-    if (num_thresholds < 1 || num_thresholds > LV_MAX_T) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 15
-    for (int t = 0; t < num_thresholds; ++t)
-        if (!(thresholds[t] == thresholds[t]) || (t > 0 && !(thresholds[t] > thresholds[t - 1])))
-            return EFFDET_EINVAL;      // thresholds must ascend
-    if (num_areas < 1 || num_areas > LV_MAX_A) return EFFDET_EINVAL;      // 1 <= num_areas <= 4
-    for (int a = 0; a < num_areas; ++a)
-        if (!(area_ranges[2 * a] <= area_ranges[2 * a + 1])) return EFFDET_EINVAL;      // an area range needs lo <= hi
-    if (B <= 0 || max_det <= 0 || M <= 0 || (long long)B * max_det > LV_MAX_N) return EFFDET_EINVAL;      // bad B, max_det or M
+    if (!em_thresholds_ok(thresholds, num_thresholds, EM_MAX_T)) return EFFDET_EINVAL;      // 1 <= num_thresholds <= 15, ascending, no NaN
+    if (!em_areas_ok(area_ranges, num_areas)) return EFFDET_EINVAL;      // 1 <= num_areas <= 4, an area range needs lo <= hi
+    if (!em_slots_ok(B, max_det) || M <= 0) return EFFDET_EINVAL;      // bad B, max_det or M
     if (max_det > LV_MAX_DET) return EFFDET_EINVAL;      // max_det exceeds 2048
-    if (num_classes < 1 || num_classes > LV_MAX_C) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
+    if (!em_classes_ok(num_classes)) return EFFDET_EINVAL;      // 1 <= num_classes <= 65535
     if (max_rank < 1) return EFFDET_EINVAL;      // max_rank (the largest max_dets) must be positive
     if (min_score != min_score) return EFFDET_EINVAL;      // min_score is NaN
     if ((neg_cls && Kn < 0) || (nel_cls && Ke < 0)) return EFFDET_EINVAL;      // a category list of negative length
@@ -237,8 +230,8 @@ extern "C" int effdet_lvis_match(void* stream, const float* det, const int* det_
     a.neg_cls = neg_cls; a.nel_cls = nel_cls; a.Kn = neg_cls ? Kn : 0; a.Ke = nel_cls ? Ke : 0;
     a.B = B; a.max_det = max_det; a.M = M; a.C = num_classes; a.T = num_thresholds; a.A = num_areas; a.max_rank = max_rank;
     a.min_score = min_score;
-    for (int t = 0; t < LV_MAX_T; ++t) a.thr[t] = t < num_thresholds ? thresholds[t] : 0.f;
-    for (int k = 0; k < LV_MAX_A; ++k) { a.lo[k] = k < num_areas ? area_ranges[2 * k] : 0.f; a.hi[k] = k < num_areas ? area_ranges[2 * k + 1] : 0.f; }
+    for (int t = 0; t < EM_MAX_T; ++t) a.thr[t] = t < num_thresholds ? thresholds[t] : 0.f;
+    for (int k = 0; k < EM_MAX_A; ++k) { a.lo[k] = k < num_areas ? area_ranges[2 * k] : 0.f; a.hi[k] = k < num_areas ? area_ranges[2 * k + 1] : 0.f; }
     a.flags = flags; a.rank = rank; a.kept = kept; a.npig = npig;
     hipLaunchKernelGGL(lv_match_kernel, dim3(B), dim3(LV_THREADS), (size_t)sh, reinterpret_cast<hipStream_t>(stream), a);
     return effdet_check_launch();

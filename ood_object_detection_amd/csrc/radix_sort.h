@@ -1,4 +1,5 @@
-// One pass of the stable LSD radix sort of the evaluation units (ood_eval.hip, eval_scale.hip), 8 bits a pass:
+// One pass of the stable LSD radix sort of ood_eval.hip, outlier_synth.hip and, through eval_sorted.h, eval_scale.hip and
+// coco_eval.hip, 8 bits a pass:
 //   rs_hist_kernel     workgroup (tile, y): the digit counts of one tile of RS_TILE keys, in LDS by integer atomics -> hist[d][tile]
 //   rs_scan_kernel     workgroup (d, y): the exclusive prefix of digit d's counts over the live tiles, in place, and the digit's total
 //   rs_scatter_kernel  workgroup (tile, y): every entry of the tile to (digits below in the array) + (this digit in earlier tiles) +

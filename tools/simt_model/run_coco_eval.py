@@ -41,7 +41,7 @@ NAMES = ('effdet_coco_match', 'effdet_coco_append', 'effdet_coco_sorted_workspac
 
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for header in ('compact.h', 'radix_sort.h', 'eval_match.h'):                                  # included by the unit
+    for header in ('compact.h', 'radix_sort.h', 'eval_match.h', 'eval_sorted.h'):                            # included by the unit
         shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
     src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'coco_eval.hip')).read()
     assert src.count(DYNAMIC_LDS) == 1

@@ -43,7 +43,7 @@ NAMES = ('effdet_eval_match_multi', 'effdet_eval_open_words', 'effdet_eval_appen
 
 def build(tmp):
     shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for header in ('compact.h', 'radix_sort.h', 'eval_match.h'):                                  # included by the unit
+    for header in ('compact.h', 'radix_sort.h', 'eval_match.h', 'eval_sorted.h'):                            # included by the unit
         shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
     src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'eval_scale.hip')).read()
     assert src.count(DYNAMIC_LDS) == 1
