@@ -853,6 +853,57 @@ int effdet_lvis_match(void* stream, const float* det, const int* det_count, cons
                       const float* area_ranges, int num_areas, int max_rank, float min_score, const long long* neg_cls, int Kn,
                       const long long* nel_cls, int Ke, unsigned int* flags, int* rank, int* kept, int* npig);
 
+/* ---- OpenImages detection evaluation (csrc/openimages_eval.hip): group-of boxes, weighted AP, verified labels, pooled mAP ---------- */
+
+/* pure host query: the LDS bytes of one effdet_openimages_match workgroup,
+ * 4 (num_classes + ceil(num_classes / 32) + (3 + num_thresholds) M + 24); -22 for M < 1, num_classes outside 1..65535 or
+ * num_thresholds outside 1..15.  The launch needs it <= 64 KiB. */
+long long effdet_openimages_match_lds_bytes(int M, int num_classes, int num_thresholds);
+/* The matching of effdet_eval_match_multi with group-of boxes, for 1..15 ASCENDING thresholds (HOST array).  gt_group_of [B,M]
+ * (NULL: none) marks group-of boxes, gt_difficult [B,M] (NULL: none) difficult ones; labeled_cls [B,K] int64 1-based verified
+ * image-level labels (<= 0 or > num_classes: padding; NULL: every class is evaluatable in every image; K may be 0): with a list, a
+ * detection whose class is neither the class of a box of its image nor in the list is dropped (bit 31).  Stage 1: the candidate is
+ * the box of the class that is NOT group-of with the largest IoU (first on ties); IoU >= thr and difficult: ignored; IoU >= thr and
+ * not taken: true positive.  Stage 2: a detection that is neither at thr takes the group-of box of its class with the largest
+ * intersection over the detection's own area (first on ties); IoA >= thr: absorbed (bit 16 + t) and the box remembers the largest
+ * absorbed score.  flags [B,max_det]: bit t true positive, bit 16 + t ignored or absorbed, bit 31 dropped.  vscore / vflags
+ * [B,M,num_thresholds]: slot (j, t) is the virtual entry of group-of box j at threshold t when emit_virtual != 0 and the
+ * remembered score is > 0 - vscore = that score, vflags = bit t | the ignore bits of every other threshold | bit 15 - else
+ * vscore = 0 and vflags = bit 31.  kept [2 B]: kept detection slots + virtual entries of image b, then its NaN scores.  Integer
+ * atomics add to n_plain [C] (boxes neither difficult nor group-of), n_group [C] (group-of, not difficult), gt_imgs [C] and
+ * correct_imgs [T][C] (the top-scoring detection of the class reaches thr by IoU with ANY box of the class).  A box that is both
+ * difficult and group-of absorbs like a group-of box and is counted in neither.  B * max_det and B * M * num_thresholds <= 2^24. */
+int effdet_openimages_match(void* stream, const float* det, const int* det_count, const float* gt_boxes, const long long* gt_cls,
+                            const unsigned char* gt_difficult, const unsigned char* gt_group_of, const long long* labeled_cls, int K,
+                            int B, int max_det, int M, int num_classes, const float* thresholds, int num_thresholds, int emit_virtual,
+                            unsigned int* flags, float* vscore, unsigned int* vflags, int* kept, int* n_plain, int* n_group,
+                            int* gt_imgs, int* correct_imgs);
+/* effdet_eval_append for that match: per image its kept detection slots in slot order, then its virtual entries in (box,
+ * threshold) order (class = the box's), at the device cursor state[0]; state as effdet_eval_append.  Virtual entries count
+ * against the capacity. */
+int effdet_openimages_append(void* stream, const float* det, const unsigned int* flags, const long long* gt_cls, const float* vscore,
+                             const unsigned int* vflags, const int* kept, int B, int max_det, int M, int num_thresholds, float* scores,
+                             int* classes, unsigned int* out_flags, long long capacity, unsigned int* state);
+/* workspace bytes of effdet_openimages_sorted (pooled != 0: with the buffers of the second sort); -22 for a bad argument */
+long long effdet_openimages_sorted_workspace_bytes(long long capacity, int num_classes, int pooled);
+/* byte offset in the workspace of the sorted keys (which = 0) and flag words (1) of the class sort, and of the keys (2) and flag
+ * words (3) of the pooled sort; keys are (class << 32) | order-preserving score key, the pooled class being 0 (takes part) or 1 */
+long long effdet_openimages_sorted_offset(long long capacity, int num_classes, int which);
+/* bytes of the result block: 8-byte words {n, lost, NaN scores, T, C, pooled, 0, 0}, AP [T][C] float64, pooled AP [T] float64,
+ * then int64 n_plain [C], n_group [C], gt_imgs [C], correct [T][C] */
+long long effdet_openimages_sorted_result_bytes(int num_thresholds, int num_classes);
+/* The stable radix sort by (class, score descending) and the weighted VOC all-points AP per (threshold, class) over the first n
+ * entries (n < 0: min(state[0], capacity), read on the device): num_gt = n_plain + w n_group (w = group_of_weight, finite, >= 0);
+ * over the entries not ignored at thr, with a plain and g group true positives (bit 15) at or before an entry, ctp = a + w g,
+ * precision = ctp / (ctp + (rank - a - g)), AP = the sum over the true positives of (ctp / num_gt - ctp_before / num_gt) * the
+ * envelope of precision; NaN where num_gt = 0.  pooled != 0: the sorted entries are sorted once more by score alone, entries of
+ * classes without instances behind the rest, equal scores in (class, arrival) order, and the same AP runs over that one segment
+ * with num_gt = the sum over the classes with instances; else the pooled AP is NaN.  Capturable; bit-identical from run to run. */
+int effdet_openimages_sorted(void* stream, const float* scores, const int* classes, const unsigned int* flags, long long capacity,
+                             long long n, const unsigned int* state, int num_thresholds, int num_classes, double group_of_weight,
+                             int pooled, const int* n_plain, const int* n_group, const int* gt_imgs, const int* correct_imgs,
+                             void* workspace, long long workspace_bytes, void* result);
+
 /* ---- OOD evaluation helpers -------------------------------------------- */
 
 /* The fork's novelty score (infer.py:425-427, 465-471, 607-616), reported beside energy / max-logit:

@@ -204,6 +204,17 @@ SIGNATURES = {
     'effdet_lvis_match': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                   c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    'effdet_openimages_match_lds_bytes': (c_ll, [c_int, c_int, c_int]),
+    'effdet_openimages_match': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                        c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    'effdet_openimages_append': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                         c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'effdet_openimages_sorted_workspace_bytes': (c_ll, [c_ll, c_int, c_int]),
+    'effdet_openimages_sorted_offset': (c_ll, [c_ll, c_int, c_int]),
+    'effdet_openimages_sorted_result_bytes': (c_ll, [c_int, c_int]),
+    'effdet_openimages_sorted': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_double, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
     'effdet_train_fold_bn': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_train_convbn_grads': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

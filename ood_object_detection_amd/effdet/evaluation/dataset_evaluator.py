@@ -7,8 +7,10 @@ per image, all thresholds), then the valid rows go to capacity-sized device buff
 `enqueue()` sorts (class, score descending, equal scores in arrival order) and computes AP per (threshold, class); `result()`
 is the one device-to-host copy.  Nothing before `result()` synchronises with the host, so `add_batch` and `enqueue` can be
 captured in a `torch.cuda.graph`; the same images give the same bits however they are split into `add_batch` calls.  No CPU
-fallback.  Not built (they raise): group-of boxes, masks, weighted mAP, full precision / recall curves, recall bounds.  The
-precision at ONE recall level, per-class recall / precision and the open-set metrics are in open_set_evaluator.py.
+fallback.  Group-of boxes, their weight, verified image-level labels and the weighted (pooled) mAP are the subclasses of
+openimages_evaluator.py (csrc/openimages_eval.hip); this class still raises for `group_of`.  Not built (they raise): masks, full
+precision / recall curves, recall bounds.  The precision at ONE recall level, per-class recall / precision and the open-set
+metrics are in open_set_evaluator.py.
 """
 import ctypes
 

@@ -2,8 +2,8 @@
 object_detection_evaluation.py, per_image_evaluation.py, metrics.py - ~3000 lines of per-image numpy in the fork, run
 inside its training loop, pretrain.py:246-252).
 
-Same surface as the reference class for the inputs that loop produces (boxes, scores, 1-based classes; no difficult /
-group-of flags, no masks - those raise): `add_single_ground_truth_image_info`, `add_single_detected_image_info`,
+Same surface as the reference class for the inputs that loop produces (boxes, scores, 1-based classes; group-of flags and
+masks raise here - group-of boxes and the weighted mAP are openimages_evaluator.py's): `add_single_ground_truth_image_info`, `add_single_detected_image_info`,
 `evaluate(task_categories, batch_cats=None)` with the reference's metric names, `clear()`.  `add_batch` is the native
 entry: the `[B, max_det, 6]` detections + counts of `DetBenchPredict` / `batched_detections` and padded ground truth go
 to ONE launch (`effdet_eval_match`, a workgroup per image); `evaluate` runs `effdet_eval_ap` over everything
@@ -28,22 +28,32 @@ def create_category_index(categories):
 
 class SingleImageAPI(object):
     """The reference's per-image calls on top of `add_batch(det, count, gt_boxes, gt_cls, gt_difficult)`; the host class keeps
-    `_pending_gt`, `_seen_det`, `_image_ids` and says whether it takes `difficult` ground truth."""
+    `_pending_gt`, `_seen_det`, `_image_ids` and says whether it takes `difficult` and `group_of` ground truth.  A class that
+    takes more than `difficult` overrides `_gt_flags` (what it keeps of a ground-truth dict) and `_add_image` (what it does with it)."""
+
+    def _accepts_group_of(self):
+        return False
+
+    def _gt_flags(self, gt_dict, n):
+        """what is kept beside the n boxes and classes of a ground-truth dict until the image's detections arrive"""
+        difficult = None
+        if 'difficult' in gt_dict:
+            difficult = torch.as_tensor(np.asarray(gt_dict['difficult']).astype(bool)).reshape(-1)
+            if difficult.numel() != n:
+                raise ValueError('difficult: one flag per ground-truth box')
+        return difficult
 
     def add_single_ground_truth_image_info(self, image_id, gt_dict):
         if image_id in self._image_ids:
             return
         for k in gt_dict:
-            if k in ('group_of', 'instance_masks', 'groundtruth_difficult', 'groundtruth_group_of') \
+            if (k == 'group_of' and not self._accepts_group_of()) \
+                    or k in ('instance_masks', 'groundtruth_difficult', 'groundtruth_group_of') \
                     or (k == 'difficult' and not self._accepts_difficult()):
                 raise NotImplementedError('difficult / group-of / mask ground truth is not built')
         boxes = torch.as_tensor(np.asarray(gt_dict['bbox']), dtype=torch.float32).reshape(-1, 4)
-        difficult = None
-        if 'difficult' in gt_dict:
-            difficult = torch.as_tensor(np.asarray(gt_dict['difficult']).astype(bool)).reshape(-1)
-            if difficult.numel() != boxes.shape[0]:
-                raise ValueError('difficult: one flag per ground-truth box')
-        self._pending_gt[image_id] = (boxes, torch.as_tensor(np.asarray(gt_dict['cls']), dtype=torch.int64).reshape(-1), difficult)
+        self._pending_gt[image_id] = (boxes, torch.as_tensor(np.asarray(gt_dict['cls']), dtype=torch.int64).reshape(-1),
+                                      self._gt_flags(gt_dict, boxes.shape[0]))
         self._image_ids.add(image_id)
 
     def add_single_detected_image_info(self, image_id, detections_dict):

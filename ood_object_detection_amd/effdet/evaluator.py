@@ -1,8 +1,8 @@
 """`effdet.evaluator` (reference: effdet/evaluator.py): the validation metric behind `create_evaluator(name, dataset)`.
 
 `CocoEvaluator` is COCO `bbox` mAP@[.5:.95] - what the reference gets from pycocotools' COCOeval through a json file - computed
-on the device by `CocoDetectionEvaluator` (csrc/coco_eval.hip).  `PascalEvaluator` / `OpenImagesEvaluator` run on the device
-evaluators of effdet/evaluation.  The ground truth of the whole dataset is uploaded once, as padded tables indexed by image index;
+on the device by `CocoDetectionEvaluator` (csrc/coco_eval.hip).  `PascalEvaluator` / `OpenImagesEvaluator` / `OpenImagesChallengeEvaluator`
+run on the device evaluators of effdet/evaluation (group-of boxes: csrc/openimages_eval.hip).  The ground truth of the whole dataset is uploaded once, as padded tables indexed by image index;
 `add_predictions(detections, target)` gathers the batch's rows with `target['img_idx']` on the device, so a validation loop reads
 nothing back before `evaluate()`.  Ground truth comes from `dataset.parser` as plain data (no pycocotools import):
 `parser.img_ids`, `parser.coco.imgToAnns[img_id]` (dicts with `bbox` xywh, `category_id`, `iscrowd`, `area`), `parser.cat_ids`
@@ -20,12 +20,14 @@ import torch
 import torch.distributed as dist
 
 from .distributed import all_gather_container
-from .evaluation import CocoDetectionEvaluator, LvisDetectionEvaluator, ObjectDetectionEvaluator, PascalDetectionEvaluator
+from .evaluation import (CocoDetectionEvaluator, LvisDetectionEvaluator, ObjectDetectionEvaluator, OpenImagesDetectionEvaluator,
+                         PascalDetectionEvaluator)
+from .evaluation import OpenImagesChallengeEvaluator as OpenImagesChallengeDetectionEvaluator
 
 _logger = logging.getLogger(__name__)
 
-__all__ = ['CocoEvaluator', 'LvisEvaluator', 'PascalEvaluator', 'OpenImagesEvaluator', 'create_evaluator', 'coco_ground_truth',
-           'lvis_ground_truth']
+__all__ = ['CocoEvaluator', 'LvisEvaluator', 'PascalEvaluator', 'OpenImagesEvaluator', 'OpenImagesChallengeEvaluator', 'create_evaluator',
+           'coco_ground_truth', 'lvis_ground_truth']
 
 
 def coco_ground_truth(anns, cat_id_to_label=None, cat_ids=None, M=None):
@@ -344,17 +346,73 @@ class PascalEvaluator(TfmEvaluator):
 
 
 class OpenImagesEvaluator(TfmEvaluator):
-    """OpenImages V2 without group-of boxes: the same matching and AP as the PASCAL protocol (group-of ground truth raises)."""
+    """OpenImages V2 on `OpenImagesDetectionEvaluator` (csrc/openimages_eval.hip): `parser.get_ann_info(i)` may carry `group_of` [n]
+    bool beside bbox and cls; the flags are uploaded as a third table.  Without a group-of box the figures are the PASCAL
+    protocol's.  `group_of_weight`, `iou_thresholds`, `capacity` and `evaluate_corlocs` go to the device evaluator; `difficult`
+    ground truth still raises (the reference's OpenImages evaluators drop it)."""
+
+    def __init__(self, dataset, distributed=False, pred_yxyx=False, evaluator_cls=OpenImagesDetectionEvaluator, **kw):
+        kw.setdefault('metric_prefix', 'OpenImagesV2')
+        super().__init__(dataset, distributed=distributed, pred_yxyx=pred_yxyx, evaluator_cls=evaluator_cls, **kw)
+
+    def _annotations(self):
+        parser = self._dataset
+        gts = [parser.get_ann_info(i) for i in range(len(parser.img_ids))]
+        for gt in gts:
+            if 'difficult' in gt and np.asarray(gt['difficult']).any():
+                raise NotImplementedError('difficult ground truth is not built for this evaluator')
+        return gts
+
+    def _ground_truth_tables(self):
+        gts = self._annotations()
+        M = max([len(np.asarray(gt['cls']).reshape(-1)) for gt in gts] + [1])
+        boxes, cls = torch.zeros(len(gts), M, 4), torch.full((len(gts), M), -1, dtype=torch.int64)
+        group_of = torch.zeros(len(gts), M, dtype=torch.uint8)
+        for i, gt in enumerate(gts):
+            c = torch.as_tensor(np.asarray(gt['cls']), dtype=torch.int64).reshape(-1)
+            boxes[i, :c.numel()] = torch.as_tensor(np.asarray(gt['bbox']), dtype=torch.float32).reshape(-1, 4)
+            cls[i, :c.numel()] = c
+            if 'group_of' in gt and np.asarray(gt['group_of']).size:
+                g = torch.as_tensor(np.asarray(gt['group_of']).astype(np.uint8)).reshape(-1)
+                if g.numel() != c.numel():
+                    raise ValueError('group_of: one flag per ground-truth box')
+                group_of[i, :c.numel()] = g
+        return boxes, cls, group_of
+
+    def _add(self, det, count, gt):
+        self._evaluator.add_batch(det, count, gt[0], gt[1], gt_group_of=gt[2])
+
+
+class OpenImagesChallengeEvaluator(OpenImagesEvaluator):
+    """The OpenImages Challenge metric: group-of boxes weigh 1 and the verified image-level labels of `parser.get_ann_info(i)`
+    (`img_cls`, else `labeled_cls`: 1-based classes) decide, with the boxes' classes, which detections of an image are evaluated."""
 
     def __init__(self, dataset, distributed=False, pred_yxyx=False, **kw):
-        super().__init__(dataset, distributed=distributed, pred_yxyx=pred_yxyx, evaluator_cls=ObjectDetectionEvaluator,
-                         metric_prefix='OpenImagesV2', **kw)
+        kw.setdefault('metric_prefix', 'OpenImagesDetectionChallenge')
+        super().__init__(dataset, distributed=distributed, pred_yxyx=pred_yxyx, evaluator_cls=OpenImagesChallengeDetectionEvaluator, **kw)
+
+    def _ground_truth_tables(self):
+        boxes, cls, group_of = super()._ground_truth_tables()
+        lists = []
+        for gt in self._annotations():
+            l = gt['img_cls'] if 'img_cls' in gt else gt.get('labeled_cls', [])
+            lists.append(torch.as_tensor(np.asarray(l), dtype=torch.int64).reshape(-1))
+        K = max([l.numel() for l in lists] + [1])
+        labels = torch.zeros(len(lists), K, dtype=torch.int64)
+        for i, l in enumerate(lists):
+            labels[i, :l.numel()] = l
+        return boxes, cls, group_of, labels
+
+    def _add(self, det, count, gt):
+        self._evaluator.add_batch(det, count, gt[0], gt[1], gt_group_of=gt[2], labeled_cls=gt[3])
 
 
 def create_evaluator(name, dataset, distributed=False, pred_yxyx=False, **kw):
     if 'coco' in name:
         return CocoEvaluator(dataset, distributed=distributed, pred_yxyx=pred_yxyx, **kw)
     elif 'openimages' in name:
+        if 'challenge' in name:
+            return OpenImagesChallengeEvaluator(dataset, distributed=distributed, pred_yxyx=pred_yxyx, **kw)
         return OpenImagesEvaluator(dataset, distributed=distributed, pred_yxyx=pred_yxyx, **kw)
     else:
         return PascalEvaluator(dataset, distributed=distributed, pred_yxyx=pred_yxyx, **kw)

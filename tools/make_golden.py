@@ -18,6 +18,9 @@ Fixtures written
     evaluation.npz            ObjectDetectionEvaluator mAP / CorLoc on seeded detections
     evaluation_scale.npz      the same with `difficult` ground truth at IoU thresholds 0.5, 0.55, 0.75 (one reference
                               evaluator per threshold): per-class AP / CorLoc, the means, the difficult arrays
+    evaluation_openimages.npz the reference's OpenImagesDetectionEvaluator (group-of weights 0, 1, 0.5, 0.3), OpenImagesChallenge-
+                              Evaluator (verified labels) and WeightedPascalDetectionEvaluator (pooled mAP) at the same thresholds:
+                              the drawn group-of / difficult flags and label lists, per-class AP / CorLoc and the mAP figures
     labeler.npz               anchors.AnchorLabeler.batch_label_anchors
     labeler_edges.npz         TargetAssigner.assign on edge cases (ties, shared best anchor, IoU 0 / 1, zero area, rows of
                               class -1 with and without filter_valid, 40 boxes); compact: int16 matches, box targets at
@@ -648,6 +651,95 @@ def gen_evaluation_scale():
     save_reproducible('evaluation_scale', **out)
 
 
+EVAL_OPENIMAGES_WEIGHTS = (0.0, 1.0, 0.5, 0.3)
+
+
+def gen_evaluation_openimages():
+    """The reference's OpenImagesDetectionEvaluator at group-of weights 0, 1, 0.5 and 0.3, its OpenImagesChallengeEvaluator (weight 1,
+    verified image-level labels) and its WeightedPascalDetectionEvaluator (difficult flags, pooled mAP) on eval_case inputs, one
+    reference evaluator per IoU threshold.  Group-of and difficult flags and the label lists are drawn per image, in order, from one
+    RandomState(7) per case and stored; the boxes are rebuilt from the seed.  eval_case has distinct scores and a virtual entry
+    takes the score of a detection that left, so the reference's unstable sort does not matter."""
+    np.float, np.bool, np.NAN = float, bool, np.nan      # as in gen_evaluation
+    from effdet.evaluation.detection_evaluator import (OpenImagesChallengeEvaluator, OpenImagesDetectionEvaluator,
+                                                       WeightedPascalDetectionEvaluator)
+    import _eval_openimages_ref as O
+    out = {'thresholds': np.array(EVAL_SCALE_THRESHOLDS, np.float64), 'weights': np.array(EVAL_OPENIMAGES_WEIGHTS, np.float64)}
+
+    def run(ev, images, extra, thr, C):
+        for i, im in enumerate(images):
+            gt = {'bbox': im['gt_boxes'], 'cls': im['gt_classes']}
+            gt.update({k: np.array(v[i]) for k, v in extra.items()})
+            ev.add_single_ground_truth_image_info(i, gt)
+            # the Challenge class reads DetectionResultFields.detection_scores = 'score', its bases 'scores'
+            ev.add_single_detected_image_info(i, {'bbox': im['det_boxes'], 'scores': im['det_scores'], 'score': im['det_scores'],
+                                                  'cls': im['det_classes']})
+        with np.errstate(all='ignore'):
+            m = ev.evaluate(['c%d' % i for i in range(C)])
+        ap = np.array([m['AP@{}IOU/c{}'.format(thr, i)] for i in range(C)])
+        inside = np.sum((ap > 0) & (ap < 1))
+        assert inside >= 2, '%s at %s: %d classes with 0 < AP < 1 - the fixture would not discriminate' % (type(ev).__name__, thr, inside)
+        # CorLoc from the evaluation object: OpenImagesDetectionEvaluator passes evaluate_corlocs on as its base's third positional
+        # argument, recall_lower_bound (detection_evaluator.py:400-403), so it is left False here
+        return ap, m[ev._metric_names[0]], np.array(ev._evaluation.corloc_per_class, np.float64)
+
+    # Few detections an image: with gen_evaluation_scale's 40 and 100 every group-of box absorbs one.  The seeds are the first of
+    # their shape for which every assert below holds (a duplicate of a matched plain box inside a group-of box of its class is rare).
+    for tag, seed, n_img, C, n_det in (('a', 41, 12, 6, 20), ('b', 51, 10, 10, 24)):
+        cats = [{'id': i + 1, 'name': 'c%d' % i} for i in range(C)]
+        images = eval_case(seed, n_img, C, n_det)
+        rs = np.random.RandomState(7)
+        group_of = [rs.uniform(size=len(im['gt_classes'])) < 0.4 for im in images]
+        difficult = [rs.uniform(size=len(im['gt_classes'])) < 0.3 for im in images]
+        labels = [np.sort(rs.choice(C, size=rs.randint(0, 4), replace=False) + 1).astype(np.int64) for _ in images]
+        # what the data exercises, by the restatement's own intermediate results
+        emitted = silent = duplicate = dropped = 0
+        for i, im in enumerate(images):
+            z = O.zero_based(im, group_of=group_of[i])
+            flags, _, vflags, _ = O.match_image(z, C, EVAL_SCALE_THRESHOLDS, emit=True)
+            live = (vflags[group_of[i]] & O.INVALID) == 0
+            emitted += int(live.any(axis=1).sum())
+            silent += int((~live.any(axis=1)).sum())
+            plain = np.nonzero(~group_of[i])[0]
+            for k in np.nonzero(((flags >> 16) & 1 == 1) & (flags & O.INVALID == 0))[0]:          # absorbed at 0.5
+                same = plain[z['gt_classes'][plain] == z['det_classes'][k]]
+                if same.size and O.iou_matrix(z['det_boxes'][k:k + 1], z['gt_boxes'][same]).max() >= np.float32(0.5):
+                    duplicate += 1
+            zl = O.zero_based(im, group_of=group_of[i], labeled=labels[i])
+            dropped += int(((O.match_image(zl, C, EVAL_SCALE_THRESHOLDS)[0] & O.INVALID) != 0).sum() - ((flags & O.INVALID) != 0).sum())
+        assert emitted >= 1 and silent >= 1, 'case %s: %d group-of boxes with a virtual entry, %d without' % (tag, emitted, silent)
+        assert duplicate >= 1, 'case %s: no absorbed detection would otherwise have been a duplicate false positive' % tag
+        assert dropped >= 1, 'case %s: the Challenge label rule drops nothing' % tag
+        oi_ap, oi_map, oi_cl, ch_ap, ch_map, wp_ap, wp_map = [], [], [], [], [], [], []
+        for w in EVAL_OPENIMAGES_WEIGHTS:
+            res = [run(OpenImagesDetectionEvaluator(cats, matching_iou_threshold=thr, group_of_weight=w), images,
+                       {'group_of': group_of}, thr, C) for thr in EVAL_SCALE_THRESHOLDS]
+            oi_ap.append([r[0] for r in res])
+            oi_map.append([r[1] for r in res])
+            oi_cl.append([r[2] for r in res])
+        for thr in EVAL_SCALE_THRESHOLDS:
+            r = run(OpenImagesChallengeEvaluator(cats, matching_iou_threshold=thr), images, {'group_of': group_of, 'img_cls': labels}, thr, C)
+            ch_ap.append(r[0])
+            ch_map.append(r[1])
+            r = run(WeightedPascalDetectionEvaluator(cats, matching_iou_threshold=thr), images, {'difficult': difficult}, thr, C)
+            wp_ap.append(r[0])
+            wp_map.append(r[1])
+        out[tag + '_meta'] = np.array([seed, n_img, C, n_det])
+        out[tag + '_group_of'] = np.concatenate(group_of).astype(np.uint8)
+        out[tag + '_difficult'] = np.concatenate(difficult).astype(np.uint8)
+        out[tag + '_labels'] = np.concatenate(labels).astype(np.int64)
+        out[tag + '_labels_n'] = np.array([len(l) for l in labels], np.int64)
+        out[tag + '_oi_ap'] = np.array(oi_ap, np.float64)              # [W, T, C]
+        out[tag + '_oi_map'] = np.array(oi_map, np.float64)            # [W, T]
+        out[tag + '_oi_cl'] = np.array(oi_cl, np.float64)              # [W, T, C]
+        out[tag + '_ch_ap'] = np.array(ch_ap, np.float64)              # [T, C]
+        out[tag + '_ch_map'] = np.array(ch_map, np.float64)
+        out[tag + '_wp_ap'] = np.array(wp_ap, np.float64)
+        out[tag + '_wp_map'] = np.array(wp_map, np.float64)            # [T] pooled
+    save_reproducible('evaluation_openimages', **out)
+    assert os.path.getsize(os.path.join(OUT, 'evaluation_openimages.npz')) < 32 * 1024
+
+
 def gen_transforms():
     """The reference's own transform pipelines (effdet/data/transforms.py:304-368) under a seeded `random` / `np.random`.  What PIL
     is asked to do is recorded by wrapping Image.transpose / resize / crop for the duration of a call."""
@@ -727,6 +819,6 @@ def gen_transforms():
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ['anchors', 'post_process', 'decode', 'soft_nms', 'generate_detections', 'loss',
-                             'labeler', 'labeler_edges', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'evaluation_scale', 'meta_nets', 'aux_losses', 'transforms']
+                             'labeler', 'labeler_edges', 'labeler_task_cls', 'config', 'bifpn_head', 'bifpn_head_pad0', 'evaluation', 'evaluation_scale', 'evaluation_openimages', 'meta_nets', 'aux_losses', 'transforms']
     for w in which:
         globals()['gen_' + w]()
