@@ -76,6 +76,19 @@ int effdet_stem_dw_fused(void* stream, int in_dtype, int dtype, const void* X, c
                          const float* s1, const float* t1, const float* taps, const float* s2, const float* t2,
                          void* Y, float* pool_partial, int B, int H, int W, int C);
 int effdet_stem_dw_parts(int dtype, int H, int W, int C);      /* pool partial rows per image of the kernel that will run (bf16: rolling-window form) */
+/* Alignment of X: the rolling-window form (bf16 and two-term bf16 with C = 32, an even W and ceil(W/2) >= 16, ceil(H/2) >= 8)
+ * loads two adjacent pixels of a plane with one instruction and returns EFFDET_EINVAL, before any launch, unless X is aligned to
+ * that load: 4 bytes for float32 and bfloat16 images, 2 bytes for uint8 images.  The tile form takes any element-aligned X.
+ * Host-only: the form and geometry an effdet_stem_dw_fused[_u8] call (in_dtype 0 | 1 | 2 = uint8) would run, from the functions
+ * the launch itself uses (stem_dw_plan / pick_stem_roll); contract of effdet_pw_gemm_plan_describe (negative where the launch
+ * refuses; the pad flag in dtype selects pad_t / pad_l and is otherwise stripped).  Slots:
+ *    0  form: 0 = 16 x 16 tiles (stem_dw.hip), 1 = rolling window (stem_roll.hip);  1  pool partial rows per image (= effdet_stem_dw_parts)
+ *    2  pad_t;  3  pad_l;  4  Ho;  5  Wo;  6  tiles along x | strips;  7  tiles along y | bands;  8  tile width | strip width in
+ *    output columns;  9  tile height | rows per band;  10  workgroups per image (rolling form; 0 for tiles);  11  dynamic LDS bytes
+ *    12  tile form: the geometric part of the two-pixel patch load (bf16 image into bf16, even W, even pad_l; the launch also
+ *        wants X 4-byte aligned); 0 in the rolling form */
+#define EFFDET_STEM_DW_PLAN_INTS 13
+int effdet_stem_dw_plan_describe(int dtype, int in_dtype, int H, int W, int C, int* out, int n);
 
 /* Input normalisation of the reference's PrefetchLoader (effdet/data/loader.py:114-128):
  * y = (float(x) - mean[c]) / std[c], x uint8 NCHW [B,C,hw], mean/std = 255 * the dataset constants

@@ -303,11 +303,11 @@ __attribute__((visibility("hidden"))) int effdet_mbconv_wide_launch(hipStream_t 
                               int B, int H, int W, int Cin, int mid, int k, int stride, int pair = 0, int sym = 0);
 
 // stem_roll.hip (internal): rolling-window form of the fused stem + stage-0 depthwise, bf16 only; parts = SE pool partial rows
-// per image when the form applies, 0 otherwise
+// per image when the form applies, 0 otherwise.  plan set: fill the slots of effdet_stem_dw_plan_describe instead of launching
 __attribute__((visibility("hidden"))) int effdet_stem_roll_parts(int H, int W, int C, int pair = 0, int sym = 0);
 __attribute__((visibility("hidden"))) int effdet_stem_roll_launch(hipStream_t st, int in_dtype, const void* X, const float* mean, const float* stdv,
                             const void* Wk, const float* s1, const float* t1, const float* taps, const float* s2, const float* t2,
-                            void* Y, float* pool_partial, int B, int H, int W, int C, int pair = 0, int sym = 0);
+                            void* Y, float* pool_partial, int B, int H, int W, int C, int pair = 0, int sym = 0, int* plan = nullptr);
 
 // train_net.hip (internal): out[g][l] (+)= alpha * sum_s in[g][s][l], summed in a fixed order
 __attribute__((visibility("hidden"))) int effdet_launch_reduce_mid(hipStream_t st, const float* in, int G, int S, long long L, float* out,

@@ -295,7 +295,7 @@ extern "C" int effdet_stem_dw_parts(int dtype, int H, int W, int C) {
 static int stem_dw_common(void* stream, int in_dtype, int dtype, const void* X, const float* mean, const float* stdv, const void* Wk,
                           const float* s1, const float* t1, const float* taps,
                           const float* s2, const float* t2, void* Y, float* pool_partial,
-                          int B, int H, int W, int C) {
+                          int B, int H, int W, int C, int* plan = nullptr) {
     if (!X || !Wk || !s1 || !t1 || !taps || !s2 || !t2 || !Y || B <= 0 || H <= 0 || W <= 0) return EFFDET_EINVAL;
     const int sym = take_pad_flag(dtype);
     if (C <= 0 || C % 8 || C > 64 || in_dtype < 0 || in_dtype > 2 || dtype < 0 || dtype > 2 || (in_dtype == 2 && (!mean || !stdv))) return EFFDET_EINVAL;
@@ -305,7 +305,7 @@ static int stem_dw_common(void* stream, int in_dtype, int dtype, const void* X, 
     if (stem_dw_plan(dtype, H, W, C, sym, &roll) <= 0) return EFFDET_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (roll)
-        return effdet_stem_roll_launch(st, in_dtype, X, mean, stdv, Wk, s1, t1, taps, s2, t2, Y, pool_partial, B, H, W, C, dtype == 2, sym);
+        return effdet_stem_roll_launch(st, in_dtype, X, mean, stdv, Wk, s1, t1, taps, s2, t2, Y, pool_partial, B, H, W, C, dtype == 2, sym, plan);
     SdArgs a;
     for (int i = 0; i < 3; ++i) { a.nmean[i] = in_dtype == 2 ? mean[i] : 0.f; a.nstd[i] = in_dtype == 2 ? stdv[i] : 1.f; }
     a.X = X; a.in_dtype = in_dtype; a.Wk = Wk; a.s1 = s1; a.t1 = t1; a.taps = taps; a.s2 = s2; a.t2 = t2;
@@ -313,9 +313,15 @@ static int stem_dw_common(void* stream, int in_dtype, int dtype, const void* X, 
     a.Ho = same_out(H, 2); a.Wo = same_out(W, 2);
     a.pad_t = pad_before(H, 3, 2, sym); a.pad_l = pad_before(W, 3, 2, sym);
     a.tiles_x = (a.Wo + SD_TW - 1) / SD_TW; a.tiles_y = (a.Ho + SD_TH - 1) / SD_TH;
-    a.vec_in = in_dtype == 1 && dtype == 1 && W % 2 == 0 && a.pad_l % 2 == 0 && reinterpret_cast<uintptr_t>(X) % 4 == 0;
+    const int vec_geom = in_dtype == 1 && dtype == 1 && W % 2 == 0 && a.pad_l % 2 == 0;
+    a.vec_in = vec_geom && reinterpret_cast<uintptr_t>(X) % 4 == 0;
     dim3 grid(a.tiles_x * a.tiles_y, B), block(256);
     const size_t lds = dtype == 0 ? sd_lds_bytes<float>(C) : sd_lds_bytes<bf16_t>(C);
+    if (plan) {                                  // effdet_stem_dw_plan_describe: report the geometry, launch nothing
+        const int v[EFFDET_STEM_DW_PLAN_INTS] = {0, a.tiles_x * a.tiles_y, a.pad_t, a.pad_l, a.Ho, a.Wo, a.tiles_x, a.tiles_y, SD_TW, SD_TH, 0, (int)lds, vec_geom};
+        for (int i = 0; i < EFFDET_STEM_DW_PLAN_INTS; ++i) plan[i] = v[i];
+        return EFFDET_OK;
+    }
     void (*kern)(SdArgs) = nullptr;
     if (dtype == 0) kern = in_dtype == 0 ? stem_dw_kernel<float, 0> : in_dtype == 1 ? stem_dw_kernel<float, 1> : stem_dw_kernel<float, 2>;
     else kern = in_dtype == 0 ? stem_dw_kernel<bf16_t, 0> : in_dtype == 1 ? stem_dw_kernel<bf16_t, 1> : stem_dw_kernel<bf16_t, 2>;
@@ -325,6 +331,18 @@ static int stem_dw_common(void* stream, int in_dtype, int dtype, const void* X, 
     }
     hipLaunchKernelGGL(kern, grid, block, lds, st, a);
     return effdet_check_launch();
+}
+
+extern "C" int effdet_stem_dw_plan_describe(int dtype, int in_dtype, int H, int W, int C, int* out, int n) {
+    if (!out || n <= 0) return EFFDET_EINVAL;
+    alignas(16) static float present[4];                             // stand-in for every pointer: present, 16-byte aligned
+    int plan[EFFDET_STEM_DW_PLAN_INTS];
+    const int rc = stem_dw_common(nullptr, in_dtype, dtype, present, present, present, present, present, present, present, present, present,
+                                  present, present, 1, H, W, C, plan);
+    if (rc != EFFDET_OK) return rc;
+    const int m = n < EFFDET_STEM_DW_PLAN_INTS ? n : EFFDET_STEM_DW_PLAN_INTS;
+    for (int i = 0; i < m; ++i) out[i] = plan[i];
+    return m;
 }
 
 extern "C" int effdet_stem_dw_fused(void* stream, int in_dtype, int dtype, const void* X, const void* Wk,

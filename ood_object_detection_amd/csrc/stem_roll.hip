@@ -422,10 +422,18 @@ int effdet_stem_roll_parts(int H, int W, int C, int pair, int sym) {
 
 int effdet_stem_roll_launch(hipStream_t st, int in_dtype, const void* X, const float* mean, const float* stdv, const void* Wk,
                             const float* s1, const float* t1, const float* taps, const float* s2, const float* t2,
-                            void* Y, float* pool_partial, int B, int H, int W, int C, int pair, int sym) {
+                            void* Y, float* pool_partial, int B, int H, int W, int C, int pair, int sym, int* plan) {
     const SrGeometry g = pick_stem_roll(H, W, C, pair != 0, sym);
     if (!g.use) return EFFDET_EINVAL;
     if (pair && in_dtype == 1) return EFFDET_EINVAL;                 // two-term mode takes float32 or raw uint8 images
+    // a lane loads two adjacent pixels at once (a dword of bfloat16, a dwordx2 of float32, a 16-bit pair of uint8): X aligned to that load
+    if (reinterpret_cast<uintptr_t>(X) % (in_dtype == 2 ? 2 : 4)) return EFFDET_EINVAL;
+    if (plan) {                                                       // effdet_stem_dw_plan_describe: report the geometry, launch nothing
+        const int v[EFFDET_STEM_DW_PLAN_INTS] = {1, g.nstrips * g.nbands, pad_before(H, 3, 2, sym), pad_before(W, 3, 2, sym), same_out(H, 2), same_out(W, 2),
+                                                 g.nstrips, g.nbands, g.TWo, g.band_rows, g.per_image, (int)g.lds, 0};
+        for (int i = 0; i < EFFDET_STEM_DW_PLAN_INTS; ++i) plan[i] = v[i];
+        return EFFDET_OK;
+    }
     SrArgs a;
     a.X = X; a.Wk = Wk;
     for (int i = 0; i < 3; ++i) { a.nmean[i] = in_dtype == 2 ? mean[i] : 0.f; a.nstd[i] = in_dtype == 2 ? stdv[i] : 1.f; }
