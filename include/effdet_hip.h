@@ -1095,6 +1095,60 @@ int effdet_logit_ood_fit(void* stream, int dtype, const void* logits, long long 
 /* bytes of the fit workspace for `rows` = B * K rows of C classes (pure host code; -22 for a bad argument) */
 long long effdet_logit_ood_workspace_bytes(long long rows, int C);
 
+/* ---- activation-shaping OOD scores (csrc/act_shaping.hip): ReAct, ASH-P / ASH-B / ASH-S, SCALE, GradNorm -------------------------
+ * The class tower - the input of class_net.predict.conv_dw - is addressed by a level table as above (float32 or bfloat16, channel
+ * stride 1, F in {64, 88, 112, 160, 224, 288}) with level_heights / level_widths (host int arrays; height * width = the level's
+ * cells, a cell is y * width + x).  taps [9][F] float32 (k = 3 ky + kx).  With Cp = C rounded up to 16 and Fp = F rounded up to 16
+ * the pointwise weight W [A * C][F] comes packed per anchor slot a: w_rows [A][F][Cp] (w_rows[a][j][c] = W[a C + c][j]) for the
+ * entries form, w_tiles [A][Cp][Fp] for the cells form, bias [A][Cp] for both; zero in the padding of the weights, -inf in that of
+ * the bias.  1 <= C <= 1024, A >= 1, B * K <= 2^27.
+ * Penultimate row of a cell in float32 (bfloat16 widened exactly), every product and every sum rounded once:
+ *   d_j = t_0j x_0j, then d_j = d_j + t_kj x_kj for k = 1 .. 8, x_k the tower value at (y + ky - 1, x + kx - 1), 0 outside the map.
+ * Shaping d -> x', method 0 none: x' = d;  1 react: x'_j = min(d_j, react_c[0]) (device memory);  with the kept set = the k largest
+ * d_j by value (1 <= k <= F; equal values: the lower j first), s1 = sum_j max(d_j, 0), s2 = the same over the kept set and
+ * f = exp(s1 / s2) (1 where s2 == 0):  2 ash_p: kept d_j, others 0;  3 ash_b: kept s1 / k, others 0;  4 ash_s: kept d_j f, others 0;
+ * 5 scale: d_j f for every j.  s1, s2: a lane's channels t, t + 64, .. ascending, then the lanes by the xor tree 32 .. 1.
+ * Logits of anchor slot a: z_c = bias[a][c] + sum_j W[a C + c][j] x'_j, u = z / temperature (> 0):
+ *   energy = -(temperature * logsumexp(u)),  max_logit = max z,  predicted_class = the lowest argmax (int64),
+ *   gradnorm (NULL: not wanted) = (sum_c |p_c - 1 / C|) * (sum_j |d_j|), p the softmax at temperature 1 of the logits of the
+ *   unshaped row d.  A row with a non-finite d_j scores NaN in the float outputs and -1 in the class output.
+ * A row's scores are not bit-equal between the entries and the cells form.  Bad arguments return -22 before any launch.  No call
+ * synchronises with the host or allocates; no floating-point atomics; results are bit-identical from run to run and a row's
+ * (a cell's) scores do not depend on how rows (cells) are grouped into workgroups or calls. */
+/* bytes of the fit workspace for `rows` = B * K rows (pure host code; -22 for a bad argument) */
+long long effdet_act_shaping_workspace_bytes(long long rows, int F);
+/* Entries form.  Row (b, j) is the cell anchor / A and the slot anchor % A of anchor = anchor_index[b * K + j] (NULL: j); it counts
+ * when j < count[b] (NULL: all) and the anchor lies in [0, A * P).  Outputs [B][K]; a row that does not count holds 0 in the float
+ * outputs and -1 in the class output.  rows (NULL: not wanted) [B][K][F] float32 receives x' (NaN for a non-finite row, 0 for a
+ * row that does not count).  One wave per row, sum_j a float64 fma chain with j ascending, rounded to float32 once.  One launch. */
+int effdet_act_shaping_score(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                             const long long* level_batch_strides, const long long* level_cell_strides,
+                             const long long* level_channel_strides, const int* level_heights, const int* level_widths, int F, int C,
+                             int A, int B, long long K, const long long* anchor_index, const void* count, int count_is_int64,
+                             const float* taps, const float* w_rows, const float* bias, int method, int k, const float* react_c,
+                             float temperature, float* energy, float* max_logit, long long* predicted_class, float* gradnorm,
+                             float* rows);
+/* Cells form: every anchor of every cell, outputs [B][A * P] at index cell * A + a (the head's anchor order).  The shaped row is
+ * formed once per cell; the [16 cells x Fp] by [Fp x Cp] products run on the float32-input MFMA (K-chunk c of 16 into accumulator
+ * c mod 4, then (a0 + a1) + (a2 + a3)), the log-sum-exp is kept online in
+ * registers over the class tiles ascending and combined over the 16 lanes of a row by the xor tree 1 .. 8.  One launch. */
+int effdet_act_shaping_score_cells(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                                   const long long* level_batch_strides, const long long* level_cell_strides,
+                                   const long long* level_channel_strides, const int* level_heights, const int* level_widths, int F,
+                                   int C, int A, int B, const float* taps, const float* w_tiles, const float* bias, int method, int k,
+                                   const float* react_c, float temperature, float* energy, float* max_logit,
+                                   long long* predicted_class, float* gradnorm);
+/* Fit statistics over the rows that count (selected as in the entries form) and whose d is finite: their number onto n [1] int64,
+ * sum d onto sum_d [F] float64 - the rows compacted in (b, j) order; workgroup s of 256 adds chunk s of that list (wave w the rows
+ * w, w + 4, .. in list order, then the waves in order), one workgroup adds the chunks in chunk order: the order follows from the
+ * number of such rows alone - and every d_j onto hist [65536] int64 at the upper 16 bits of its order-preserving key (bits ^ 2^31
+ * for a cleared sign bit, ~bits otherwise; integer atomics).  Six launches. */
+int effdet_act_shaping_fit(void* stream, int dtype, int num_levels, const void* const* level_bases, const long long* level_cells,
+                           const long long* level_batch_strides, const long long* level_cell_strides,
+                           const long long* level_channel_strides, const int* level_heights, const int* level_widths, int F, int A,
+                           int B, long long K, const long long* anchor_index, const void* count, int count_is_int64, const float* taps,
+                           long long* n, double* sum_d, long long* hist, void* workspace, long long workspace_bytes);
+
 /* ---- energy-margin OOD training losses (csrc/energy_reg.hip): energy-bounded hinge and logistic uncertainty loss, with gradients --
  * Rows are the C class logits (float32 or bfloat16, dtype = EFFDET_F32 / EFFDET_BF16) of a contiguous [B][N][C] tensor, role [B][N]
  * int8: 1 = in-distribution, 0 = outlier, anything else = the row does not count and is not read.  1 <= C <= 1024, B * N <= 2^27.

@@ -112,6 +112,16 @@ SIGNATURES = {
     'effdet_logit_ood_fit': (c_int, [c_void_p, c_int, c_void_p, c_ll, c_ll, c_int, c_int, c_ll, c_ll, c_void_p, c_void_p, c_int, c_float,
                                      c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
     'effdet_logit_ood_workspace_bytes': (c_ll, [c_ll, c_int]),
+    'effdet_act_shaping_workspace_bytes': (c_ll, [c_ll, c_int]),
+    'effdet_act_shaping_score': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), P(c_int), P(c_int), c_int,
+                                         c_int, c_int, c_int, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                         c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_act_shaping_score_cells': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), P(c_int), P(c_int),
+                                               c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
+                                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_act_shaping_fit': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), P(c_int), P(c_int), c_int,
+                                       c_int, c_int, c_ll, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_ll]),
     'effdet_energy_reg': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_ll, c_int, c_int, c_int, c_float, c_float, c_float,
                                   c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_ll]),

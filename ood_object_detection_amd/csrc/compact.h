@@ -1,5 +1,5 @@
 // Workgroup reductions, integer helpers and the ordered compaction that the OOD and the evaluation units share (feature_ood.hip,
-// feature_knn.hip, feature_subspace.hip, logit_ood.hip, energy_reg.hip, outlier_synth.hip, ood_eval.hip, and through radix_sort.h,
+// feature_knn.hip, feature_subspace.hip, logit_ood.hip, act_shaping.hip, energy_reg.hip, outlier_synth.hip, ood_eval.hip, and through radix_sort.h,
 // eval_match.h and eval_sorted.h the evaluation units eval_scale.hip, coco_eval.hip, lvis_eval.hip).  The compaction: the kept entries of a [B, K] call
 // get consecutive positions in (b, j) order by three launches - kept entries per tile of 2048 (fo_count_kernel), the tiles' first
 // positions in one workgroup (fo_base_kernel), then ballot ranks inside a tile (fo_positions, called by the unit's own write

@@ -1,4 +1,4 @@
-// What the OOD units that read rows of a [B, K] call share (feature_ood.hip, feature_knn.hip, feature_subspace.hip, logit_ood.hip;
+// What the OOD units that read rows of a [B, K] call share (feature_ood.hip, feature_knn.hip, feature_subspace.hip, logit_ood.hip, act_shaping.hip;
 // DESIGN.md §8): which entries count (FoSel), the class label of an entry (FoClasses), the feature rows - F-vectors of pyramid cells
 // read through a level table (<= 8 entries: base, cells, batch stride, cell stride; channel stride 1), float32 or bfloat16 -, the
 // geometry and staging of the kernels that keep 16 centred rows per wave in LDS, the dispatch on the width, and the host checks of

@@ -125,7 +125,9 @@ class DetBenchPredict(nn.Module):
     `partial_mahalanobis`, and `vim` once its alpha is set.  A scorer that declares `WANTS_CLASS_LOGITS = True`
     (`ood_logits.LogitOOD`) is given the packed class logits [B, N, C] of the (sub-)batch instead of the pyramid (a view of the
     engine's own buffer, no copy): it adds `msp`, `neg_entropy`, `gen`, `joint_energy`, `predicted_class` and, once fitted,
-    `kl_matching`, `kl_class` and `standardized_max_logit`."""
+    `kl_matching`, `kl_class` and `standardized_max_logit`.  A scorer that declares `WANTS_CLASS_TOWER = True`
+    (`ood_shaping.ActivationShapingOOD`) sets `model.keep_class_tower` and is given the engine's `class_tower_views()`: it adds
+    `<name>_energy`, `<name>_max_logit`, `<name>_class` (and `gradnorm`); several shapers with different names share one pass."""
 
     def __init__(self, model, streams=None, feature_ood=None):
         super().__init__()
@@ -139,7 +141,9 @@ class DetBenchPredict(nn.Module):
         self.soft_nms = model.config.soft_nms
         self.streams = streams
         self.feature_ood = feature_ood
-        _feature_scorers(feature_ood)             # refuses colliding keys here, not in the first forward
+        scorers = _feature_scorers(feature_ood)   # refuses colliding keys here, not in the first forward
+        if any(getattr(s, 'WANTS_CLASS_TOWER', False) for s in scorers):
+            model.keep_class_tower = True         # (shallow copies of _split_setup take the flag with them)
         self.last_count = None
         self.last_ood = None
         self._replicas = None       # [(model copy, stream)], built on first use
@@ -171,7 +175,9 @@ class DetBenchPredict(nn.Module):
         if scorers:
             feat = {}
             for scorer in scorers:
-                if getattr(scorer, 'WANTS_CLASS_LOGITS', False):
+                if getattr(scorer, 'WANTS_CLASS_TOWER', False):
+                    feat.update(scorer.score(model._engine.class_tower_views(), anchor, count))
+                elif getattr(scorer, 'WANTS_CLASS_LOGITS', False):
                     feat.update(scorer.score(_packed(class_out, self.num_levels, self.num_classes), anchor, count))
                 elif getattr(scorer, 'WANTS_LOGIT_SCORE', False):
                     logit = {'energy': energy, 'max_logit': maxlogit}[scorer.logit]
@@ -185,7 +191,7 @@ class DetBenchPredict(nn.Module):
         import copy
         B, size = x.shape[0], (x.shape[2], x.shape[3])
         N = self.anchors.boxes.shape[0]
-        key = (B, size, n, x.device, self.model.weights_token(), self.num_classes)
+        key = (B, size, n, x.device, self.model.weights_token(), self.num_classes, bool(getattr(self.model, 'keep_class_tower', False)))
         if self._replicas is not None and self._replicas[0] == key and all(rep._engine is eng for rep, _, eng in self._replicas[1]):
             return self._replicas[1]
         e = torch.empty(B, N, dtype=torch.float32, device=x.device)

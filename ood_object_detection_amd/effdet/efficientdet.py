@@ -303,6 +303,8 @@ class EfficientDet(nn.Module):
         # 'native': the kernels compute in the parameters' dtype (float32 parity / bfloat16 throughput).  'accurate' (float32
         # parameters): two-term bf16 values everywhere - float32-grade results (north_star's 1e-3) at matrix-core speed.
         self.compute_mode = 'native'
+        # True: the inference engine keeps the class tower's output (the input of class_net.predict) for ood_shaping; outputs unchanged
+        self.keep_class_tower = False
         # [0]: bumped whenever parameters may have changed (load_state_dict, .to(), reset_head, invalidate(), PretrainStep);
         # [1]: cached (module ids, parameter + buffer tensors) behind weights_token().  Shared by shallow copies of the model.
         self._wver = [0, None]

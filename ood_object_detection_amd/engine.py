@@ -49,6 +49,8 @@ class Engine(object):
         self.lib = _lib.load()
         self.device, self.dtype, self.dt = p0.device, p0.dtype, _DT[p0.dtype]
         self.mode = getattr(model, 'compute_mode', 'native') or 'native'
+        # keep the class tower's output (the input of class_net.predict) in a buffer of its own: ood_shaping reads it
+        self.keep_class_tower = bool(getattr(model, 'keep_class_tower', False))
         if self.mode not in ('native', 'accurate'):
             raise ValueError("compute_mode must be 'native' or 'accurate' (got %r)" % (self.mode,))
         self.pair = self.mode == 'accurate'
@@ -84,7 +86,8 @@ class Engine(object):
     def matches(self, model):
         p0 = model.backbone.conv_stem.weight
         return p0.device == self.device and p0.dtype == self.dtype and model.config.num_classes == self.C and \
-            (getattr(model, 'compute_mode', 'native') or 'native') == self.mode
+            (getattr(model, 'compute_mode', 'native') or 'native') == self.mode and \
+            bool(getattr(model, 'keep_class_tower', False)) == self.keep_class_tower
 
     # ------------------------------------------------------------------------------------ utils
     def _new(self, *shape, dtype=None):
@@ -581,6 +584,17 @@ class Engine(object):
             out.append(pyr[:, off:off + h * w, :].unflatten(1, (h, w)).permute(0, 3, 1, 2))
         return out
 
+    def class_tower_views(self):
+        """per-level [B, F, h, w] views of the class tower's output, the input of class_net.predict (model.keep_class_tower; a
+        decoded copy in accurate mode, exactly as pyramid_views)"""
+        if self.cls_tower is None:
+            raise RuntimeError('the class tower is not kept: set model.keep_class_tower = True (a HeadNet class_net) before the forward')
+        out = []
+        tw = self._act_out(self.cls_tower)
+        for (h, w), off in zip(self.level_hw, self.level_off):
+            out.append(tw[:, off:off + h * w, :].unflatten(1, (h, w)).permute(0, 3, 1, 2))
+        return out
+
     def run_fpn(self, feats, ret=True):
         if feats is not None:
             if len(feats) != len(self.feats):
@@ -614,7 +628,7 @@ class Engine(object):
         def level_ptrs(t, width):
             return [t.data_ptr() + off * width * es for off in self.level_off]
 
-        def plan_for(head, name, out_t, K, ood, out_f32=False):
+        def plan_for(head, name, out_t, K, ood, out_f32=False, keep=None):
             plan = []
             src = self.pyr
             bufs = [t1, t2]
@@ -628,7 +642,7 @@ class Engine(object):
                     ss.append(s)
                     ts.append(t)
                 s, t = self._f32(torch.stack(ss)), self._f32(torch.stack(ts))
-                dst = bufs[r % 2]
+                dst = keep if keep is not None and r == cfg.box_class_repeats - 1 else bufs[r % 2]
                 ins = [[(p, P * F, hw, 0)] for p, hw in zip(level_ptrs(src, F), self.level_hw)]
                 plan.append(self._sepconv_call(self.level_hw, ins, 0, [], 1.0, 0, taps, wq, s, t, list(range(L)), 1, F, F,
                                                level_ptrs(dst, F), [P * F] * L, '%s.conv_rep.%d' % (name, r)))
@@ -651,7 +665,9 @@ class Engine(object):
 
         # infer.py:186-191 replaces `model.class_net` by a MetaHead (functional head, own launches in effdet/meta_head.py):
         # backbone / BiFPN / box head then still run from this plan, the class outputs come from the MetaHead's forward
-        self._cls_plan = plan_for(model.class_net, 'class_net', self.cls_all, C, True) if hasattr(model.class_net, 'conv_rep') else None
+        # keep_class_tower: the last conv_rep of the class plan writes a [B, P, F] buffer that the box head does not reuse
+        self.cls_tower = self._new(B, P, F) if self.keep_class_tower and hasattr(model.class_net, 'conv_rep') else None
+        self._cls_plan = plan_for(model.class_net, 'class_net', self.cls_all, C, True, keep=self.cls_tower) if hasattr(model.class_net, 'conv_rep') else None
         self._box_plan = plan_for(model.box_net, 'box_net', self.box_all, 4, False, out_f32=True)
 
     def head_views(self, t, K):
