@@ -917,6 +917,55 @@ int effdet_openimages_sorted(void* stream, const float* scores, const int* class
                              int pooled, const int* n_plain, const int* n_group, const int* gt_imgs, const int* correct_imgs,
                              void* workspace, long long workspace_bytes, void* result);
 
+/* ---- detection calibration (csrc/calibration_eval.hip): reliability tables, D-ECE / LaECE terms, Platt / temperature fit ---------- */
+
+/* effdet_eval_match_multi (the same flag words, gt_count, gt_imgs and correct_imgs, bit for bit) that also writes iou [B,max_det]:
+ * the float32 IoU of the slot's box with its candidate, the box of its class with the largest IoU (lowest index on ties), 0 where
+ * the class has no box or the slot is dropped.  kept [2 B] (required): the slots of image b that are not dropped and have
+ * score >= score_threshold (not NaN), then its NaN scores.  (num_classes + 3 M + 8) ints of LDS <= 64 KiB. */
+int effdet_calibration_match(void* stream, const float* det, const int* det_count, const float* gt_boxes, const long long* gt_cls,
+                             const unsigned char* gt_difficult, int B, int max_det, int M, int num_classes, const float* thresholds,
+                             int num_thresholds, float score_threshold, unsigned int* flags, float* iou, int* kept, int* gt_count,
+                             int* gt_imgs, int* correct_imgs);
+/* effdet_eval_append for that match and the same score_threshold: (score, 0-based class, flag word, IoU) of the kept slots to
+ * scores, classes, out_flags and out_iou at the device cursor; `state` as there. */
+int effdet_calibration_append(void* stream, const float* det, const unsigned int* flags, const float* iou, const int* kept, int B,
+                              int max_det, float score_threshold, float* scores, int* classes, unsigned int* out_flags,
+                              float* out_iou, long long capacity, unsigned int* state);
+/* pure host queries: workspace bytes of effdet_calibration_table; byte offset in it of the sorted keys (which = 0), flag words (1)
+ * and IoU (2) of the class sort and of the same three of the pooled sort (3, 4, 5); bytes of the result block, -22 unless
+ * 1 <= num_thresholds <= 16, 1 <= num_classes <= 65535, 1 <= bins <= 64 and num_thresholds (num_classes + 1) bins <= 2^20 */
+long long effdet_calibration_workspace_bytes(long long capacity, int num_classes);
+long long effdet_calibration_sorted_offset(long long capacity, int num_classes, int which);
+long long effdet_calibration_result_bytes(int num_thresholds, int num_classes, int bins);
+/* The stable radix sort by (class, score descending, arrival) of the first n entries (n < 0: min(state[0], capacity), read on the
+ * device) with flag word and IoU as payload, the same sort again by score alone (scope `pooled`), then per (threshold t, scope s
+ * = class 0 .. C-1 or pooled = C, scheme, bin k) over the bin's entries not ignored at t: n, tp, sum_p, sum_iou (over the true
+ * positives).  Scheme 0 (width): k = min(bins - 1, max(0, (int)(p * (float)bins))); scheme 1 (mass): the sorted positions
+ * [floor(k m / bins), floor((k + 1) m / bins)) of the scope's m entries.  result: 8-byte words {n, lost, NaN scores, T, C, bins, 0,
+ * 0}; n, tp (int64), sum_p, sum_iou (float64) [T][C+1][2][bins] each; brier, nll (float64), out_of_range, entries (int64)
+ * [T][C+1] each; int64 gt_count [C], gt_imgs [C], correct [T][C].  Every float64 sum is taken in an order that depends on the
+ * sorted positions alone (calibration_eval.hip's header).  Capturable; bit-identical from run to run. */
+int effdet_calibration_table(void* stream, const float* scores, const int* classes, const unsigned int* flags, const float* iou,
+                             long long capacity, long long n, const unsigned int* state, int num_thresholds, int num_classes, int bins,
+                             const int* gt_count, const int* gt_imgs, const int* correct_imgs, void* workspace,
+                             long long workspace_bytes, void* result);
+/* bytes of the partial sums of effdet_calibration_fit_step: 64 per 2048 entries of the capacity */
+long long effdet_calibration_fit_workspace_bytes(long long capacity);
+/* One iteration (two launches) of the damped Newton fit of p' = sigmoid(a logit(p~) + b) over the appended, unsorted entries that
+ * are not ignored at threshold_index, target tp (soft_target = 0) or tp ? IoU : 0; temperature != 0 keeps b = 0.  fit_state: 16
+ * float64 on the device {a, b, NLL, trial a, trial b, step scale, direction a, b, first NLL, evaluations, halvings, converged,
+ * frozen, has an accepted point, entries used, 0}, started as {1, 0, 0, 1, 0, 1, 0 ...}.  A frozen state (converged, or given
+ * up) makes the launches exit at once.  Nothing is read back; capturable. */
+int effdet_calibration_fit_step(void* stream, const float* scores, const unsigned int* flags, const float* iou, long long capacity,
+                                const unsigned int* state, int threshold_index, int soft_target, int temperature, double* fit_state,
+                                void* workspace, long long workspace_bytes);
+/* det_out [B,max_det,6] = det_in with the score (column 4) of row (b, j), j < count[b], replaced by
+ * float32(sigmoid(a logit(p~) + b)) in float64, (a, b) = fit_state[0], fit_state[1] read on the device, p~ = the score clamped
+ * to [2^-24, 1 - 2^-24]; a NaN score stays NaN.  det_out may be det_in.  One launch. */
+int effdet_calibration_apply(void* stream, const float* det_in, const int* count, const double* fit_state, int B, int max_det,
+                             float* det_out);
+
 /* ---- OOD evaluation helpers -------------------------------------------- */
 
 /* The fork's novelty score (infer.py:425-427, 465-471, 607-616), reported beside energy / max-logit:

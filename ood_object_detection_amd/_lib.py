@@ -226,6 +226,19 @@ SIGNATURES = {
     'effdet_openimages_sorted_result_bytes': (c_ll, [c_int, c_int]),
     'effdet_openimages_sorted': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_double, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'effdet_calibration_match': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                         c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_calibration_append': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_ll, c_void_p]),
+    'effdet_calibration_workspace_bytes': (c_ll, [c_ll, c_int]),
+    'effdet_calibration_sorted_offset': (c_ll, [c_ll, c_int, c_int]),
+    'effdet_calibration_result_bytes': (c_ll, [c_int, c_int, c_int]),
+    'effdet_calibration_table': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p, c_int, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]),
+    'effdet_calibration_fit_workspace_bytes': (c_ll, [c_ll]),
+    'effdet_calibration_fit_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_ll]),
+    'effdet_calibration_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'effdet_train_fold_bn': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'effdet_train_convbn_grads': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

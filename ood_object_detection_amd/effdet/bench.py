@@ -127,11 +127,16 @@ class DetBenchPredict(nn.Module):
     engine's own buffer, no copy): it adds `msp`, `neg_entropy`, `gen`, `joint_energy`, `predicted_class` and, once fitted,
     `kl_matching`, `kl_class` and `standardized_max_logit`.  A scorer that declares `WANTS_CLASS_TOWER = True`
     (`ood_shaping.ActivationShapingOOD`) sets `model.keep_class_tower` and is given the engine's `class_tower_views()`: it adds
-    `<name>_energy`, `<name>_max_logit`, `<name>_class` (and `gradnorm`); several shapers with different names share one pass."""
+    `<name>_energy`, `<name>_max_logit`, `<name>_class` (and `gradnorm`); several shapers with different names share one pass.
 
-    def __init__(self, model, streams=None, feature_ood=None):
+    `calibrator` (extension, default None: nothing changes): a `calibration.DetectionCalibrator`; its `apply` is the last step on
+    the returned tensor (one elementwise launch that rewrites the score column).  The engine, its graphs, `last_ood` and
+    `last_count` are untouched."""
+
+    def __init__(self, model, streams=None, feature_ood=None, calibrator=None):
         super().__init__()
         self.model = model
+        self.calibrator = calibrator
         self.config = model.config
         self.num_levels = model.config.num_levels
         self.num_classes = model.config.num_classes
@@ -210,7 +215,10 @@ class DetBenchPredict(nn.Module):
         # detections are not differentiable (top-k, NMS): the network always runs on the fused inference engine here, also
         # when the wrapped model was left in training mode or the caller did not enter torch.no_grad()
         with torch.no_grad():
-            return self._forward(x, img_info)
+            det = self._forward(x, img_info)
+            if self.calibrator is not None:
+                det = self.calibrator.apply(det, self.last_count)
+            return det
 
     def _forward(self, x, img_info):
         if tuple(x.shape[2:]) != tuple(self.anchors.image_size):

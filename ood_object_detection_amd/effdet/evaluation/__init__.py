@@ -5,3 +5,4 @@ from .coco_evaluator import CocoDetectionEvaluator  # noqa: F401
 from .lvis_evaluator import LvisDetectionEvaluator  # noqa: F401
 from .openimages_evaluator import (OpenImagesChallengeEvaluator, OpenImagesDetectionEvaluator,  # noqa: F401
                                    WeightedPascalDetectionEvaluator)
+from .calibration_evaluator import CalibrationEvaluator  # noqa: F401

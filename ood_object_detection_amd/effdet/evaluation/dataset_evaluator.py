@@ -158,13 +158,16 @@ class DatasetDetectionEvaluator(SingleImageAPI):
                 raise ValueError('gt_difficult must be [B, M]')
         flags = torch.empty(B, max_det, dtype=torch.int32, device=dev)
         kept = torch.empty(2 * B, dtype=torch.int32, device=dev)
-        st = self._st()
-        _lib.check(self.lib.effdet_eval_match_multi(st, det.data_ptr(), count.data_ptr(), gt_boxes.data_ptr(), gt_cls.data_ptr(),
-                                                    gt_difficult.data_ptr() if gt_difficult is not None else None, B, max_det, M,
-                                                    self._num_classes, self._thr, len(self._thresholds), flags.data_ptr(),
-                                                    kept.data_ptr(), self._gt_count.data_ptr(), self._gt_imgs.data_ptr(),
-                                                    self._correct.data_ptr()), 'effdet_eval_match_multi')
+        self._launch_match(det, count, gt_boxes, gt_cls, gt_difficult.data_ptr() if gt_difficult is not None else None, B, max_det, M,
+                           flags, kept)
         return det, flags, kept, gt_boxes, gt_cls
+
+    def _launch_match(self, det, count, gt_boxes, gt_cls, gt_difficult_ptr, B, max_det, M, flags, kept):
+        """the matching launch itself on prepared device tensors (a subclass with its own entry point overrides this)"""
+        _lib.check(self.lib.effdet_eval_match_multi(self._st(), det.data_ptr(), count.data_ptr(), gt_boxes.data_ptr(), gt_cls.data_ptr(),
+                                                    gt_difficult_ptr, B, max_det, M, self._num_classes, self._thr,
+                                                    len(self._thresholds), flags.data_ptr(), kept.data_ptr(), self._gt_count.data_ptr(),
+                                                    self._gt_imgs.data_ptr(), self._correct.data_ptr()), 'effdet_eval_match_multi')
 
     def enqueue(self):
         """Sort + metrics into the result block on the device; no host synchronisation."""

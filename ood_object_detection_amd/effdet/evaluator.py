@@ -23,10 +23,11 @@ from .distributed import all_gather_container
 from .evaluation import (CocoDetectionEvaluator, LvisDetectionEvaluator, ObjectDetectionEvaluator, OpenImagesDetectionEvaluator,
                          PascalDetectionEvaluator)
 from .evaluation import OpenImagesChallengeEvaluator as OpenImagesChallengeDetectionEvaluator
+from .evaluation import CalibrationEvaluator as CalibrationDetectionEvaluator
 
 _logger = logging.getLogger(__name__)
 
-__all__ = ['CocoEvaluator', 'LvisEvaluator', 'PascalEvaluator', 'OpenImagesEvaluator', 'OpenImagesChallengeEvaluator', 'create_evaluator',
+__all__ = ['CocoEvaluator', 'LvisEvaluator', 'PascalEvaluator', 'OpenImagesEvaluator', 'OpenImagesChallengeEvaluator', 'CalibrationEvaluator', 'create_evaluator',
            'coco_ground_truth', 'lvis_ground_truth']
 
 
@@ -407,8 +408,49 @@ class OpenImagesChallengeEvaluator(OpenImagesEvaluator):
         self._evaluator.add_batch(det, count, gt[0], gt[1], gt_group_of=gt[2], labeled_cls=gt[3])
 
 
+class CalibrationEvaluator(TfmEvaluator):
+    """Calibration of the detection score on `effdet.evaluation.CalibrationEvaluator` (csrc/calibration_eval.hip): D-ECE, MCE, ACE,
+    classwise ECE, LaECE, Brier and NLL under the PASCAL matching; `evaluate()` returns the D-ECE at the first threshold.
+    `parser.get_ann_info(i)` may carry `difficult` [n] bool beside bbox and cls (matches with such boxes are ignored); `bins`,
+    `score_threshold`, `iou_thresholds` and `capacity` go to the device evaluator."""
+
+    def __init__(self, dataset, distributed=False, pred_yxyx=False, **kw):
+        super().__init__(dataset, distributed=distributed, pred_yxyx=pred_yxyx, evaluator_cls=CalibrationDetectionEvaluator, **kw)
+
+    @property
+    def device_evaluator(self):
+        """the `effdet.evaluation.CalibrationEvaluator` underneath (built at first use): what `DetectionCalibrator.fit` reads.
+        `evaluate()` clears it, so a calibrator is fitted before `evaluate()` is called."""
+        return self._evaluator
+
+    def _ground_truth_tables(self):
+        parser = self._dataset
+        gts = [parser.get_ann_info(i) for i in range(len(parser.img_ids))]
+        for gt in gts:
+            if 'group_of' in gt and np.asarray(gt['group_of']).any():
+                raise NotImplementedError('group-of ground truth is not built for this evaluator')
+        M = max([len(np.asarray(gt['cls']).reshape(-1)) for gt in gts] + [1])
+        boxes, cls = torch.zeros(len(gts), M, 4), torch.full((len(gts), M), -1, dtype=torch.int64)
+        difficult = torch.zeros(len(gts), M, dtype=torch.uint8)
+        for i, gt in enumerate(gts):
+            c = torch.as_tensor(np.asarray(gt['cls']), dtype=torch.int64).reshape(-1)
+            boxes[i, :c.numel()] = torch.as_tensor(np.asarray(gt['bbox']), dtype=torch.float32).reshape(-1, 4)
+            cls[i, :c.numel()] = c
+            if 'difficult' in gt and np.asarray(gt['difficult']).size:
+                d = torch.as_tensor(np.asarray(gt['difficult']).astype(np.uint8)).reshape(-1)
+                if d.numel() != c.numel():
+                    raise ValueError('difficult: one flag per ground-truth box')
+                difficult[i, :c.numel()] = d
+        return boxes, cls, difficult
+
+    def _add(self, det, count, gt):
+        self._evaluator.add_batch(det, count, gt[0], gt[1], gt_difficult=gt[2])
+
+
 def create_evaluator(name, dataset, distributed=False, pred_yxyx=False, **kw):
-    if 'coco' in name:
+    if 'calibration' in name:
+        return CalibrationEvaluator(dataset, distributed=distributed, pred_yxyx=pred_yxyx, **kw)
+    elif 'coco' in name:
         return CocoEvaluator(dataset, distributed=distributed, pred_yxyx=pred_yxyx, **kw)
     elif 'openimages' in name:
         if 'challenge' in name:
