@@ -34,6 +34,7 @@
 // synchronises with the host or allocates, so all of them can be captured in a graph.
 #include "common.h"
 #include "feature_rows.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -41,7 +42,6 @@ constexpr int AS_MAX_CLASSES = 1024;
 constexpr int AS_WAVES = 4;
 constexpr int AS_CELLS = 16;                                     // cells of a score_cells workgroup
 constexpr int AS_CHUNKS = 256;                                   // row chunks of the fit partials
-constexpr int AS_NONE = 0x7FFFFFFF;
 enum { AS_M_NONE = 0, AS_M_REACT, AS_M_ASH_P, AS_M_ASH_B, AS_M_ASH_S, AS_M_SCALE, AS_METHODS };
 
 struct AsLevels { FoLevels L; int h[FO_MAX_LEVELS], w[FO_MAX_LEVELS]; };
@@ -58,11 +58,6 @@ struct AsArgs {
 
 DEV float as_nan() { return __uint_as_float(0x7FC00000u); }
 DEV bool as_finite(float v) { return v - v == 0.f; }
-DEV int as_wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
 // the ordered key of a value, -0 as +0
 DEV unsigned as_key(float v) { return fo_key(v == 0.f ? 0u : __float_as_uint(v)); }
 
@@ -100,40 +95,6 @@ template <int NV> DEV bool as_dw(const AsLevels& T, const float* taps, int F, un
     return __ballot(bad) == 0ull;
 }
 
-// bit i of the result: channel lane + 64 i is among the k largest d (by value; equal values: the lower channel first)
-template <int NV> DEV unsigned as_top(const float (&d)[NV], int F, int k, int lane) {
-    unsigned all = 0;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) all |= (lane + 64 * i < F ? 1u : 0u) << i;
-    if (k >= F) return all;
-    unsigned key[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) key[i] = as_key(d[i]);
-    unsigned tau = 0;                                           // the largest t with at least k keys >= t: the k-th largest key
-    for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = tau | (1u << bit);
-        unsigned n = 0;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) n += fo_popc(__ballot(((all >> i) & 1u) && key[i] >= cand));
-        if (n >= (unsigned)k) tau = cand;
-    }
-    unsigned above = 0;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) above += fo_popc(__ballot(((all >> i) & 1u) && key[i] > tau));
-    const unsigned need = (unsigned)k - above;                  // of the keys equal to tau, in channel order
-    const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned sel = 0, run = 0;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const bool live = (all >> i) & 1u, tie = live && key[i] == tau;
-        const unsigned long long bal = __ballot(tie);
-        const unsigned rank = run + fo_popc(bal & below);
-        run += fo_popc(bal);
-        if (live && (key[i] > tau || (tie && rank < need))) sel |= 1u << i;
-    }
-    return sel;
-}
-
 // d -> x' (zero beyond F)
 template <int NV> DEV void as_shape(const AsArgs& a, const float (&d)[NV], int lane, float (&x)[NV]) {
     const int F = a.F, method = a.method;
@@ -143,7 +104,10 @@ template <int NV> DEV void as_shape(const AsArgs& a, const float (&d)[NV], int l
         for (int i = 0; i < NV; ++i) x[i] = lane + 64 * i < F ? (method == AS_M_REACT ? fminf(d[i], c) : d[i]) : 0.f;
         return;
     }
-    const unsigned kept = as_top<NV>(d, F, a.k, lane);
+    unsigned key[NV];                                           // the k largest d by value, equal values: the lower channel first
+#pragma unroll
+    for (int i = 0; i < NV; ++i) key[i] = as_key(d[i]);
+    const unsigned kept = wr_top<NV>(key, F, a.k, lane);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -196,22 +160,9 @@ template <int NC> DEV void as_logits(const float* x, const float* W, const float
 
 // max u + log sum exp(u - max u) of u = z / T, max z and its lowest argmax
 template <int NC> DEV float as_lse(const float (&z)[NC], int C, float T, int lane, float* maxz, int* kstar) {
-    float mz = -__builtin_inff();
-#pragma unroll
-    for (int m = 0; m < NC; ++m)
-        if (lane + 64 * m < C) mz = fmaxf(mz, z[m]);
-    mz = wave_reduce_max(mz);
-    int ks = AS_NONE;
-#pragma unroll
-    for (int m = NC - 1; m >= 0; --m)
-        if (lane + 64 * m < C && z[m] == mz) ks = lane + 64 * m;
-    ks = as_wave_min(ks);
-    const float mu = mz / T;                                    // = max u: the division is monotone
-    float s = 0.f;
-#pragma unroll
-    for (int m = 0; m < NC; ++m) s += lane + 64 * m < C ? expf(z[m] / T - mu) : 0.f;
-    s = wave_reduce_sum(s);
-    *maxz = mz; *kstar = ks;
+    float mu, s;
+    *maxz = wr_argmax<NC>(z, C, lane, kstar);
+    wr_lse<NC>(z, C, T, *maxz, lane, &mu, &s);
     return mu + logf(s);
 }
 
@@ -298,7 +249,7 @@ template <int NT> DEV void as_cells_lse(const float* xs, const float* W, const f
                                         float (&lse)[4], float (&bz)[4], int (&bc)[4]) {
     float m[4], s[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { m[q] = -__builtin_inff(); s[q] = 0.f; bz[q] = -__builtin_inff(); bc[q] = AS_NONE; }
+    for (int q = 0; q < 4; ++q) { m[q] = -__builtin_inff(); s[q] = 0.f; bz[q] = -__builtin_inff(); bc[q] = WR_NONE; }
     as_tiles<NT>(xs, W, bias, Cp, r16, g, [&](int q, int c, float z) {
         if (c >= C) return;                                     // (the padding: bias -inf)
         const float u = z / T;
@@ -418,14 +369,6 @@ DEV bool cp_keep(const AsArgs& a, unsigned i) { return i < a.sel.total && a.flag
 DEV unsigned cp_begin(const AsArgs&) { return 0u; }
 DEV void cp_finish(const AsArgs& a, unsigned, unsigned total) { a.header[0] = fo_min(total, a.sel.total); }
 
-__global__ __launch_bounds__(256) void as_fit_write_kernel(AsArgs a) {
-    unsigned pos[FO_ITEMS];
-    const unsigned kept = fo_positions(a.counts, pos, [&](int, unsigned i) { return cp_keep(a, i); });
-#pragma unroll
-    for (int r = 0; r < FO_ITEMS; ++r)
-        if ((kept & (1u << r)) && pos[r] < a.sel.total) a.list[pos[r]] = fo_entry(r);
-}
-
 // workgroup s: partial[s][j] = sum of d_j over the rows of chunk s of the compacted list
 template <int NT>
 __global__ __launch_bounds__(AS_WAVES * 64) void as_fit_sum_kernel(AsArgs a) {
@@ -473,15 +416,14 @@ struct AsLayout { long long flag, list, counts, header, partial, bytes; unsigned
 
 bool as_layout(long long rows, int F, AsLayout* L) {
     if (rows < 1 || rows > FO_MAX_ROWS || !fo_width_ok(F)) return false;
-    const auto up = [](long long v) { return (v + 255) & ~255ll; };
     L->nblocks = (unsigned)((rows + FO_TILE - 1) / FO_TILE);
-    long long at = 0;
-    L->flag = at; at += up(rows * 4);
-    L->list = at; at += up(rows * 4);
-    L->counts = at; at += up((long long)L->nblocks * 4);
-    L->header = at; at += 256;
-    L->partial = at; at += up((long long)AS_CHUNKS * F * 8);
-    L->bytes = at;
+    FoCarve ws;
+    L->flag = ws.take(rows * 4);
+    L->list = ws.take(rows * 4);
+    L->counts = ws.take((long long)L->nblocks * 4);
+    L->header = ws.take(256);
+    L->partial = ws.take((long long)AS_CHUNKS * F * 8);
+    L->bytes = ws.at;
     return true;
 }
 
@@ -533,11 +475,9 @@ extern "C" int effdet_act_shaping_score(void* stream, int dtype, int num_levels,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((a.sel.total + AS_WAVES - 1) / AS_WAVES), block(AS_WAVES * 64);
     fo_for_width(F, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        if (a.Cp <= 128) hipLaunchKernelGGL((as_score_kernel<NT, 2>), grid, block, 0, st, a);
-        else if (a.Cp <= 256) hipLaunchKernelGGL((as_score_kernel<NT, 4>), grid, block, 0, st, a);
-        else if (a.Cp <= 512) hipLaunchKernelGGL((as_score_kernel<NT, 8>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((as_score_kernel<NT, 16>), grid, block, 0, st, a);
+        wr_for_classes(a.Cp, [&](auto nc) {
+            hipLaunchKernelGGL((as_score_kernel<decltype(nt)::value, decltype(nc)::value>), grid, block, 0, st, a);
+        });
     });
     return effdet_check_launch();
 }
@@ -595,7 +535,7 @@ extern "C" int effdet_act_shaping_fit(void* stream, int dtype, int num_levels, c
     fo_for_width(F, [&](auto nt) { hipLaunchKernelGGL(as_fit_rows_kernel<decltype(nt)::value>, grid, block, 0, st, a); });
     hipLaunchKernelGGL(fo_count_kernel<AsArgs>, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(fo_base_kernel<AsArgs>, dim3(1), dim3(FO_THREADS), 0, st, a);
-    hipLaunchKernelGGL(as_fit_write_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_write_index_kernel<AsArgs>, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
     fo_for_width(F, [&](auto nt) { hipLaunchKernelGGL(as_fit_sum_kernel<decltype(nt)::value>, dim3(AS_CHUNKS), block, 0, st, a); });
     hipLaunchKernelGGL(as_fit_reduce_kernel, dim3(1), dim3(256), 0, st, a);
     return effdet_check_launch();

@@ -1,9 +1,9 @@
-// Workgroup reductions, integer helpers and the ordered compaction that the OOD and the evaluation units share (feature_ood.hip,
+// Workgroup reductions, integer helpers, the workspace carve and the ordered compaction that the OOD and the evaluation units share (feature_ood.hip,
 // feature_knn.hip, feature_subspace.hip, logit_ood.hip, act_shaping.hip, energy_reg.hip, outlier_synth.hip, ood_eval.hip, and through radix_sort.h,
 // eval_match.h and eval_sorted.h the evaluation units eval_scale.hip, coco_eval.hip, lvis_eval.hip).  The compaction: the kept entries of a [B, K] call
 // get consecutive positions in (b, j) order by three launches - kept entries per tile of 2048 (fo_count_kernel), the tiles' first
 // positions in one workgroup (fo_base_kernel), then ballot ranks inside a tile (fo_positions, called by the unit's own write
-// kernel).  No atomic decides a position.  A unit describes its compaction by a struct
+// kernel, or by fo_write_index_kernel where the list holds the entry index).  No atomic decides a position.  A unit describes its compaction by a struct
 // A with `unsigned* counts` ([nblocks]), `unsigned nblocks` and three overloads beside it:
 //   bool cp_keep(const A&, unsigned i)                          is entry i kept?  (false at i >= total)
 //   unsigned cp_begin(const A&)                                 the position of the first kept entry
@@ -124,5 +124,23 @@ template <typename Keep> DEV unsigned fo_positions(const unsigned* counts, unsig
     for (int r = 0; r < FO_ITEMS; ++r) pos[r] += first;
     return kept;
 }
+
+// The write kernel of a unit whose compacted list holds the entry index itself (logit_ood.hip, act_shaping.hip): A has beside
+// `counts` an `unsigned* list` of `sel.total` places.  The three overloads stay the unit's own: a template of them here would
+// stand in for an overload that a unit forgot.
+template <typename A> __global__ __launch_bounds__(256) void fo_write_index_kernel(A a) {
+    unsigned pos[FO_ITEMS];
+    const unsigned kept = fo_positions(a.counts, pos, [&](int, unsigned i) { return cp_keep(a, i); });
+#pragma unroll
+    for (int r = 0; r < FO_ITEMS; ++r)
+        if ((kept & (1u << r)) && pos[r] < a.sel.total) a.list[pos[r]] = fo_entry(r);
+}
+
+// ---- host ----
+// Carves a workspace: take(bytes) is the offset of the next region, every region a multiple of 256 bytes; `at` the bytes taken so far
+struct FoCarve {
+    long long at = 0;
+    long long take(long long bytes) { const long long o = at; at += (bytes + 255) & ~255ll; return o; }
+};
 
 }  // namespace

@@ -29,6 +29,7 @@
 // extent before a pointer is formed, every store index before the store; no call synchronises with the host or allocates.
 #include "common.h"
 #include "feature_rows.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -50,15 +51,10 @@ struct ErArgs {
     float* loss; double* stats; float* energy; void* grad; float* grad_phi;
 };
 
-DEV float er_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 DEV float er_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 DEV const char* er_rowp(const ErArgs& a, unsigned i) {
     return reinterpret_cast<const char*>(a.z) + (long long)i * a.C * (a.bf16 ? 2 : 4);
-}
-template <int NC> DEV void er_load(const ErArgs& a, const char* p, int lane, float (&z)[NC]) {
-#pragma unroll
-    for (int k = 0; k < NC; ++k) z[k] = lane + 64 * k < a.C ? fo_ld(p, lane + 64 * k, a.bf16) : 0.f;
 }
 // float32 -> bfloat16 bits, round to nearest even (a NaN becomes the quiet NaN 0x7FC0, as torch's conversion writes it)
 DEV unsigned short er_bf16(float v) {
@@ -80,8 +76,8 @@ __global__ __launch_bounds__(ER_WAVES * 64) void er_rows_kernel(ErArgs a) {
         float E = 0.f, m = 0.f, s = 0.f, dE = 0.f;
         if (side) {
             float z[NC];
-            er_load<NC>(a, er_rowp(a, i), lane, z);
-            float mz = -__builtin_inff();
+            wr_load<NC>(er_rowp(a, i), C, a.bf16, lane, z);
+            float mz = -__builtin_inff();                       // the maximum and the NaN test in one pass over the registers
             bool bad = false;
 #pragma unroll
             for (int k = 0; k < NC; ++k)
@@ -91,17 +87,13 @@ __global__ __launch_bounds__(ER_WAVES * 64) void er_rows_kernel(ErArgs a) {
             if (side == 2 && a.use_min && (nan || !(mz >= a.min_max))) side = 0;
             if (side) {                                         // (uniform over the wave)
                 if (a.kind == ER_LSE) {
-                    m = mz / a.T;
-                    float t = 0.f;
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) t += lane + 64 * k < C ? expf(z[k] / a.T - m) : 0.f;
-                    s = wave_reduce_sum(t);
+                    wr_lse<NC>(z, C, a.T, mz, lane, &m, &s);
                     const float lse = m + logf(s);
                     E = -(a.T * lse);
                 } else {
                     float t = 0.f;
 #pragma unroll
-                    for (int k = 0; k < NC; ++k) t += lane + 64 * k < C ? er_softplus(z[k]) : 0.f;
+                    for (int k = 0; k < NC; ++k) t += lane + 64 * k < C ? wr_softplus(z[k]) : 0.f;
                     E = -wave_reduce_sum(t);
                 }
                 if (a.form == ER_HINGE) {
@@ -208,7 +200,7 @@ __global__ __launch_bounds__(ER_WAVES * 64) void er_grad_kernel(ErArgs a) {
             for (int k = 0; k < NC; ++k) out[k] = 0.f;
         } else {
             float z[NC];
-            er_load<NC>(a, er_rowp(a, i), lane, z);
+            wr_load<NC>(er_rowp(a, i), C, a.bf16, lane, z);
             if (a.kind == ER_LSE) {
                 const float m = a.m[i], s = a.s[i];
 #pragma unroll
@@ -235,17 +227,16 @@ struct ErLayout { long long side, E, m, s, dE, partial, coef, bytes; unsigned nb
 
 bool er_layout(long long rows, ErLayout* L) {
     if (rows < 1 || rows > FO_MAX_ROWS) return false;
-    const auto up = [](long long v) { return (v + 255) & ~255ll; };
     L->nblocks = (unsigned)((rows + FO_TILE - 1) / FO_TILE);
-    long long at = 0;
-    L->side = at; at += up(rows);
-    L->E = at; at += up(rows * 4);
-    L->m = at; at += up(rows * 4);
-    L->s = at; at += up(rows * 4);
-    L->dE = at; at += up(rows * 4);
-    L->partial = at; at += up((long long)L->nblocks * ER_TERMS * 8);
-    L->coef = at; at += 256;
-    L->bytes = at;
+    FoCarve ws;
+    L->side = ws.take(rows);
+    L->E = ws.take(rows * 4);
+    L->m = ws.take(rows * 4);
+    L->s = ws.take(rows * 4);
+    L->dE = ws.take(rows * 4);
+    L->partial = ws.take((long long)L->nblocks * ER_TERMS * 8);
+    L->coef = ws.take(256);
+    L->bytes = ws.at;
     return true;
 }
 
@@ -289,17 +280,9 @@ extern "C" int effdet_energy_reg(void* stream, int dtype, const void* logits, co
     a.loss = loss; a.stats = stats; a.energy = energy; a.grad = grad_logits; a.grad_phi = grad_phi;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((a.total + ER_ROWS - 1) / ER_ROWS), block(ER_WAVES * 64);
-    if (C <= 128) hipLaunchKernelGGL(er_rows_kernel<2>, grid, block, 0, st, a);
-    else if (C <= 256) hipLaunchKernelGGL(er_rows_kernel<4>, grid, block, 0, st, a);
-    else if (C <= 512) hipLaunchKernelGGL(er_rows_kernel<8>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(er_rows_kernel<16>, grid, block, 0, st, a);
+    wr_for_classes(C, [&](auto nc) { hipLaunchKernelGGL(er_rows_kernel<decltype(nc)::value>, grid, block, 0, st, a); });
     hipLaunchKernelGGL(er_partial_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(er_final_kernel, dim3(1), dim3(FO_THREADS), 0, st, a);
-    if (grad_logits) {
-        if (C <= 128) hipLaunchKernelGGL(er_grad_kernel<2>, grid, block, 0, st, a);
-        else if (C <= 256) hipLaunchKernelGGL(er_grad_kernel<4>, grid, block, 0, st, a);
-        else if (C <= 512) hipLaunchKernelGGL(er_grad_kernel<8>, grid, block, 0, st, a);
-        else hipLaunchKernelGGL(er_grad_kernel<16>, grid, block, 0, st, a);
-    }
+    if (grad_logits) wr_for_classes(C, [&](auto nc) { hipLaunchKernelGGL(er_grad_kernel<decltype(nc)::value>, grid, block, 0, st, a); });
     return effdet_check_launch();
 }

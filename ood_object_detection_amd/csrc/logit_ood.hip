@@ -26,6 +26,7 @@
 // synchronises with the host or allocates, so all of them can be captured in a graph.
 #include "common.h"
 #include "feature_rows.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -34,7 +35,6 @@ constexpr int LO_ROWS = 16;                                      // rows of a wo
 constexpr int LO_WAVES = 4;
 constexpr int LO_MAX_CHUNKS = 16;                                // row chunks of the fit partials
 constexpr long long LO_PARTIAL_DOUBLES = 1ll << 18;              // the partials of all chunks stay below this many float64
-constexpr int LO_NONE = 0x7FFFFFFF;
 
 struct LoArgs {
     const void* z; int bf16; long long bstride, astride;        // the logits: row (b, n) at b * bstride + n * astride (elements)
@@ -57,31 +57,12 @@ DEV const char* lo_rowp(const LoArgs& a, unsigned i) {
     return reinterpret_cast<const char*>(a.z) + ((long long)b * a.bstride + an * a.astride) * (a.bf16 ? 2 : 4);
 }
 
-DEV int lo_wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
-// the pattern of a float as an unsigned that orders like the float
-DEV unsigned lo_key(float v) {
-    const unsigned b = (unsigned)__float_as_int(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 template <int NC> struct LoSoft { float m, s, lse; int kstar; float e[NC], l[NC], p[NC]; };
 
 // the softmax of the wave's row u (lane t: classes t + 64 i); e, l, p are 0 beyond C
 template <int NC> DEV void lo_softmax(const float (&u)[NC], int C, int lane, LoSoft<NC>& r) {
-    float m = -__builtin_inff();
-#pragma unroll
-    for (int i = 0; i < NC; ++i)
-        if (lane + 64 * i < C) m = fmaxf(m, u[i]);
-    m = wave_reduce_max(m);
-    int ks = LO_NONE;
-#pragma unroll
-    for (int i = NC - 1; i >= 0; --i)
-        if (lane + 64 * i < C && u[i] == m) ks = lane + 64 * i;
-    ks = lo_wave_min(ks);
+    int ks;
+    const float m = wr_argmax<NC>(u, C, lane, &ks);
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
@@ -105,51 +86,6 @@ template <int NC> DEV float lo_neg_entropy(const LoSoft<NC>& r) {
     for (int i = 0; i < NC; ++i) t += r.p[i] * r.l[i];           // (0 * 0 beyond C)
     return wave_reduce_sum(t);
 }
-
-template <int NC> DEV void lo_load(const LoArgs& a, const char* p, int lane, float (&z)[NC]) {
-#pragma unroll
-    for (int i = 0; i < NC; ++i) z[i] = lane + 64 * i < a.C ? fo_ld(p, lane + 64 * i, a.bf16) : 0.f;
-}
-
-// bit i of the result: class lane + 64 i is among the top_m largest u (equal values: the lower class first)
-template <int NC> DEV unsigned lo_top(const float (&u)[NC], int C, int top_m, int lane) {
-    unsigned all = 0;
-#pragma unroll
-    for (int i = 0; i < NC; ++i) all |= (lane + 64 * i < C ? 1u : 0u) << i;
-    if (top_m >= C) return all;
-    unsigned key[NC];
-#pragma unroll
-    for (int i = 0; i < NC; ++i) key[i] = lo_key(u[i]);
-    unsigned tau = 0;                                           // the largest t with at least top_m keys >= t: the top_m-th largest key
-    for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = tau | (1u << bit);
-        unsigned n = 0;
-#pragma unroll
-        for (int i = 0; i < NC; ++i)
-            if (64 * i < C) n += fo_popc(__ballot(((all >> i) & 1u) && key[i] >= cand));
-        if (n >= (unsigned)top_m) tau = cand;
-    }
-    unsigned above = 0;
-#pragma unroll
-    for (int i = 0; i < NC; ++i)
-        if (64 * i < C) above += fo_popc(__ballot(((all >> i) & 1u) && key[i] > tau));
-    const unsigned need = (unsigned)top_m - above;              // of the keys equal to tau, in class order
-    const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned sel = 0, run = 0;
-#pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        if (64 * i < C) {
-            const bool live = (all >> i) & 1u, tie = live && key[i] == tau;
-            const unsigned long long bal = __ballot(tie);
-            const unsigned rank = run + fo_popc(bal & below);
-            run += fo_popc(bal);
-            if (live && (key[i] > tau || (tie && rank < need))) sel |= 1u << i;
-        }
-    }
-    return sel;
-}
-
-DEV float lo_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
 DEV bool lo_less(float v, int c, float bv, int bc) { return v < bv || (v == bv && c < bc); }
 
@@ -181,7 +117,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_score_kernel(LoArgs a) {
             continue;
         }
         float z[NC];
-        lo_load<NC>(a, p, lane, z);
+        wr_load<NC>(p, C, a.bf16, lane, z);
         LoSoft<NC> s;
         lo_softmax<NC>(z, C, lane, s);                          // T = 1
         const float maxz = s.m;
@@ -189,7 +125,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_score_kernel(LoArgs a) {
         if (lane == 0) lse1s[r] = s.lse;
         float je = 0.f;
 #pragma unroll
-        for (int k = 0; k < NC; ++k) je += lane + 64 * k < C ? lo_softplus(z[k]) : 0.f;
+        for (int k = 0; k < NC; ++k) je += lane + 64 * k < C ? wr_softplus(z[k]) : 0.f;
         je = wave_reduce_sum(je);
         if (fitted) {
 #pragma unroll
@@ -210,7 +146,10 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_score_kernel(LoArgs a) {
         for (int k = 0; k < NC; ++k) so += lane + 64 * k == ks ? 0.f : s.e[k];
         so = wave_reduce_sum(so);
         const float qs = logf(so) - logf(s.s);
-        const unsigned sel = lo_top<NC>(z, C, a.top_m, lane);
+        unsigned key[NC];                                       // the top_m largest u, equal values: the lower class first
+#pragma unroll
+        for (int k = 0; k < NC; ++k) key[k] = fo_key(__float_as_uint(z[k]));
+        const unsigned sel = wr_top<NC>(key, C, a.top_m, lane);
         float ge = 0.f;
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
@@ -275,7 +214,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_score_kernel(LoArgs a) {
     // a lane holds kl of class 16 tile + (lane & 15) for rows 4 (lane >> 4) + 0 .. 3
     float bv[4]; int bc[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { bv[q] = __builtin_inff(); bc[q] = LO_NONE; }
+    for (int q = 0; q < 4; ++q) { bv[q] = __builtin_inff(); bc[q] = WR_NONE; }
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
         const int tile = wave + LO_WAVES * t;
@@ -310,7 +249,7 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_score_kernel(LoArgs a) {
             for (int w = 1; w < LO_WAVES; ++w)
                 if (lo_less(bestv[w][tid], bestc[w][tid], v, c)) { v = bestv[w][tid]; c = bestc[w][tid]; }
             a.kl[i] = -v;
-            a.kl_class[i] = c == LO_NONE ? -1 : (long long)c;
+            a.kl_class[i] = c == WR_NONE ? -1 : (long long)c;
         }
     }
 }
@@ -329,21 +268,15 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_fit_rows_kernel(LoArgs a) {
         int cls = -1; float mz = 0.f, lse = 0.f;
         if (p) {
             float z[NC];
-            lo_load<NC>(a, p, lane, z);
+            wr_load<NC>(p, C, a.bf16, lane, z);
             LoSoft<NC> s;
             lo_softmax<NC>(z, C, lane, s);
             mz = s.m; lse = s.lse;
             int ks = s.kstar;
             if (a.T != 1.f) {                                   // the predicted class is the argmax of u = z / T, as in the score
-                float m = -__builtin_inff();
 #pragma unroll
-                for (int k = 0; k < NC; ++k) { z[k] = z[k] / a.T; if (lane + 64 * k < C) m = fmaxf(m, z[k]); }
-                m = wave_reduce_max(m);
-                ks = LO_NONE;
-#pragma unroll
-                for (int k = NC - 1; k >= 0; --k)
-                    if (lane + 64 * k < C && z[k] == m) ks = lane + 64 * k;
-                ks = lo_wave_min(ks);
+                for (int k = 0; k < NC; ++k) z[k] = z[k] / a.T;
+                wr_argmax<NC>(z, C, lane, &ks);
             }
             if (ks >= 0 && ks < C && (!a.use_min || mz >= a.min_max)) cls = ks;
         }
@@ -354,14 +287,6 @@ __global__ __launch_bounds__(LO_WAVES * 64) void lo_fit_rows_kernel(LoArgs a) {
 DEV bool cp_keep(const LoArgs& a, unsigned i) { return i < a.sel.total && a.cls[i] >= 0; }
 DEV unsigned cp_begin(const LoArgs&) { return 0u; }
 DEV void cp_finish(const LoArgs& a, unsigned, unsigned total) { a.header[0] = fo_min(total, a.sel.total); }
-
-__global__ __launch_bounds__(256) void lo_fit_write_kernel(LoArgs a) {
-    unsigned pos[FO_ITEMS];
-    const unsigned kept = fo_positions(a.counts, pos, [&](int, unsigned i) { return cp_keep(a, i); });
-#pragma unroll
-    for (int r = 0; r < FO_ITEMS; ++r)
-        if ((kept & (1u << r)) && pos[r] < a.sel.total) a.list[pos[r]] = fo_entry(r);
-}
 
 // blockIdx.x = class c, blockIdx.y = chunk s of the compacted list: partial[s][c] = {sum p [C], sum max z, sum (max z)^2, n} over
 // the chunk's rows of class c, in list order
@@ -433,18 +358,17 @@ int lo_chunks(int C) {
 
 bool lo_layout(long long rows, int C, LoLayout* L) {
     if (rows < 1 || rows > FO_MAX_ROWS || C < 1 || C > LO_MAX_CLASSES) return false;
-    const auto up = [](long long v) { return (v + 255) & ~255ll; };
     L->nblocks = (unsigned)((rows + FO_TILE - 1) / FO_TILE);
     L->S = lo_chunks(C);
-    long long at = 0;
-    L->cls = at; at += up(rows * 4);
-    L->mz = at; at += up(rows * 4);
-    L->lse = at; at += up(rows * 4);
-    L->list = at; at += up(rows * 4);
-    L->counts = at; at += up((long long)L->nblocks * 4);
-    L->header = at; at += 256;
-    L->partial = at; at += up((long long)L->S * C * (C + 3) * 8);
-    L->bytes = at;
+    FoCarve ws;
+    L->cls = ws.take(rows * 4);
+    L->mz = ws.take(rows * 4);
+    L->lse = ws.take(rows * 4);
+    L->list = ws.take(rows * 4);
+    L->counts = ws.take((long long)L->nblocks * 4);
+    L->header = ws.take(256);
+    L->partial = ws.take((long long)L->S * C * (C + 3) * 8);
+    L->bytes = ws.at;
     return true;
 }
 
@@ -490,10 +414,10 @@ extern "C" int effdet_logit_ood_score(void* stream, int dtype, const void* logit
     a.kl = kl_matching; a.kl_class = kl_class; a.sml = standardized;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((a.sel.total + LO_ROWS - 1) / LO_ROWS), block(LO_WAVES * 64);
-    if (a.Cp <= 128) hipLaunchKernelGGL((lo_score_kernel<2, 128, 2>), grid, block, 0, st, a);
-    else if (a.Cp <= 256) hipLaunchKernelGGL((lo_score_kernel<4, 256, 4>), grid, block, 0, st, a);
-    else if (a.Cp <= 512) hipLaunchKernelGGL((lo_score_kernel<8, 512, 8>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((lo_score_kernel<16, 512, 16>), grid, block, 0, st, a);
+    wr_for_classes(a.Cp, [&](auto nc) {                         // p passes through LDS in K-chunks of at most 512 classes
+        constexpr int NC = decltype(nc)::value, KC = 64 * NC < 512 ? 64 * NC : 512;
+        hipLaunchKernelGGL((lo_score_kernel<NC, KC, NC>), grid, block, 0, st, a);
+    });
     return effdet_check_launch();
 }
 
@@ -518,13 +442,10 @@ extern "C" int effdet_logit_ood_fit(void* stream, int dtype, const void* logits,
     a.n_c = n_c; a.P_c = P_c; a.a_c = a_c; a.b_c = b_c;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((a.sel.total + LO_ROWS - 1) / LO_ROWS), block(LO_WAVES * 64);
-    if (a.Cp <= 128) hipLaunchKernelGGL(lo_fit_rows_kernel<2>, grid, block, 0, st, a);
-    else if (a.Cp <= 256) hipLaunchKernelGGL(lo_fit_rows_kernel<4>, grid, block, 0, st, a);
-    else if (a.Cp <= 512) hipLaunchKernelGGL(lo_fit_rows_kernel<8>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(lo_fit_rows_kernel<16>, grid, block, 0, st, a);
+    wr_for_classes(a.Cp, [&](auto nc) { hipLaunchKernelGGL(lo_fit_rows_kernel<decltype(nc)::value>, grid, block, 0, st, a); });
     hipLaunchKernelGGL(fo_count_kernel<LoArgs>, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(fo_base_kernel<LoArgs>, dim3(1), dim3(FO_THREADS), 0, st, a);
-    hipLaunchKernelGGL(lo_fit_write_kernel, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
+    hipLaunchKernelGGL(fo_write_index_kernel<LoArgs>, dim3(a.nblocks), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(lo_fit_sum_kernel, dim3(C, a.S), dim3(FO_THREADS), 0, st, a);
     hipLaunchKernelGGL(lo_fit_reduce_kernel, dim3(C), dim3(FO_THREADS), 0, st, a);
     return effdet_check_launch();

@@ -168,18 +168,17 @@ struct OsLayout { long long r2, ka, ia, kb, ib, hist, totals, bytes; unsigned ti
 
 bool os_layout(int n, long long S, OsLayout* L) {
     if (n < 1 || n > OS_MAX_CLASSES || S < 1 || S > OS_MAX_CANDIDATES || (long long)n * S > OS_MAX_ENTRIES) return false;
-    const auto up = [](long long v) { return (v + 255) & ~255ll; };
-    const long long e = up((long long)n * S * 4);
+    const long long e = (long long)n * S * 4;
     L->tiles = (unsigned)((S + RS_TILE - 1) / RS_TILE);
-    long long at = 0;
-    L->r2 = at; at += e;
-    L->ka = at; at += e;
-    L->ia = at; at += e;
-    L->kb = at; at += e;
-    L->ib = at; at += e;
-    L->hist = at; at += up((long long)n * 256 * L->tiles * 4);
-    L->totals = at; at += up((long long)n * 256 * 4);
-    L->bytes = at;
+    FoCarve ws;
+    L->r2 = ws.take(e);
+    L->ka = ws.take(e);
+    L->ia = ws.take(e);
+    L->kb = ws.take(e);
+    L->ib = ws.take(e);
+    L->hist = ws.take((long long)n * 256 * L->tiles * 4);
+    L->totals = ws.take((long long)n * 256 * 4);
+    L->bytes = ws.at;
     return true;
 }
 

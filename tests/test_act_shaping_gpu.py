@@ -280,6 +280,54 @@ def test_bf16_tower_against_its_widening():
     assert _eq(s.score(c['tower'], an, rows=True), s.score(wide, an, rows=True)) and _eq(s.score_anchors(c['tower']), s.score_anchors(wide))
 
 
+def test_kept_set_with_equal_values_at_the_cut():
+    """The in-wave select of the k largest (wave_rows.h) where equal values meet the cut.  One 1 x 1 level, A = 1 and taps that are 1 on
+    the centre and -0 elsewhere, so that d IS the tower value, its sign of zero included (-0 * 0 = -0, -0 + -0 = -0, -0 + +0 = +0), on
+    the device and in the restatement alike; F = 88: two registers a lane, 24 channels live in the second.  Rows: four equal values
+    at channels 3, 63, 64 and 87 below ten larger ones (positive, and once more negative), -0 at channel 40 and +0 at channel 80 below
+    eleven larger ones, 88 equal values, 88 distinct ones.  k = 12, 13: inside the group (and the pair); 14: its end; 15: one past; 1 and F - 1."""
+    F, C, GROUP = 88, 2, [3, 63, 64, 87]
+    rs = np.random.RandomState(88)
+
+    def row(fixed, larger, top, rest):
+        """`fixed`: channel -> value; of the other channels, shuffled, `larger` get distinct values above `top`, the rest below `rest`"""
+        x = np.zeros(F, np.float32)
+        free = rs.permutation([j for j in range(F) if j not in fixed])
+        x[free[:larger]] = top + 0.125 * (1 + np.arange(larger))
+        x[free[larger:]] = rest - 0.03125 * (1 + np.arange(len(free) - larger))
+        for j, v in fixed.items():
+            x[j] = v
+        return x
+
+    x = np.stack([row({j: 1.0 for j in GROUP}, 10, 1.0, 1.0),           # the rest runs from 0.97 down to -1.3
+                  row({j: -0.25 for j in GROUP}, 10, -0.25, -0.25),
+                  row({40: -0.0, 80: 0.0}, 11, 0.0, 0.0),
+                  np.full(F, 0.5, np.float32),
+                  rs.normal(size=F).astype(np.float32)])
+    n = len(x)
+    taps = np.full((9, F), -0.0, np.float32)
+    taps[4] = 1.0
+    d = R.penultimate([x.reshape(n, 1, 1, F)], taps).reshape(n, F)
+    assert np.array_equal(d.view(np.uint32), x.view(np.uint32)) and np.signbit(d[2, 40]) and not np.signbit(d[2, 80])
+    W = rs.normal(size=(C, F)).astype(np.float32)
+    tower = _place([x.reshape(n, 1, 1, F)])
+    an = torch.zeros(n, 1, dtype=torch.int64, device=DEV)
+    for k, group, pair in ((1, [], []), (12, [3, 63], [40]), (13, [3, 63, 64], [40, 80]), (14, GROUP, [40, 80]), (15, GROUP, [40, 80]),
+                           (F - 1, GROUP, [40, 80])):
+        kept = R.kept_set(d, k)                                            # the restatement keeps what this test means it to keep
+        assert (kept.sum(1) == k).all() and np.array_equal(kept[3], np.arange(F) < k)
+        for r in (0, 1):
+            assert [j for j in GROUP if kept[r, j]] == group, (k, r)
+        assert [j for j in (40, 80) if kept[2, j]] == pair, k
+        p = 100.0 * (F - k) / F
+        assert R.k_of(F, p) == k
+        s = _S()(F, C, 1, method='ash_p', percentile=p, device=DEV).set_weights(taps, W, np.zeros(C, np.float32))
+        got = s.score(tower, an, rows=True)['rows'].cpu().numpy().reshape(n, F)
+        want = R.shape(d, 'ash_p', k=k, dtype=np.float32)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (k, np.argwhere(got.view(np.uint32) != want.view(np.uint32)))
+        assert np.array_equal(got != 0, kept & (d != 0))
+
+
 def test_graph_replay_of_add_score_and_score_anchors():
     c = _case(64, 17, 3)
     s = _scorer(c, 'react', gradnorm=True)

@@ -141,6 +141,32 @@ def test_entry_points_declared_bound_and_exported():
     assert 'mma_chunk(' in src                                                                   # the float32-input MFMA of common.h
 
 
+def test_wave_per_row_primitives_are_stated_once():
+    """what the units that walk a row with one wave share is wave_rows.h's; none of them keeps a copy of its own"""
+    from ood_object_detection_amd import _lib
+    mk = open(os.path.join(_lib.CSRC, 'Makefile')).read()
+    shared = open(os.path.join(_lib.CSRC, 'wave_rows.h')).read()
+    assert '#include "compact.h"' in shared
+    for text in ('DEV int wr_min(int', 'DEV unsigned wr_top(', 'DEV float wr_argmax(', 'DEV void wr_load(', 'DEV void wr_lse(',
+                 'DEV float wr_softplus(float', 'void wr_for_classes(int'):
+        assert shared.count(text) == 1, text
+    for unit in ('logit_ood', 'act_shaping', 'energy_reg'):
+        src = open(os.path.join(_lib.CSRC, unit + '.hip')).read()
+        assert '#include "wave_rows.h"' in src, unit
+        assert re.search(r'build/%s\.o:.*\bwave_rows\.h' % unit, mk), unit
+        assert 'cand = tau |' not in src and 'key[i] >= cand' not in src, unit                 # the 32-step top-k search
+        assert '__shfl_xor(v, o, 64); v = w < v' not in src and not re.search(r'DEV int \w+_min\(', src), unit     # the wave min
+        assert 'log1pf(expf(-fabsf(' not in src and not re.search(r'\w+_softplus\(float', src), unit              # softplus
+        assert not re.search(r'\bCp? <= 128\b', src) and 'wr_for_classes(' in src, unit          # the dispatch on the class count
+        assert not re.search(r'int \w+_NONE\b', src), unit
+        assert '_fit_write_kernel' not in src and 'const auto up' not in src, unit
+    for unit in ('logit_ood', 'act_shaping'):
+        src = open(os.path.join(_lib.CSRC, unit + '.hip')).read()
+        assert 'wr_top<' in src and 'fo_write_index_kernel<' in src, unit
+    assert open(os.path.join(_lib.CSRC, 'compact.h')).read().count('void fo_write_index_kernel(A a)') == 1
+    assert 'const auto up' not in open(os.path.join(_lib.CSRC, 'outlier_synth.hip')).read()
+
+
 def test_argument_refusals_before_any_launch():
     """every call below must return -22 from pure host code: nothing is launched"""
     from ood_object_detection_amd import _lib

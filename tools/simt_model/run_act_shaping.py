@@ -7,8 +7,6 @@ arithmetic, indexing and bounds (a guard region follows every buffer), not timin
     python3 tools/simt_model/run_act_shaping.py     needs g++ with C++20 (std::barrier); a thread per lane: a few minutes"""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -20,46 +18,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _act_shaping_ref as R  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+from _model import GUARD, build, guarded, ptr  # noqa: E402
 from ood_object_detection_amd.ood_shaping import METHODS, pack_head  # noqa: E402
 
-PRELUDE = ('#include "common.h"\n#include "effdet_hip.h"\n'
-           '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
-GUARD = 64
-CSRC = os.path.join(ROOT, 'ood_object_detection_amd', 'csrc')
 A = 3
-
-
-def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    shutil.copy(os.path.join(CSRC, 'feature_rows.h'), tmp)       # included by the unit
-    shutil.copy(os.path.join(CSRC, 'compact.h'), tmp)
-    src = open(os.path.join(CSRC, 'act_shaping.hip')).read()
-    with open(os.path.join(tmp, 'act_shaping.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'libact_shaping_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-Wno-unknown-pragmas',
-                    '-I', os.path.join(ROOT, 'include'), '-o', out, os.path.join(tmp, 'act_shaping.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if name.startswith('effdet_act_shaping_'):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data
 
 
 def arr(ctype, v):
     return (ctype * len(v))(*[int(x) for x in v])
-
-
-def guarded(shape, dtype, fill):
-    n = int(np.prod(shape))
-    whole = np.full(n + GUARD, fill, dtype)
-    return whole[:n].reshape(shape), whole
 
 
 def table(tower):
@@ -177,7 +143,7 @@ def run(lib, F, C, bf16):
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        lib = build(tmp)
+        lib = build(tmp, 'act_shaping', 'effdet_act_shaping_')
         assert lib.effdet_act_shaping_workspace_bytes(0, 64) == -22 and lib.effdet_act_shaping_workspace_bytes(4, 65) == -22
         for F, C, bf16 in ((64, 2, False), (88, 17, False), (64, 17, True)):
             run(lib, F, C, bf16)

@@ -11,8 +11,6 @@ region follows every buffer.  It checks arithmetic, indexing and bounds, not tim
 What the model adds to common.h for this unit: a fixed-size array in place of the matching kernel's dynamic LDS."""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -27,33 +25,16 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import _calibration_ref as R  # noqa: E402
 import _eval_openimages_ref as O  # noqa: E402
 import run_coco_eval as RC  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+import _model  # noqa: E402
+from _model import GUARD  # noqa: E402
 from ood_object_detection_amd.calibration import _start_state  # noqa: E402
 from ood_object_detection_amd.effdet.evaluation.calibration_evaluator import parse_calibration_result  # noqa: E402
 
-DYNAMIC_LDS = 'extern __shared__ int ca_lds[];'
-NAMES = [n for n in _lib.SIGNATURES if n.startswith('effdet_calibration_')]
-GUARD = RC.GUARD
 ptr, guarded = RC.ptr, RC.guarded
 
 
 def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for header in ('compact.h', 'radix_sort.h', 'eval_match.h', 'eval_sorted.h'):                            # included by the unit
-        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
-    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'calibration_eval.hip')).read()
-    assert src.count(DYNAMIC_LDS) == 1
-    src = src.replace(DYNAMIC_LDS, 'static int ca_lds[16384];')                                   # 64 KiB
-    with open(os.path.join(tmp, 'calibration_eval.cpp'), 'w') as f:
-        f.write(RC.PRELUDE + src)
-    out = os.path.join(tmp, 'libcalibration_eval_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-o', out,
-                    os.path.join(tmp, 'calibration_eval.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name in NAMES:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+    return _model.build(tmp, 'calibration_eval', 'effdet_calibration_', lds=('extern __shared__ int ca_lds[];', 'static int ca_lds[16384];'))   # 64 KiB
 
 
 class Model:

@@ -12,8 +12,6 @@ indexing and bounds (a guard region follows every buffer), not timing or the mem
 What the model adds to common.h for this unit: a fixed-size array in place of the matching kernel's dynamic LDS."""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -25,37 +23,15 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _coco_eval_ref as K  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+import _model  # noqa: E402
+from _model import GUARD  # noqa: E402
 
-PRELUDE = '''#include "common.h"
-#include <cstdint>
-#undef EFFDET_EINVAL
-#define EFFDET_EINVAL (-22)
-using std::min; using std::floor; using std::fabs;
-'''
-DYNAMIC_LDS = 'extern __shared__ double cc_lds[];'
-GUARD = 64
 NAMES = ('effdet_coco_match', 'effdet_coco_append', 'effdet_coco_sorted_workspace_bytes', 'effdet_coco_sorted_offset',
          'effdet_coco_sorted_result_bytes', 'effdet_coco_sorted')
 
 
 def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for header in ('compact.h', 'radix_sort.h', 'eval_match.h', 'eval_sorted.h'):                            # included by the unit
-        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
-    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'coco_eval.hip')).read()
-    assert src.count(DYNAMIC_LDS) == 1
-    src = src.replace(DYNAMIC_LDS, 'static double cc_lds[8192];')
-    with open(os.path.join(tmp, 'coco_eval.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'libcoco_eval_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-o', out,
-                    os.path.join(tmp, 'coco_eval.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name in NAMES:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+    return _model.build(tmp, 'coco_eval', NAMES, lds=('extern __shared__ double cc_lds[];', 'static double cc_lds[8192];'))
 
 
 def ptr(a):

@@ -12,8 +12,6 @@ arithmetic, indexing and bounds (a guard region follows every buffer), not timin
 What the model adds to common.h for this unit: a fixed-size array in place of the matching kernel's dynamic LDS."""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -25,16 +23,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _eval_open_ref as O  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+import _model  # noqa: E402
+from _model import GUARD  # noqa: E402
 
-PRELUDE = '''#include "common.h"
-#include <cstdint>
-#undef EFFDET_EINVAL
-#define EFFDET_EINVAL (-22)
-using std::min; using std::floor; using std::fabs;
-'''
-DYNAMIC_LDS = 'extern __shared__ int sh[];'
-GUARD = 64
 NAMES = ('effdet_eval_match_multi', 'effdet_eval_open_words', 'effdet_eval_append_open', 'effdet_eval_open_sorted_workspace_bytes',
          'effdet_eval_open_sorted_offset', 'effdet_eval_open_sorted_result_bytes', 'effdet_eval_open_sorted',
          'effdet_eval_ap_sorted_workspace_bytes', 'effdet_eval_ap_sorted_result_bytes', 'effdet_eval_ap_sorted', 'effdet_eval_append',
@@ -42,22 +33,7 @@ NAMES = ('effdet_eval_match_multi', 'effdet_eval_open_words', 'effdet_eval_appen
 
 
 def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for header in ('compact.h', 'radix_sort.h', 'eval_match.h', 'eval_sorted.h'):                            # included by the unit
-        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
-    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'eval_scale.hip')).read()
-    assert src.count(DYNAMIC_LDS) == 1
-    src = src.replace(DYNAMIC_LDS, 'static int sh[16384];')
-    with open(os.path.join(tmp, 'eval_scale.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'libeval_scale_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-o', out,
-                    os.path.join(tmp, 'eval_scale.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name in NAMES:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+    return _model.build(tmp, 'eval_scale', NAMES, lds=('extern __shared__ int sh[];', 'static int sh[16384];'))
 
 
 def ptr(a):

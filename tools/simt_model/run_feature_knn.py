@@ -8,8 +8,6 @@ memory model.
     python3 tools/simt_model/run_feature_knn.py     needs g++ with C++20 (std::barrier); a thread per lane, so minutes"""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -21,45 +19,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _feature_knn_ref as R  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
-
-PRELUDE = ('#include "common.h"\n#include "effdet_hip.h"\n'
-           '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
-GUARD = 64
-CSRC = os.path.join(ROOT, 'ood_object_detection_amd', 'csrc')
-
-
-def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    shutil.copy(os.path.join(CSRC, 'feature_rows.h'), tmp)
-    shutil.copy(os.path.join(CSRC, 'compact.h'), tmp)
-    src = open(os.path.join(CSRC, 'feature_knn.hip')).read()
-    with open(os.path.join(tmp, 'feature_knn.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'libfeature_knn_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-Wno-unknown-pragmas',
-                    '-I', os.path.join(ROOT, 'include'), '-o', out, os.path.join(tmp, 'feature_knn.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if name.startswith('effdet_feature_knn_'):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data
+from _model import GUARD, build, guarded, ptr  # noqa: E402
 
 
 def lls(v):
     return (ctypes.c_longlong * len(v))(*[int(x) for x in v])
-
-
-def guarded(shape, dtype, fill):
-    """(view of `shape`, the whole buffer with GUARD trailing sentinels)"""
-    n = int(np.prod(shape))
-    whole = np.full(n + GUARD, fill, dtype)
-    return whole[:n].reshape(shape), whole
 
 
 def table(levels):
@@ -227,7 +191,7 @@ def run(lib, F, C, normalize):
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        lib = build(tmp)
+        lib = build(tmp, 'feature_knn', 'effdet_feature_knn_')
         run(lib, 64, 7, True)
         run(lib, 88, 0, False)
         run(lib, 88, 3, True)

@@ -8,8 +8,6 @@ checks arithmetic, indexing and bounds (a guard region follows every buffer), no
                                                             (--wide: also F = 288, several minutes more)"""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -21,44 +19,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _feature_ood_ref as R  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
-
-PRELUDE = ('#include "common.h"\n#include "effdet_hip.h"\n'
-           '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
-GUARD = 64
-
-
-def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'feature_rows.h'), tmp)      # included by the unit
-    shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'compact.h'), tmp)
-    src =open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'feature_ood.hip')).read()
-    with open(os.path.join(tmp, 'feature_ood.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'libfeature_ood_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-Wno-unknown-pragmas',
-                    '-I', os.path.join(ROOT, 'include'), '-o', out, os.path.join(tmp, 'feature_ood.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if name.startswith('effdet_feature_ood_'):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data
+from _model import GUARD, build, guarded, ptr  # noqa: E402
 
 
 def lls(v):
     return (ctypes.c_longlong * len(v))(*[int(x) for x in v])
-
-
-def guarded(shape, dtype, fill):
-    """(view of `shape`, the whole buffer with GUARD trailing sentinels)"""
-    n = int(np.prod(shape))
-    whole = np.full(n + GUARD, fill, dtype)
-    return whole[:n].reshape(shape), whole
 
 
 class Model:
@@ -204,7 +169,7 @@ def run(lib, F, C, n_fit=300, n_score=70):
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        lib = build(tmp)
+        lib = build(tmp, 'feature_ood', 'effdet_feature_ood_')
         run(lib, 64, 1)
         run(lib, 88, 7)
         run(lib, 64, 90, n_fit=600)

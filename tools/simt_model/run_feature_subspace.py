@@ -7,8 +7,6 @@ bounds (a guard region follows every buffer), not timing or the memory model.
     python3 tools/simt_model/run_feature_subspace.py     needs g++ with C++20 (std::barrier); a thread per lane: about half a minute"""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -20,47 +18,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _feature_subspace_ref as R  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+from _model import GUARD, build, guarded, ptr  # noqa: E402
 from ood_object_detection_amd.ood_features import finalize_subspace  # noqa: E402
 
-PRELUDE = ('#include "common.h"\n#include "effdet_hip.h"\n'
-           '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
-GUARD = 64
-CSRC = os.path.join(ROOT, 'ood_object_detection_amd', 'csrc')
 A = 3
-
-
-def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    shutil.copy(os.path.join(CSRC, 'feature_rows.h'), tmp)       # included by the unit
-    shutil.copy(os.path.join(CSRC, 'compact.h'), tmp)
-    src = open(os.path.join(CSRC, 'feature_subspace.hip')).read()
-    with open(os.path.join(tmp, 'feature_subspace.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'libfeature_subspace_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-Wno-unknown-pragmas',
-                    '-I', os.path.join(ROOT, 'include'), '-o', out, os.path.join(tmp, 'feature_subspace.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if name.startswith('effdet_feature_subspace_'):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data
 
 
 def lls(v):
     return (ctypes.c_longlong * len(v))(*[int(x) for x in v])
-
-
-def guarded(shape, dtype, fill):
-    """(view of `shape`, the whole buffer with GUARD trailing sentinels)"""
-    n = int(np.prod(shape))
-    whole = np.full(n + GUARD, fill, dtype)
-    return whole[:n].reshape(shape), whole
 
 
 def table(levels):
@@ -217,7 +182,7 @@ def refusals(lib):
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        lib = build(tmp)
+        lib = build(tmp, 'feature_subspace', 'effdet_feature_subspace_')
         refusals(lib)
         for F in (64, 88):
             for Rn in (1, 44, F):

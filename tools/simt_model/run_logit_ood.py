@@ -5,10 +5,7 @@ T in {1, 2.5} - against the restatement of tests/_logit_ood_ref.py.  It checks a
 follows every buffer), not timing or the memory model.
 
     python3 tools/simt_model/run_logit_ood.py [C T top_m]    needs g++ with C++20 (std::barrier); a thread per lane: about five minutes"""
-import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -20,43 +17,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _logit_ood_ref as R  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+from _model import GUARD, build, guarded, ptr  # noqa: E402
 from ood_object_detection_amd.ood_logits import finalize  # noqa: E402
 
-PRELUDE = ('#include "common.h"\n#include "effdet_hip.h"\n'
-           '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
-GUARD = 64
-CSRC = os.path.join(ROOT, 'ood_object_detection_amd', 'csrc')
 FILL = -12345.5
-
-
-def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    shutil.copy(os.path.join(CSRC, 'feature_rows.h'), tmp)       # included by the unit
-    shutil.copy(os.path.join(CSRC, 'compact.h'), tmp)
-    src = open(os.path.join(CSRC, 'logit_ood.hip')).read()
-    with open(os.path.join(tmp, 'logit_ood.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'liblogit_ood_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-Wno-unknown-pragmas',
-                    '-I', os.path.join(ROOT, 'include'), '-o', out, os.path.join(tmp, 'logit_ood.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if name.startswith('effdet_logit_ood_'):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data
-
-
-def guarded(shape, dtype, fill):
-    """(view of `shape`, the whole buffer with GUARD trailing sentinels)"""
-    n = int(np.prod(shape))
-    whole = np.full(n + GUARD, fill, dtype)
-    return whole[:n].reshape(shape), whole
 
 
 class Model:
@@ -240,7 +204,7 @@ def refusals(lib):
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        lib = build(tmp)
+        lib = build(tmp, 'logit_ood', 'effdet_logit_ood_')
         refusals(lib)
         if len(sys.argv) == 4:                                   # one case of the caller's: C T top_m
             run(lib, int(sys.argv[1]), float(sys.argv[2]), int(sys.argv[3]))

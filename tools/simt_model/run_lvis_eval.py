@@ -9,10 +9,7 @@ included.  It checks arithmetic, indexing and bounds, not timing or the memory m
     python3 tools/simt_model/run_lvis_eval.py [--quick]    needs g++ with C++20 (std::barrier); minutes, a thread per lane
 
 What the model adds to common.h for this unit: a fixed-size array in place of the kernel's dynamic LDS."""
-import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -26,30 +23,12 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _lvis_eval_ref as L  # noqa: E402
 import run_coco_eval as RC  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
-
-DYNAMIC_LDS = 'extern __shared__ double lv_lds[];'
-NAMES = ('effdet_lvis_match', 'effdet_lvis_match_lds_bytes')
-GUARD = RC.GUARD
+import _model  # noqa: E402
+from _model import GUARD  # noqa: E402
 
 
 def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for header in ('compact.h', 'eval_match.h'):                                                  # included by the unit
-        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
-    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'lvis_eval.hip')).read()
-    assert src.count(DYNAMIC_LDS) == 1
-    src = src.replace(DYNAMIC_LDS, 'static double lv_lds[8192];')                                 # 64 KiB
-    with open(os.path.join(tmp, 'lvis_eval.cpp'), 'w') as f:
-        f.write(RC.PRELUDE + src)
-    out = os.path.join(tmp, 'liblvis_eval_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-o', out,
-                    os.path.join(tmp, 'lvis_eval.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name in NAMES:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+    return _model.build(tmp, 'lvis_eval', 'effdet_lvis_match', lds=('extern __shared__ double lv_lds[];', 'static double lv_lds[8192];'))   # 64 KiB
 
 
 def guarded_copy(a, fill):

@@ -7,10 +7,7 @@ buffer), not timing or the memory model.
 
     python3 tools/simt_model/run_ood_eval.py [--quick]    needs g++ with C++20 (std::barrier); ten minutes or so, a thread per lane
                                                           (--quick: without the tile-boundary, tie and digit shapes)"""
-import ctypes
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -22,30 +19,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _ood_eval_ref as R  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+from _model import GUARD, build  # noqa: E402
 
-PRELUDE = ('#include "common.h"\n'
-           '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
-GUARD = 64
 SENTINEL = np.float32(-12345.5)
-
-
-def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for header in ('compact.h', 'radix_sort.h'):                                                 # included by the unit
-        shutil.copy(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', header), tmp)
-    src = open(os.path.join(ROOT, 'ood_object_detection_amd', 'csrc', 'ood_eval.hip')).read()
-    with open(os.path.join(tmp, 'ood_eval.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'libood_eval_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-o', out,
-                    os.path.join(tmp, 'ood_eval.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if name.startswith('effdet_ood_eval_'):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    return lib
 
 
 def ptr(a, offset=0):
@@ -124,7 +100,7 @@ def bits(b, sign, rs, n):
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        lib = build(tmp)
+        lib = build(tmp, 'ood_eval', 'effdet_ood_eval_')
         T = lib.effdet_ood_eval_sort_tile()
         rs = np.random.RandomState(0)
         check(lib, 'one each, >', [1.0], [0.5])

@@ -6,10 +6,8 @@ against the restatement of tests/_outlier_synth_ref.py under its bound.  It chec
 follows every buffer), not timing or the memory model.
 
     python3 tools/simt_model/run_outlier_synth.py    needs g++ with C++20 (std::barrier); a thread per lane: a few minutes"""
-import ctypes
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -21,41 +19,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _outlier_synth_ref as R  # noqa: E402
-from ood_object_detection_amd import _lib  # noqa: E402
+from _model import GUARD, build, guarded, ptr  # noqa: E402
 
-PRELUDE = ('#include "common.h"\n#include "effdet_hip.h"\n'
-           '#undef EFFDET_EINVAL\n#define EFFDET_EINVAL (-22)\n')
-GUARD = 64
-CSRC = os.path.join(ROOT, 'ood_object_detection_amd', 'csrc')
 FILL = -12345.5
-
-
-def build(tmp):
-    shutil.copy(os.path.join(HERE, 'common.h'), tmp)
-    for h in ('compact.h', 'radix_sort.h'):                      # included by the unit
-        shutil.copy(os.path.join(CSRC, h), tmp)
-    src = open(os.path.join(CSRC, 'outlier_synth.hip')).read()
-    with open(os.path.join(tmp, 'outlier_synth.cpp'), 'w') as f:
-        f.write(PRELUDE + src)
-    out = os.path.join(tmp, 'liboutlier_synth_model.so')
-    subprocess.run(['g++', '-std=c++20', '-O1', '-fPIC', '-shared', '-pthread', '-ffp-contract=off', '-Wno-attributes', '-Wno-unknown-pragmas',
-                    '-I', os.path.join(ROOT, 'include'), '-o', out, os.path.join(tmp, 'outlier_synth.cpp')], check=True)
-    lib = ctypes.CDLL(out)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if name.startswith('effdet_outlier_synth'):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data
-
-
-def guarded(shape, dtype, fill):
-    n = int(np.prod(shape))
-    whole = np.full(n + GUARD, fill, dtype)
-    return whole[:n].reshape(shape), whole
 
 
 def call(lib, F, C, ids, S, k, seed, t, mu, L, valid, advance=1):
@@ -123,7 +89,7 @@ def check(lib, F, C, S, k, seed, t, ids=None, invalid=()):
 def main():
     tmp = tempfile.mkdtemp(prefix='simt_outlier_synth_')
     try:
-        lib = build(tmp)
+        lib = build(tmp, 'outlier_synth', 'effdet_outlier_synth')
         t = (3 << 32) | 5
         check(lib, 8, 1, 1, 1, 1, 0)
         check(lib, 64, 2, 63, 4, 1, t)
