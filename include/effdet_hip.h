@@ -1223,6 +1223,48 @@ int effdet_energy_reg(void* stream, int dtype, const void* logits, const signed 
 /* bytes of the workspace for `rows` = B * N rows (pure host code; -22 for a bad argument) */
 long long effdet_energy_reg_workspace_bytes(long long rows);
 
+/* ---- von Mises-Fisher hyperspherical OOD head (csrc/vmf.hip; SIREN, Du et al. 2022) ------------------------------------------------
+ * U [B][P][d] float32 (contiguous) is the embedding of every pyramid cell, 2 <= d <= 256; prototypes [C][d] float32 and valid [C]
+ * int32 are the unit class means and whether a class has received a row; 1 <= C <= 1024.  A dense label map [B][K = A * P]
+ * (classes_dtype 0 int32, 1 int64, 2 float32; element (b, j) at b * pitch + j * stride) names the class of anchor j, which sits on
+ * cell j / A; an entry counts when its label less class_offset lies in [0, C) and its cell's row holds finite values only.
+ *   n = max(sqrt(sum u_k^2), 1e-12), r = u / n        (float32; lane t of 64 adds elements t, t + 64, .. then the xor tree 32 .. 1)
+ * effdet_vmf_partition: theta [C] float32 -> kappa = float32(exp(clamp(theta, log 2^-7, log 2^13))) [C] float32, logZ [C] float32
+ *   and float64, logZ = (d / 2 - 1) log kappa - (d / 2) log(2 pi) - log I_{d/2-1}(kappa), ratio [C] float64 = I_{d/2} / I_{d/2-1}
+ *   at kappa, clamped [C] int32 = 1 where theta lies outside the clamp (or is a NaN).  Float64 on the device, a thread per class.
+ * effdet_vmf_update: per class c, its counted rows in (b, j) order, at most rows_per_class of them (0: all):
+ *   v = alpha * mu_c + (1 - alpha) * r, mu_c = v / max(|v|, 1e-12); valid[c] = 1 once a row arrived.  0 <= alpha <= 1.
+ * effdet_vmf_loss: over the entries that count and whose class is valid, l_c = logZ_c + kappa_c (mu_c . r) over the valid classes,
+ *   loss [1] float32 = (1 / max(m, 1)) sum_i (logsumexp_c l_ic - l_iy), dU [B][P][d] float32 = d loss / d U (zero in every other cell;
+ *   the counted anchors of a cell added in ascending order), dtheta [C] float32 = d loss / d theta (0 where clamped),
+ *   stats [8] float64 = m, rows skipped as non-finite, valid classes, mean mu_y . r, mean kappa, max kappa, the loss in float64, 0.
+ *   The prototypes are constants.  Sums over rows are float64 in an order that follows from B * K alone.
+ * effdet_vmf_score: entry (b, j) of a [B][K] call is the cell anchor_index[b][j] / A (NULL: j / A) and counts when j < count[b]
+ *   (NULL: all) and the anchor lies in [0, A * P); gathered != 0: U is [B][K][d], the row of entry (b, j) is row j.  vmf = max_c l_c,
+ *   vmf_class (int64) the lowest class that attains it, vmf_cosine = max_c mu_c . r; 0, -1, 0 for an entry that does not count or
+ *   without a valid class; NaN, -1, NaN for a non-finite row.  rows [B][K][d] or NULL: r (zeros where the entry does not count).
+ * effdet_vmf_gather: out [B * K][F] float32 = the tower rows (level table as in effdet_feature_ood_*; float32 or bfloat16 widened
+ *   exactly; F a BiFPN width) of the selected anchors, zeros where the entry does not count.
+ * The workspace (effdet_vmf_workspace_bytes(B * K, C, d)) is scratch.  Bad arguments return -22 before any launch; no call
+ * synchronises with the host or allocates; no floating-point atomics; results are bit-identical from run to run. */
+long long effdet_vmf_workspace_bytes(long long rows, int C, int d);
+int effdet_vmf_partition(void* stream, const float* theta, int C, int d, float* kappa, float* logz, double* logz64, double* ratio,
+                         int* clamped);
+int effdet_vmf_update(void* stream, const float* U, int B, long long P, int A, int d, const void* classes, int classes_dtype,
+                      long long classes_pitch, long long classes_stride, long long class_offset, int C, float alpha,
+                      long long rows_per_class, float* prototypes, int* valid, void* workspace, long long workspace_bytes);
+int effdet_vmf_loss(void* stream, const float* U, int B, long long P, int A, int d, const void* classes, int classes_dtype,
+                    long long classes_pitch, long long classes_stride, long long class_offset, int C, const float* prototypes,
+                    const int* valid, const float* kappa, const float* logz, const double* ratio, const int* clamped, float* loss,
+                    double* stats, float* dU, float* dtheta, void* workspace, long long workspace_bytes);
+int effdet_vmf_score(void* stream, const float* U, int B, long long P, int A, int d, long long K, const long long* anchor_index,
+                     const void* count, int count_is_int64, int gathered, int C, const float* prototypes, const int* valid,
+                     const float* kappa, const float* logz, float* vmf, long long* vmf_class, float* vmf_cosine, float* rows,
+                     void* workspace, long long workspace_bytes);
+int effdet_vmf_gather(void* stream, int dtype, int num_levels, const void* const* bases, const long long* cells,
+                      const long long* batch_strides, const long long* cell_strides, const long long* channel_strides, int F, int A,
+                      int B, long long K, const long long* anchor_index, const void* count, int count_is_int64, float* out);
+
 /* ---- virtual outlier synthesis (csrc/outlier_synth.hip): sample the class-conditional Gaussians, keep the least likely ------------
  * For each of the n classes c = class_ids[ci] (device int32 [n]; NULL: c = ci) draw S candidates x = mu_c + L eps, eps ~ N(0, I_F),
  * and keep the k with the largest |eps|^2, which is the Mahalanobis distance of x: the least likely ones.  eps comes from

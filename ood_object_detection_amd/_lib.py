@@ -126,6 +126,16 @@ SIGNATURES = {
                                   c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_ll]),
     'effdet_energy_reg_workspace_bytes': (c_ll, [c_ll]),
+    'effdet_vmf_workspace_bytes': (c_ll, [c_ll, c_int, c_int]),
+    'effdet_vmf_partition': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'effdet_vmf_update': (c_int, [c_void_p, c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_int, c_ll, c_ll, c_ll, c_int, c_float, c_ll,
+                                  c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_vmf_loss': (c_int, [c_void_p, c_void_p, c_int, c_ll, c_int, c_int, c_void_p, c_int, c_ll, c_ll, c_ll, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_vmf_score': (c_int, [c_void_p, c_void_p, c_int, c_ll, c_int, c_int, c_ll, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),
+    'effdet_vmf_gather': (c_int, [c_void_p, c_int, c_int, P(c_void_p), P(c_ll), P(c_ll), P(c_ll), P(c_ll), c_int, c_int, c_int, c_ll,
+                                  c_void_p, c_void_p, c_int, c_void_p]),
     'effdet_outlier_synth_workspace_bytes': (c_ll, [c_int, c_ll]),
     'effdet_outlier_synth': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_ll, c_int, ctypes.c_ulonglong, c_void_p, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll]),

@@ -29,7 +29,7 @@ def set_bn_eval(module):
 class PretrainStep(object):
     def __init__(self, model, lr=1e-3, max_grad_norm=10.0, alpha=0.15, box_loss_weight=50.0, freeze_bn=False,
                  labeler=True, graph=False, graph_warmup=2, optimizer=None, ood_regularizer=None, ood_background='none',
-                 outlier_synthesizer=None, synth_refresh_every=100, synth_shrinkage=0.0):
+                 outlier_synthesizer=None, synth_refresh_every=100, synth_shrinkage=0.0, vmf_head=None, vmf_weight=1.5):
         """graph=True: after `graph_warmup` eager iterations the whole iteration (zero_grad, forward, loss, backward and -
         single GPU - clip + Adam) is captured into one hipGraph and replayed; the ~5 000 launches of a step then cost one
         submission.  Shapes must stay fixed; labels are assigned eagerly and copied into the graph's static buffers.
@@ -46,7 +46,11 @@ class PretrainStep(object):
         `FeatureOOD.fit`; once a fit exists the regulariser's term is `ood_train.virtual_outlier_loss`, the virtual rows pushed
         through class_net.predict.conv_pw, and the returned dict gains n_virtual, mean_l_virtual and mean_energy_virtual.
         target['outlier'] is then optional (default: no outlier image).  With graph=True the steps before the first fit run
-        eagerly; the capture holds the virtual side and reads a later fit from the buffers `fit` writes in place."""
+        eagerly; the capture holds the virtual side and reads a later fit from the buffers `fit` writes in place.
+        vmf_head: an `ood_vmf.VMFHead` (SIREN, Du et al. 2022).  The engine's fpn-and-heads node then also returns the class tower
+        (`TrainEngine.tower_output`), the head embeds it, updates its prototypes from the step's labels and adds
+        `vmf_weight` times its vMF loss, whose gradient reaches the class tower and the BiFPN; the returned dict gains 'vmf_loss'
+        and the head's statistics as 'vmf_m', 'vmf_skipped', ...  The default FlatAdam also covers the head's parameters."""
         from .effdet.anchors import Anchors, AnchorLabeler
         from .effdet.config import set_config_writeable
         from .effdet.loss import DetectionLoss
@@ -71,14 +75,21 @@ class PretrainStep(object):
             pw = model.class_net.predict.conv_pw
             if (self.synth.C, self.synth.F) != (cfg.num_classes, pw.weight.shape[1]) or pw.weight.shape[0] != self.synth.A * self.synth.C:
                 raise ValueError('the outlier_synthesizer must have the class head\'s num_classes, width and anchors per cell')
+        self.vmf, self.vmf_weight = vmf_head, float(vmf_weight)
+        if self.vmf is not None:
+            pw = model.class_net.predict.conv_pw
+            if (self.vmf.C, self.vmf.F) != (cfg.num_classes, pw.weight.shape[1]) or pw.weight.shape[0] != self.vmf.A * self.vmf.C:
+                raise ValueError('the vmf_head must have the class head\'s num_classes, width and anchors per cell')
+        self._cap_vmf = None
         self._synth_steps = 0                   # steps since the synthesiser was given: fit after every synth_refresh_every-th
         self._synth_eager = 0                   # eager steps that ran the virtual side (one comes before a capture)
         if self._grouped:
             self.opt = optimizer
-        elif self.ood is None:
+        elif self.ood is None and self.vmf is None:
             self.opt = FlatAdam(model.parameters(), lr=lr, max_grad_norm=max_grad_norm)
         else:
-            self.opt = FlatAdam(list(model.parameters()) + list(self.ood.parameters()), lr=lr, max_grad_norm=max_grad_norm)
+            extra = ([] if self.ood is None else list(self.ood.parameters())) + ([] if self.vmf is None else list(self.vmf.parameters()))
+            self.opt = FlatAdam(list(model.parameters()) + extra, lr=lr, max_grad_norm=max_grad_norm)
         self.anchors = Anchors.from_config(cfg).to(model.backbone.conv_stem.weight.device)
         self.labeler = AnchorLabeler(self.anchors, cfg.num_classes, match_threshold=0.5) if labeler else None
         self.num_levels = cfg.num_levels
@@ -128,6 +139,11 @@ class PretrainStep(object):
         from .ood_train import virtual_outlier_loss
         pw = self.model.class_net.predict.conv_pw
         return virtual_outlier_loss(self.ood, class_out, roles, self.synth, pw.weight, pw.bias)
+
+    def _vmf_terms(self, cls_t):
+        """with a vmf_head: its weighted loss on the differentiable class tower of the forward just run, and its statistics"""
+        vmf_loss, stats = self.vmf(self.model._train_engine.class_tower, cls_t)
+        return self.vmf_weight * vmf_loss, dict({'vmf_' + k: v for k, v in stats.items()}, vmf_loss=vmf_loss.detach())
 
     def _synth_refresh(self):
         if self.synth is not None:
@@ -193,6 +209,10 @@ class PretrainStep(object):
                 ood_loss, ood_stats = self._ood_terms(class_out, s_cls, s_roles)
                 loss = loss + ood_loss
                 ood = dict(ood_stats, ood_loss=ood_loss.detach())
+            vmf = None
+            if self.vmf is not None:
+                vmf_term, vmf = self._vmf_terms(s_cls)
+                loss = loss + vmf_term
             loss.backward()
             # a GroupedOptimizer's step() records only its launches under capture: its step counts live on the device
             step_captured = opt.step if self._grouped else opt.step_captured
@@ -206,6 +226,7 @@ class PretrainStep(object):
         del feats, class_out, box_out, loss
         self._cap = (g1, g2, (sx, s_cls, s_box, s_np), outs)
         self._cap_ood = (s_roles, ood)
+        self._cap_vmf = vmf
 
     def _replay(self, x, cls_t, box_t, npos, time_allreduce, roles=None):
         g1, g2, (sx, s_cls, s_box, s_np), outs = self._cap
@@ -243,6 +264,8 @@ class PretrainStep(object):
                'grad_norm': None if outs[3] is None else outs[3].clone()}
         if roles is not None:
             res.update({k: v.clone() for k, v in self._cap_ood[1].items()})
+        if self._cap_vmf is not None:
+            res.update({k: v.clone() for k, v in self._cap_vmf.items()})
         self._synth_refresh()
         return res
 
@@ -265,6 +288,8 @@ class PretrainStep(object):
             eng.direct_grad = True          # FlatAdam owns every .grad (views of one flat buffer): add into them directly
             if self.synth is not None:
                 eng.keep_penultimate = True
+            if self.vmf is not None:
+                eng.tower_output = True
 
     def __call__(self, x, target, time_allreduce=False, evaluator=None):
         model, opt = self.model, self.opt
@@ -306,6 +331,10 @@ class PretrainStep(object):
             ood = dict(ood_stats, ood_loss=ood_loss.detach())
             if self.synth is not None and self.synth.fitted:
                 self._synth_eager += 1
+        vmf = None
+        if self.vmf is not None:
+            vmf_term, vmf = self._vmf_terms(cls_t)
+            loss = loss + vmf_term
         loss.backward()
         if evaluator is not None:
             self.evaluate(class_out, box_out, target, evaluator)
@@ -316,5 +345,7 @@ class PretrainStep(object):
         res = {'loss': loss.detach(), 'class_loss': class_loss, 'box_loss': box_loss, 'grad_norm': norm}
         if ood is not None:
             res.update(ood)
+        if vmf is not None:
+            res.update(vmf)
         self._synth_refresh()
         return res

@@ -507,6 +507,14 @@ class TrainEngine(object):
         self.direct_grad = False        # True: parameter gradients are added into existing `.grad`s by one multi-tensor launch
         self.keep_penultimate = False   # True: the class head's forward leaves the input of its last pointwise map (class_penultimate)
         self._penultimate = None
+        # True: the fpn-and-heads autograd node also returns the packed output of the class tower (the input of class_net.predict)
+        # as a differentiable output; `class_tower` then holds its per-level [B, F, h, w] views (ood_vmf.VMFHead trains through it).
+        # Lifetime: `class_tower` and `_tower_lv` belong to the LAST forward and stay on the engine until the next one replaces them,
+        # also after that forward's backward has dropped its saved state - one packed tower (B * P * F floats) stays resident with
+        # the flag on.  They are not cleared by the backward, because a later forward's views must survive an earlier graph's backward.
+        self.tower_output = False
+        self.class_tower = None
+        self._tower_lv = None
 
     def _const(self, C, v):
         key = (C, v)
@@ -784,10 +792,13 @@ class TrainEngine(object):
             return self._fh_forward(feats, want_cls, want_box, want_pyr)
         return self._in_stage(stage, run)
 
-    def fh_backward(self, g_cls, g_box, saved, need_dfeats=True, g_pyr=None, stage='fh'):
-        """g_pyr: d loss / d pyramid level (NHWC, None allowed per level), added to what the heads send down.
+    def fh_backward(self, g_cls, g_box, saved, need_dfeats=True, g_pyr=None, stage='fh', g_tower=None):
+        """g_pyr: d loss / d pyramid level (NHWC, None allowed per level), added to what the heads send down.  g_tower: d loss / d
+        packed class tower (`tower_output`), added to the input gradient of the class head's predict layer.
         -> (d feats list (NHWC), {param name: grad})"""
-        return self._in_stage(stage, self._fh_backward, g_cls, g_box, saved, need_dfeats, g_pyr)
+        if g_tower is None:
+            return self._in_stage(stage, self._fh_backward, g_cls, g_box, saved, need_dfeats, g_pyr)
+        return self._in_stage(stage, self._fh_backward, g_cls, g_box, saved, need_dfeats, g_pyr, g_tower)
 
     def nc_forward(self, feats):
         """mode='not_cls' (efficientdet.py:905-908): BiFPN + box head.  -> (pyramid NHWC list, box_all [B,N,4], saved)"""
@@ -1113,8 +1124,10 @@ class TrainEngine(object):
         lv, d, t = self._penultimate
         return [v.permute(0, 3, 1, 2) for v in lv.split((t if tower else d).detach())]
 
-    def _head_bwd(self, lv, hrec, g, grads):
-        """-> d packed pyramid [B * P, F]; parameter gradients into `grads` (conv weights: one reduction over all levels)"""
+    def _head_bwd(self, lv, hrec, g, grads, g_tower=None):
+        """-> d packed pyramid [B * P, F]; parameter gradients into `grads` (conv weights: one reduction over all levels).  g_tower:
+        a gradient that arrived for the tower's output itself, added to `da` of the predict layer (g may then be None: the predict
+        layer gets no gradient)"""
         ops, name, NO = self.ops, hrec['name'], hrec['NO']
         L = lv.L
 
@@ -1124,12 +1137,17 @@ class TrainEngine(object):
 
         rec = hrec['predict']
         F = rec['W'].shape[1]
-        dW, dsum = ops.gemm_tn_levels(lv, g, rec['d'], NO, F, y_packed=True, pk=rec['pk'])
-        grads[name + 'predict.conv_pw.weight'] = dW.reshape(rec['wshape'])
-        if rec['has_bias']:
-            grads[name + 'predict.conv_pw.bias'] = dsum
-        dd = ops.gemm_nt_levels(lv, g, rec['Wt'], a_packed=True, pk=rec['pk'])
-        da = dw_grads(rec, dd, name + 'predict.')
+        da = None
+        if g is not None:
+            dW, dsum = ops.gemm_tn_levels(lv, g, rec['d'], NO, F, y_packed=True, pk=rec['pk'])
+            grads[name + 'predict.conv_pw.weight'] = dW.reshape(rec['wshape'])
+            if rec['has_bias']:
+                grads[name + 'predict.conv_pw.bias'] = dsum
+            dd = ops.gemm_nt_levels(lv, g, rec['Wt'], a_packed=True, pk=rec['pk'])
+            da = dw_grads(rec, dd, name + 'predict.')
+        if g_tower is not None:
+            gt = g_tower.contiguous()
+            da = gt if da is None else ops.add(da, gt)
         for rec in reversed(hrec['reps']):
             r, st = rec['r'], rec['st']
             N = rec['W'].shape[0]
@@ -1148,7 +1166,7 @@ class TrainEngine(object):
             da = dw_grads(rec, dd, '%sconv_rep.%d.' % (name, r))
         return da
 
-    def _fh_backward(self, g_cls, g_box, saved, need_dfeats=True, g_pyr=None):
+    def _fh_backward(self, g_cls, g_box, saved, need_dfeats=True, g_pyr=None, g_tower=None):
         """-> (d feats list (NHWC), {param name: grad})"""
         ops, L = self.ops, self.L
         grads = {}
@@ -1163,9 +1181,10 @@ class TrainEngine(object):
         lv = saved['lv']
         dpyr = None
         for hi in range(2):
-            if saved['heads'][hi] is None or gs[hi] is None:
+            gt = g_tower if hi == 0 else None
+            if saved['heads'][hi] is None or (gs[hi] is None and gt is None):
                 continue
-            da = self._head_bwd(lv, saved['heads'][hi], gs[hi], grads)
+            da = self._head_bwd(lv, saved['heads'][hi], gs[hi], grads) if gt is None else self._head_bwd(lv, saved['heads'][hi], gs[hi], grads, gt)
             dpyr = da if dpyr is None else ops.add(dpyr, da)
         if dpyr is not None:
             for l, d in enumerate(lv.split(dpyr)):
@@ -1259,11 +1278,19 @@ class FpnHeadFn(torch.autograd.Function):
         feats = [t.contiguous() for t in tensors[:n_feats]]
         cls_all, box_all, saved = eng.fh_forward(feats)
         ctx.eng, ctx.saved, ctx.names, ctx.n_feats, ctx.params = eng, saved, names, n_feats, tensors[n_feats:]
+        if eng.tower_output and saved['heads'][0] is not None:
+            # opt-in third output: the packed class tower.  An output the loss does not read arrives as None, not as zeros
+            ctx.set_materialize_grads(False)
+            eng._tower_lv = saved['lv']
+            return cls_all, box_all, saved['heads'][0]['predict']['x']
         return cls_all, box_all
 
     @staticmethod
-    def backward(ctx, g_cls, g_box):
-        dfeats, grads = ctx.eng.fh_backward(g_cls, g_box, ctx.saved)
+    def backward(ctx, g_cls, g_box, *g_tower):
+        if g_tower:
+            dfeats, grads = ctx.eng.fh_backward(g_cls, g_box, ctx.saved, g_tower=g_tower[0])
+        else:
+            dfeats, grads = ctx.eng.fh_backward(g_cls, g_box, ctx.saved)
         ctx.saved = None
         out = [d if ctx.needs_input_grad[3 + i] else None for i, d in enumerate(dfeats)]
         return (None, None, None) + tuple(out) + tuple(_param_grads(ctx, grads, 3 + ctx.n_feats))
@@ -1315,7 +1342,9 @@ def run_fpn_heads(eng, feats_nchw):
     pl = _param_list(model.fpn, 'fpn.') + _param_list(model.class_net, 'class_net.') + _param_list(model.box_net, 'box_net.')
     names = [n for n, _ in pl]
     feats = [f.permute(0, 2, 3, 1) for f in feats_nchw]
-    cls_all, box_all = FpnHeadFn.apply(eng, names, len(feats), *(feats + [p for _, p in pl]))
+    out = FpnHeadFn.apply(eng, names, len(feats), *(feats + [p for _, p in pl]))
+    cls_all, box_all = out[0], out[1]
+    eng.class_tower = [v.permute(0, 3, 1, 2) for v in eng._tower_lv.split(out[2])] if len(out) > 2 else None
     hw = [(f.shape[2], f.shape[3]) for f in feats_nchw]
     while len(hw) < eng.L:
         hw.append((_same_out(hw[-1][0], 2), _same_out(hw[-1][1], 2)))
